@@ -17,9 +17,15 @@ reference (GRCh38/pbsim are not available offline), anchors corridor (width 309-
 Reads shard across devices with no data-path collective (tiles are independent), so the scaling
 is weak: every device aligns --tiles tiles per step; `value` is the whole-job aggregate.  Rank 0
 prints ONE JSON line.  `roofline` is the dominant fill kernel of the timed steps (HIP events on
-the stream it runs on); `device_resident` is the same step with inputs already in HBM;
-`cpu_baseline` is the reference's own ConvexAlignFast on the host cores over a bounded sample of
-the same tiles, every one of which is also compared with the GPU result (`parity`).
+the stream it runs on).
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything measured beside
+it runs only with --full: `device_resident` (the same step with inputs already in HBM),
+`cpu_baseline` (the reference's own ConvexAlignFast on the host cores over a bounded sample of the
+same tiles, every one of which is also compared with the GPU result: `parity`), the text stages,
+the other BASELINE configs, the index stage, sub-read scoring, the binding's input forms and the
+e2e pipeline.  --dump-outputs DIR writes what the last timed step handed back (result records and
+a seeded sample of the ops) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -531,6 +537,32 @@ def subread_scoring_rates(lib, dev, n=32768):
             "what": "cvx_score_batch (host strings in -> scores out, incl. the python marshalling of this bench) vs StrippedSW + ssw.c"}
 
 
+def dump_outputs(directory, job, prefix, budget, ops_tiles=1024):
+    """What a caller of the timed path (cvx_submit -> cvx_wait) receives for the job's tiles, as .npy files of at most `budget`
+    bytes in all: every cvx_result field (`result_<field>`; a fixed, seeded sample of the tiles when they do not fit in half the
+    budget, listed in `tile_index`) and the run-length ops of a fixed, seeded sample of `ops_tiles` tiles in tile order
+    (`ops_tile_index`, `ops_count`, then the ops back to back in `ops`), cut short only where the rest of the budget ends."""
+    from ngmlr_amd.aligner import RESULT_DTYPE
+    os.makedirs(directory, exist_ok=True)
+    res, ops = job.results, job.ops
+    n = len(res)
+    per_tile = 8 + sum(4 if f == "score" else 8 for f in RESULT_DTYPE.names)
+    k = min(n, budget // 2 // per_tile)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    arrays = {"tile_index": idx.astype(np.float64)}
+    for f in RESULT_DTYPE.names:
+        arrays["result_" + f] = res[f][idx].astype(np.float32 if f == "score" else np.float64)
+    sample = np.sort(np.random.default_rng(1).permutation(n)[:min(n, ops_tiles)])
+    cost = np.cumsum(16 + 8 * res["n_ops"][sample].astype(np.int64))
+    pick = sample[:int(np.searchsorted(cost, budget - k * per_tile, side="right"))]
+    begin, count = res["ops_begin"][pick].astype(np.int64), res["n_ops"][pick].astype(np.int64)
+    arrays["ops_tile_index"] = pick.astype(np.float64)
+    arrays["ops_count"] = count.astype(np.float64)
+    arrays["ops"] = np.concatenate([np.zeros(0, np.uint32)] + [ops[b:b + c] for b, c in zip(begin, count)]).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, prefix + name + ".npy"), a)
+
+
 class Worker:
     """One device: a handle, its own tiles, a pipelined stream of steps."""
 
@@ -660,7 +692,7 @@ def main() -> int:
     ap.add_argument("--depth", type=int, default=3, help="batches in flight per device")
     ap.add_argument("--read-len", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=7)
-    ap.add_argument("--resident-steps", type=int, default=3, help="extra untimed-for-`value` steps with inputs resident in HBM")
+    ap.add_argument("--resident-steps", type=int, default=3, help="--full: extra untimed-for-`value` steps with inputs resident in HBM")
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling (SURVEY 8e, config C4): ONE list of --tiles tiles, partitioned over the devices by the sum of "
                          "their cells (LPT, ngmlr_amd.shard), results restored to list order; default: weak, --tiles per device")
@@ -675,6 +707,11 @@ def main() -> int:
                          "device D: exercises the N-device path on a one-GPU box -- NOT a scaling measurement (N batches' arenas share one HBM: "
                          "use --tiles <= 16384 for N = 2)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside `value` (device-resident steps, CPU baseline + parity, text stages, "
+                         "other configs, index stage, sub-read scoring, binding input forms, e2e pipeline); the --no-* options narrow it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (result records, a seeded sample of the ops) as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -728,7 +765,7 @@ def main() -> int:
             tilesets = [synth.pacbio_tileset(args.tiles, seed=args.seed + 1000 * (rank + d), read_len=args.read_len, pool=pool)
                         for d in range(n_local)]
         extra_tiles = {}
-        if rank == 0 and args.gpus == 1 and not args.no_extras and not args.no_cpu_baseline:
+        if args.full and rank == 0 and args.gpus == 1 and not args.no_extras and not args.no_cpu_baseline:
             # the other BASELINE configs (parity cases with a rate, outside the timed region): generated here, before HIP exists
             extra_tiles["ont"] = synth.parallel_workload("ont", 60000, 11, pool)
             extra_tiles["ultralong_sv"] = synth.parallel_workload("ultralong_mix", 4096, 19, pool, chunk=16)
@@ -803,6 +840,9 @@ def main() -> int:
     sync_all()
     dt = time.perf_counter() - t0
     bases = float(sum(ts.read_bases for ts in tilesets))
+    if args.dump_outputs:
+        for i_, w in enumerate(workers):
+            dump_outputs(args.dump_outputs, w.last, "" if args.gpus == 1 else "dev%d_" % (rank if under_launcher else i_), 60_000_000 // args.gpus)
 
     def device_line(w):
         """the dominant fill launch of one device (HIP events on its stream) and that device's own timed wall"""
@@ -833,96 +873,97 @@ def main() -> int:
         n_ops_total = int(np.asarray(res["n_ops"], dtype=np.int64).sum())      # (res / ops are views of the job's buffers: gone after release)
         # outside the timed region: CPU baseline on a bounded sample + parity on every sampled tile
         cpu = parity = parity_detail = None
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             cpu, parity, parity_detail = cpu_baseline_and_parity(w0.al, ts, res, ops, args.cpu_seconds)
-        # host text stage (CIGAR/MD/NM) of a sample on all host threads: reported beside `value`
         text_stage = None
         host_txt = []
-        try:
-            from ngmlr_amd.aligner import format_tileset
-            k = min(len(ts), 2048)
-            c0 = time.perf_counter()
-            host_txt = format_tileset(w0.al.lib, ts, np.arange(k), res, ops)
-            dtxt = time.perf_counter() - c0
-            text_stage = {"Gbp_per_h": float(ts.H[:k].sum()) / dtxt * 3600.0 / 1e9, "seconds": dtxt, "tiles": k,
-                          "threads": os.cpu_count(), "what": "cvx_format_batch (CIGAR + MD + NM) incl. the python marshalling of this bench"}
-        except Exception as e:  # never let the extra measurement break the contract line
-            text_stage = {"error": str(e)}
-        # the same stage on the device (cvx_job_text): CIGAR + MD + fields of ALL tiles of the step, strings back on the host
         text_dev = None
         path_columns = None
-        try:
-            w0.last.text_raw()                                # first call allocates the job's text buffers
-            c0 = time.perf_counter()
-            trec, toff, tbuf = w0.last.text_raw()
-            dtd = time.perf_counter() - c0
-            path_columns = int(np.frombuffer(trec, dtype=np.int32).reshape(-1, 17)[:len(ts), 7].sum())      # alignment_length
-            nbad = 0
-            if text_stage and "error" not in text_stage:
-                raw = tbuf.raw
-                for i_, h_ in enumerate(host_txt):            # cross-check against the host form on its sample
-                    t_ = trec[i_]
-                    o_ = int(toff[i_])
-                    if h_["cigar"] is None or raw[o_:o_ + t_.cigar_len].decode() != h_["cigar"] or raw[o_ + t_.cigar_len + 1:o_ + t_.cigar_len + 1 + t_.md_len].decode() != h_["md"]:
-                        nbad += 1
-            text_dev = {"Gbp_per_h": float(ts.read_bases) / dtd * 3600.0 / 1e9, "seconds": dtd, "tiles": len(ts), "text_bytes": len(tbuf),
-                        "equal_to_host_form": "%d/%d" % (len(host_txt) - nbad, len(host_txt)),
-                        "what": "cvx_job_text: text_kernel (lengths + fields), offsets scan, text_kernel (strings), D2H of the dense text"}
-            # SAM record assembly (cvx_sam_batch, host pack threads) fed straight from the device text: one record per tile
+        if args.full:
+            # host text stage (CIGAR/MD/NM) of a sample on all host threads: reported beside `value`
             try:
-                import ctypes as C
-                kk = min(len(ts), 8192)
-                tab_ = ts.table()
-                base_ = C.addressof(tbuf)
-                recs_ = (capi.CvxSamRecord * kk)()
-                for i_ in range(kk):
-                    t_, r_ = trec[i_], recs_[i_]
-                    r_.read_name = b"synthetic_read"; r_.seq = C.cast(int(tab_[i_]["qry"]), C.c_char_p); r_.qual = None
-                    r_.read_length = int(tab_[i_]["qry_len"]); r_.flags = 0; r_.primary = 1; r_.reverse = 0
-                    r_.ref_name = b"chrS"; r_.ref_name_len = 4; r_.location = 1000 + t_.position_offset; r_.mq = 60
-                    r_.cigar = C.cast(base_ + int(toff[i_]), C.c_char_p); r_.md = C.cast(base_ + int(toff[i_]) + t_.cigar_len + 1, C.c_char_p)
-                    r_.cigar_op_count = t_.cigar_op_count; r_.mate_ref_name = b"*"; r_.mate_location = -1; r_.template_length = 0
-                    r_.score = t_.score; r_.nm = t_.nm; r_.identity = t_.identity; r_.qstart = t_.qstart; r_.qend = t_.qend; r_.sv_type = t_.sv_type
-                    r_.n_others = 0; r_.others = None; r_.rg_id = None; r_.hard_clip = 0; r_.bam_cigar_fix = 0; r_.skip = 0
-                offs_ = np.zeros(kk + 1, dtype=np.uint64)
-                w0.al.lib.cvx_sam_batch(kk, recs_, None, 0, offs_.ctypes.data)              # sizes
-                sam_ = C.create_string_buffer(int(offs_[kk]))
+                from ngmlr_amd.aligner import format_tileset
+                k = min(len(ts), 2048)
                 c0 = time.perf_counter()
-                rc_ = w0.al.lib.cvx_sam_batch(kk, recs_, sam_, int(offs_[kk]), offs_.ctypes.data)
-                dsam = time.perf_counter() - c0
-                valid_ = sum(1 for i_ in range(kk) if trec[i_].ret >= 0)
-                text_dev["sam_records"] = {"records": kk, "valid_alignments": valid_, "bytes": int(offs_[kk]), "seconds": dsam, "rc": rc_,
-                                           "records_per_s": kk / dsam, "GB_per_s": int(offs_[kk]) / dsam * 1e-9,
-                                           "Gbp_per_h": float(ts.H[:kk].sum()) / dsam * 3600.0 / 1e9,
-                                           "what": "cvx_sam_batch: SAMWriter::DoWriteReadGeneric's record (mandatory fields + AS NM XI XS XE XR MD SV QS QE CV) on the pack threads, CIGAR / MD taken from cvx_job_text's buffer"}
-                del sam_, recs_
-            except Exception as e:
-                text_dev["sam_records"] = {"error": str(e)}
-            # nmPerPosition on the device (cvx_job_nm_profile): kernel alone for a range that fits comfortably (12 B per column),
-            # and the same range brought to the host
+                host_txt = format_tileset(w0.al.lib, ts, np.arange(k), res, ops)
+                dtxt = time.perf_counter() - c0
+                text_stage = {"Gbp_per_h": float(ts.H[:k].sum()) / dtxt * 3600.0 / 1e9, "seconds": dtxt, "tiles": k,
+                              "threads": os.cpu_count(), "what": "cvx_format_batch (CIGAR + MD + NM) incl. the python marshalling of this bench"}
+            except Exception as e:  # never let the extra measurement break the contract line
+                text_stage = {"error": str(e)}
+            # the same stage on the device (cvx_job_text): CIGAR + MD + fields of ALL tiles of the step, strings back on the host
             try:
-                kk = min(len(ts), 4096)
-                w0.last.nm_profile(0, kk, to_host=False)
-                off_, _, kms = w0.last.nm_profile(0, kk, to_host=False)
+                w0.last.text_raw()                                # first call allocates the job's text buffers
                 c0 = time.perf_counter()
-                off_, tri_, _ = w0.last.nm_profile(0, kk, to_host=True)
-                dnm = time.perf_counter() - c0
-                ent = int(off_[kk])
-                text_dev["nm_profile"] = {"tiles": kk, "entries": ent, "kernel_ms": kms, "kernel_GB_per_s": ent * 12e-6 / max(kms, 1e-9),
-                                          "kernel_Gbp_per_h": float(ts.H[:kk].sum()) / max(kms, 1e-9) * 3.6e-3,
-                                          "to_host_seconds": dnm, "to_host_Gbp_per_h": float(ts.H[:kk].sum()) / dnm * 3600.0 / 1e9,
-                                          "what": "nm_profile_kernel (12 B per EQ/X/D column written to HBM); to_host = the same + D2H into pageable memory incl. this bench's python"}
-                del tri_
+                trec, toff, tbuf = w0.last.text_raw()
+                dtd = time.perf_counter() - c0
+                path_columns = int(np.frombuffer(trec, dtype=np.int32).reshape(-1, 17)[:len(ts), 7].sum())      # alignment_length
+                nbad = 0
+                if text_stage and "error" not in text_stage:
+                    raw = tbuf.raw
+                    for i_, h_ in enumerate(host_txt):            # cross-check against the host form on its sample
+                        t_ = trec[i_]
+                        o_ = int(toff[i_])
+                        if h_["cigar"] is None or raw[o_:o_ + t_.cigar_len].decode() != h_["cigar"] or raw[o_ + t_.cigar_len + 1:o_ + t_.cigar_len + 1 + t_.md_len].decode() != h_["md"]:
+                            nbad += 1
+                text_dev = {"Gbp_per_h": float(ts.read_bases) / dtd * 3600.0 / 1e9, "seconds": dtd, "tiles": len(ts), "text_bytes": len(tbuf),
+                            "equal_to_host_form": "%d/%d" % (len(host_txt) - nbad, len(host_txt)),
+                            "what": "cvx_job_text: text_kernel (lengths + fields), offsets scan, text_kernel (strings), D2H of the dense text"}
+                # SAM record assembly (cvx_sam_batch, host pack threads) fed straight from the device text: one record per tile
+                try:
+                    import ctypes as C
+                    kk = min(len(ts), 8192)
+                    tab_ = ts.table()
+                    base_ = C.addressof(tbuf)
+                    recs_ = (capi.CvxSamRecord * kk)()
+                    for i_ in range(kk):
+                        t_, r_ = trec[i_], recs_[i_]
+                        r_.read_name = b"synthetic_read"; r_.seq = C.cast(int(tab_[i_]["qry"]), C.c_char_p); r_.qual = None
+                        r_.read_length = int(tab_[i_]["qry_len"]); r_.flags = 0; r_.primary = 1; r_.reverse = 0
+                        r_.ref_name = b"chrS"; r_.ref_name_len = 4; r_.location = 1000 + t_.position_offset; r_.mq = 60
+                        r_.cigar = C.cast(base_ + int(toff[i_]), C.c_char_p); r_.md = C.cast(base_ + int(toff[i_]) + t_.cigar_len + 1, C.c_char_p)
+                        r_.cigar_op_count = t_.cigar_op_count; r_.mate_ref_name = b"*"; r_.mate_location = -1; r_.template_length = 0
+                        r_.score = t_.score; r_.nm = t_.nm; r_.identity = t_.identity; r_.qstart = t_.qstart; r_.qend = t_.qend; r_.sv_type = t_.sv_type
+                        r_.n_others = 0; r_.others = None; r_.rg_id = None; r_.hard_clip = 0; r_.bam_cigar_fix = 0; r_.skip = 0
+                    offs_ = np.zeros(kk + 1, dtype=np.uint64)
+                    w0.al.lib.cvx_sam_batch(kk, recs_, None, 0, offs_.ctypes.data)              # sizes
+                    sam_ = C.create_string_buffer(int(offs_[kk]))
+                    c0 = time.perf_counter()
+                    rc_ = w0.al.lib.cvx_sam_batch(kk, recs_, sam_, int(offs_[kk]), offs_.ctypes.data)
+                    dsam = time.perf_counter() - c0
+                    valid_ = sum(1 for i_ in range(kk) if trec[i_].ret >= 0)
+                    text_dev["sam_records"] = {"records": kk, "valid_alignments": valid_, "bytes": int(offs_[kk]), "seconds": dsam, "rc": rc_,
+                                               "records_per_s": kk / dsam, "GB_per_s": int(offs_[kk]) / dsam * 1e-9,
+                                               "Gbp_per_h": float(ts.H[:kk].sum()) / dsam * 3600.0 / 1e9,
+                                               "what": "cvx_sam_batch: SAMWriter::DoWriteReadGeneric's record (mandatory fields + AS NM XI XS XE XR MD SV QS QE CV) on the pack threads, CIGAR / MD taken from cvx_job_text's buffer"}
+                    del sam_, recs_
+                except Exception as e:
+                    text_dev["sam_records"] = {"error": str(e)}
+                # nmPerPosition on the device (cvx_job_nm_profile): kernel alone for a range that fits comfortably (12 B per column),
+                # and the same range brought to the host
+                try:
+                    kk = min(len(ts), 4096)
+                    w0.last.nm_profile(0, kk, to_host=False)
+                    off_, _, kms = w0.last.nm_profile(0, kk, to_host=False)
+                    c0 = time.perf_counter()
+                    off_, tri_, _ = w0.last.nm_profile(0, kk, to_host=True)
+                    dnm = time.perf_counter() - c0
+                    ent = int(off_[kk])
+                    text_dev["nm_profile"] = {"tiles": kk, "entries": ent, "kernel_ms": kms, "kernel_GB_per_s": ent * 12e-6 / max(kms, 1e-9),
+                                              "kernel_Gbp_per_h": float(ts.H[:kk].sum()) / max(kms, 1e-9) * 3.6e-3,
+                                              "to_host_seconds": dnm, "to_host_Gbp_per_h": float(ts.H[:kk].sum()) / dnm * 3600.0 / 1e9,
+                                              "what": "nm_profile_kernel (12 B per EQ/X/D column written to HBM); to_host = the same + D2H into pageable memory incl. this bench's python"}
+                    del tri_
+                except Exception as e:
+                    text_dev["nm_profile"] = {"error": str(e)}
             except Exception as e:
-                text_dev["nm_profile"] = {"error": str(e)}
-        except Exception as e:
-            text_dev = {"error": str(e)}
+                text_dev = {"error": str(e)}
         valid = w0.valid
         w0.last.release()
         # the same step with inputs already resident in HBM (plan -> fill -> backtrack -> compaction)
         resident = None
         try:
-            if args.resident_steps > 0:
+            if args.full and args.resident_steps > 0:
                 tab = ts.table()
                 import ctypes as C
                 from ngmlr_amd.aligner import DeviceBatch
@@ -947,7 +988,7 @@ def main() -> int:
         # ~300-base window, src/ScoreBuffer.cpp:87-168): cvx_score_batch against the reference's own StrippedSW
         # on all host threads, same pairs, every score compared
         subread = None
-        if not args.no_cpu_baseline and args.gpus == 1:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1:
             try:
                 subread = subread_scoring_rates(w0.al.lib, devs[0])
             except Exception as e:
@@ -967,7 +1008,7 @@ def main() -> int:
 
         # SURVEY 8 f4 on the device (candidate search, reference decode) and the catch-all fill kernel: rate + parity, beside the line
         index_stage = generic_rate = None
-        if not args.no_cpu_baseline and args.gpus == 1 and not args.no_extras:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1 and not args.no_extras:
             index_stage = index_stage_rates(w0.al)
             try:
                 if extra_tiles.get("ont"):
@@ -1109,12 +1150,12 @@ def main() -> int:
         w.al.close()
     for ts in tilesets:
         ts.unpin()
-    if out is not None and args.gpus == 1 and not (args.no_extras or args.no_cpu_baseline):
+    if out is not None and args.full and args.gpus == 1 and not (args.no_extras or args.no_cpu_baseline):
         try:
             out["binding_input_form"] = binding_form_rates(lib, tilesets[0], devs[0])
         except Exception as e:        # never let the extra measurement break the contract line
             out["binding_input_form"] = {"error": str(e)}
-    if out is not None and args.gpus == 1 and not (args.no_e2e or args.no_extras or args.no_cpu_baseline):
+    if out is not None and args.full and args.gpus == 1 and not (args.no_e2e or args.no_extras or args.no_cpu_baseline):
         # ngmlr's own pipeline (the reference's only published metric is end to end, README.md:25), outside the timed region and
         # after this process has given its device memory back: the reference's binary built with every drop-in (oracle/_ref/ngmlr_hip_all)
         # against the unmodified build (ngmlr_ref) on the same synthetic reads -- wall, mapping time, SAM identical, tiles per

@@ -8,13 +8,13 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -s KILL 700 python $R/bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout -s KILL 700 python $R/bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 tail -c 600 $OUT/${TAG}_bench.json
-timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o p -- python $R/bench.py --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1
-timeout -s KILL 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/${TAG}_fetch -o p -- python $R/bench.py --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_fetch.log 2>&1
-timeout -s KILL 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/${TAG}_write -o p -- python $R/bench.py --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_write.log 2>&1
+timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o p -- python $R/bench.py --full --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/${TAG}_fetch -o p -- python $R/bench.py --full --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_fetch.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/${TAG}_write -o p -- python $R/bench.py --full --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_write.log 2>&1
 # issue-side counters: instructions, wave cycles, and the three disjoint wave states (parked / issue-stalled / issuing)
-timeout -s KILL 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/${TAG}_sq -o p -- python $R/bench.py --tiles 12288 --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_sq.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/${TAG}_sq -o p -- python $R/bench.py --full --tiles 12288 --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_sq.log 2>&1
 # VALU pipe occupancy proper (cycles the VALU is executing, not instruction counts), if this rocprofv3 has the counters
 rocprofv3 -L > $OUT/${TAG}_counters_list.txt 2>&1
 SQ2=""
@@ -22,7 +22,7 @@ for c in SQ_INST_CYCLES_VALU SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CY
 	grep -q "\b$c\b" $OUT/${TAG}_counters_list.txt && SQ2="$SQ2 $c"
 done
 echo "second SQ pass:$SQ2"
-timeout -s KILL 200 rocprofv3 --kernel-trace --pmc $SQ2 -d $OUT/${TAG}_sq2 -o p -- python $R/bench.py --tiles 12288 --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_sq2.log 2>&1
+timeout -s KILL 200 rocprofv3 --kernel-trace --pmc $SQ2 -d $OUT/${TAG}_sq2 -o p -- python $R/bench.py --full --tiles 12288 --steps 1 --warmup 0 --resident-steps 0 --no-cpu-baseline > $OUT/${TAG}_sq2.log 2>&1
 # round 5: the other BASELINE configs' fill classes (ONT mix: chained retries / M = 4 / M = 3; C5 mix) -- kernel trace and the SQ pass
 # per class (tools/ab_knobs.py: one batch, inputs resident, four runs), and the genome-scale candidate search with its HBM traffic
 for W in ont c5; do
