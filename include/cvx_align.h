@@ -35,6 +35,7 @@
  * cvx_sam_record_text / cvx_sam_batch  SAMWriter::DoWriteReadGeneric  src/SAMWriter.cpp:87-224 (f3: SAM record assembly)
  * cvx_sam_unmapped_text       SAMWriter::DoWriteUnmappedReadGeneric  src/SAMWriter.cpp:308-357
  * cvx_score_batch             StrippedSW::BatchScore/SingleScore  src/StrippedSW.cpp:118-203 (next-row f2)
+ * cvx_score_submit/poll/wait  the same, asynchronous, split by shape  (the interval and inversion checks)
  * cvx_genome_* / cvx_submit_windows  SequenceProvider's 4-bit genome + DecodeRefSequenceExact
  *                             src/SequenceProvider.cpp:333-386,475-565 (next-row f4, decode half)
  * cvx_job_window_refs         the windows cvx_submit_windows decoded, back on the host for a text stage there
@@ -463,6 +464,25 @@ int cvx_score_kernel_ms(cvx_handle h, float *ms);
  * ladder, compaction) summed, without the host round trips between them. */
 enum { CVX_STAGE_SCORE = 0, CVX_STAGE_DECODE = 1, CVX_STAGE_SEARCH = 2 };
 int cvx_stage_kernel_ms(cvx_handle h, int32_t stage, float *ms);
+
+/* Asynchronous sub-read scoring (ABI 9, additive): the scores cvx_score_batch returns, for callers that must not block
+ * while the device works (BatchingScorer: ngmlr's interval and inversion checks, src/AlignmentBuffer.cpp:2515-2548 and
+ * :1158-1235).  The pairs of one call are split by shape and each class runs in a launch of its own, in call order on
+ * the handle's stream:
+ *   - ql <= 512 and rl <= 2048 (NULs included): score_diag_kernel (no gapped path can win there, cvx_score.hip);
+ *   - min(rl, ql) <= 1024: score_wave_kernel, the shorter side in registers (cvx_score_wave.hip), one launch per
+ *     row class (1, 2, 4, 8, 16 rows per lane);
+ *   - everything else: score_kernel.
+ * The strings are copied into the job's pinned staging inside cvx_score_submit: the caller's buffers are free again when
+ * it returns.  Several jobs may be in flight per handle; calls on one handle come from one thread at a time.
+ * CVX_STAGE_SCORE reports the kernels of whichever scoring call finished last (cvx_score_batch or cvx_score_wait). */
+typedef struct cvx_score_job_s *cvx_score_job;
+int cvx_score_submit(cvx_handle h, int32_t n, const char *const *refs, const char *const *qrys, cvx_score_job *job);   /* (ABI 9, additive) */
+/* 1 done, 0 still running, < 0 an error (the job still has to be waited for, which releases it) (ABI 9, additive) */
+int cvx_score_poll(cvx_score_job job);
+/* blocks (sleeping, not spinning) until the job is done, writes its n scores in call order, releases the job -- also when
+ * it returns an error (ABI 9, additive) */
+int cvx_score_wait(cvx_score_job job, float *scores);
 
 /* Host-side text stage (convertCigar, src/ConvexAlignFast.cpp:112-333, and the
  * N-clip flags of :493-528).  Pure host code, no device needed. */

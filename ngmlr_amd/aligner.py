@@ -486,8 +486,47 @@ class StrippedSWHip:
     def single_score(self, ref: bytes, qry: bytes) -> float:
         return float(self.batch_score([ref], [qry])[0])
 
+    def submit_scores(self, refs: Sequence[bytes], qrys: Sequence[bytes]) -> "ScoreJob":
+        """cvx_score_submit: the same scores as batch_score, split by shape into one launch per class; returns at once.
+        The strings are copied before this returns."""
+        n = len(refs)
+        if len(qrys) != n:
+            raise ValueError("submit_scores: %d refs, %d qrys" % (n, len(qrys)))
+        r = (C.c_char_p * max(n, 1))(*refs)
+        q = (C.c_char_p * max(n, 1))(*qrys)
+        job = C.c_void_p()
+        capi.check(self.lib.cvx_score_submit(self._al.h, n, r, q, C.byref(job)))
+        return ScoreJob(self, job, n)
+
+    def kernel_ms(self) -> float:
+        """device time of the kernels of the handle's last scoring call (cvx_stage_kernel_ms, CVX_STAGE_SCORE)"""
+        ms = C.c_float()
+        capi.check(self.lib.cvx_stage_kernel_ms(self._al.h, capi.STAGE_SCORE, C.byref(ms)))
+        return ms.value
+
     def close(self) -> None:
         self._al.close()
+
+
+class ScoreJob:
+    """One cvx_score_submit in flight: poll() -> bool, wait() -> float32 scores in call order (releases the job)."""
+
+    def __init__(self, owner: StrippedSWHip, job, n: int):
+        self.owner, self.job, self.n = owner, job, n
+
+    def poll(self) -> bool:
+        rc = self.owner.lib.cvx_score_poll(self.job)
+        if rc < 0:
+            capi.check(rc)
+        return rc == 1
+
+    def wait(self) -> np.ndarray:
+        if self.job is None:
+            raise RuntimeError("ScoreJob.wait: already waited for")
+        out = np.zeros(max(self.n, 1), dtype=np.float32)
+        job, self.job = self.job, None
+        capi.check(self.owner.lib.cvx_score_wait(job, out.ctypes.data))
+        return out[:self.n]
 
 
 class DeviceBatch:

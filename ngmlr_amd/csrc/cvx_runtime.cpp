@@ -47,6 +47,7 @@
 #include "cvx_host_logic.h"
 #include "cvx_index_build.h"
 #include "cvx_launch.h"
+#include "cvx_score_wave.h"
 #include "cvx_types.h"
 
 using namespace cvx;
@@ -471,8 +472,12 @@ struct cvx_context {
 	float sc_kernel_ms = 0.0f;
 	float decode_kernel_ms = 0.0f;     /* decode_windows_kernel of the last cvx_genome_decode (cvx_stage_kernel_ms) */
 	bool score_no_diag = false;   /* test knob (env CVX_TUNE_SCORE_NO_DIAG): always the row-by-row kernels */
+	/* asynchronous scoring (cvx_score_submit): jobs with their own staging and device buffers, kept for reuse once waited for */
+	std::vector<struct cvx_score_job_s *> sc_jobs_free, sc_jobs_live;
 	struct cvx_search_state *search = nullptr;   /* candidate search (cvx_search_batch): persistent staging and device buffers */
 };
+
+static void score_jobs_free(cvx_context *h);     /* (cvx_destroy: every scoring job of the handle, waited for or not) */
 
 struct cvx_genome_s {            /* an encoded reference genome resident in HBM (cvx_genome.hip) */
 	int device = 0;
@@ -1539,6 +1544,7 @@ void cvx_destroy(cvx_handle h) {
 	h->pending.clear();
 	h->sc_hseq.release(); h->sc_hpairs.release(); h->sc_hout.release();
 	h->sc_seq.release(); h->sc_pairs.release(); h->sc_rows.release(); h->sc_out.release();
+	score_jobs_free(h);
 	if (h->sc_ev0) (void) hipEventDestroy(h->sc_ev0);
 	if (h->sc_done) (void) hipEventDestroy(h->sc_done);
 	if (h->sc_ev1) (void) hipEventDestroy(h->sc_ev1);
@@ -2775,6 +2781,184 @@ int cvx_score_kernel_ms(cvx_handle h, float *ms) {
 	if (!h || !ms) { set_err("cvx_score_kernel_ms: NULL argument"); return CVX_ERR_ARG; }
 	*ms = h->sc_kernel_ms;
 	return CVX_OK;
+}
+
+}  /* extern "C" */
+
+/* ------------------------------------------------------------------ asynchronous sub-read scoring */
+
+/* One cvx_score_submit call: the pairs reordered by shape class (slot order), each class a contiguous range of the
+ * pair table and of the output, launched one after the other on the handle's stream; order[slot] is the caller's index. */
+struct cvx_score_job_s {
+	cvx_context *h = nullptr;
+	int32_t n = 0;
+	PinBuf hseq, hpairs, hout;
+	std::vector<int32_t> order;
+	DevBuf<uint8_t> seq;
+	DevBuf<ScorePair> pairs;
+	DevBuf<int32_t> rows;
+	DevBuf<float> out;
+	hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
+	void release() {
+		hseq.release(); hpairs.release(); hout.release();
+		seq.release(); pairs.release(); rows.release(); out.release();
+		if (ev0) (void) hipEventDestroy(ev0);
+		if (ev1) (void) hipEventDestroy(ev1);
+		if (done) (void) hipEventDestroy(done);
+		ev0 = ev1 = done = nullptr;
+	}
+};
+
+static void score_jobs_free(cvx_context *h) {
+	for (cvx_score_job_s *j : h->sc_jobs_free) { j->release(); delete j; }
+	for (cvx_score_job_s *j : h->sc_jobs_live) { j->release(); delete j; }
+	h->sc_jobs_free.clear();
+	h->sc_jobs_live.clear();
+}
+
+namespace {
+/* shape classes of cvx_score_submit, in launch order */
+enum { kScDiag = 0, kScWave1, kScWave2, kScWave4, kScWave8, kScWave16, kScRows, kScClasses };
+
+int score_class(size_t rl, size_t ql, bool no_diag) {
+	if (ql <= 512 && rl <= 2048 && !no_diag) return kScDiag;             /* cvx_score_batch's condition, per pair */
+	switch (score_wave_rows((int64_t) std::min(rl, ql))) {
+	case 1: return kScWave1;
+	case 2: return kScWave2;
+	case 4: return kScWave4;
+	case 8: return kScWave8;
+	case 16: return kScWave16;
+	default: return kScRows;
+	}
+}
+
+void score_job_recycle(cvx_score_job_s *j) {
+	cvx_context *h = j->h;
+	h->sc_jobs_live.erase(std::find(h->sc_jobs_live.begin(), h->sc_jobs_live.end(), j));
+	h->sc_jobs_free.push_back(j);
+}
+
+int score_job_enqueue(cvx_context *h, cvx_score_job_s *j, int32_t n, const char *const *refs, const char *const *qrys) {
+	HIP_TRY(hipSetDevice(h->device));
+	std::vector<size_t> rl(n), ql(n);
+	std::vector<int> cls(n);
+	size_t count[kScClasses] = {0}, max_rl_rows = 0;
+	uint64_t bytes = 0, rows = 0;
+	for (int i = 0; i < n; ++i) {
+		if (!refs[i] || !qrys[i]) { set_err("cvx_score_submit: NULL sequence %d", i); return CVX_ERR_ARG; }
+		rl[i] = strlen(refs[i]) + 1;
+		ql[i] = strlen(qrys[i]) + 1;
+		cls[i] = score_class(rl[i], ql[i], h->score_no_diag);
+		++count[cls[i]];
+		bytes += rl[i] + ql[i];
+	}
+	size_t first[kScClasses + 1] = {0};
+	for (int c = 0; c < kScClasses; ++c) first[c + 1] = first[c] + count[c];
+	size_t fill[kScClasses];
+	memcpy(fill, first, sizeof(fill));
+	j->order.resize((size_t) n);
+	for (int i = 0; i < n; ++i) j->order[fill[cls[i]]++] = i;
+	RC_TRY(j->hpairs.ensure((size_t) n * sizeof(ScorePair)));
+	RC_TRY(j->hout.ensure((size_t) n * sizeof(float)));
+	RC_TRY(j->hseq.ensure((size_t) bytes + 256));
+	ScorePair *pairs = j->hpairs.as<ScorePair>();
+	uint8_t *hseq = j->hseq.as<uint8_t>();
+	bytes = 0;
+	for (int s = 0; s < n; ++s) {
+		const int i = j->order[(size_t) s];
+		ScorePair &p = pairs[s];
+		p.ref_off = bytes; memcpy(hseq + bytes, refs[i], rl[i]); bytes += rl[i];
+		p.qry_off = bytes; memcpy(hseq + bytes, qrys[i], ql[i]); bytes += ql[i];
+		p.ref_len = (int32_t) std::min<size_t>(rl[i], 0x7fffffff);
+		p.qry_len = (int32_t) std::min<size_t>(ql[i], 0x7fffffff);
+		p.scratch_off = 0;
+		if ((size_t) s >= first[kScRows] && rl[i] < 100000 && ql[i] < 100000) {    /* score_kernel's two DP rows */
+			p.scratch_off = rows;
+			rows += 2 * (uint64_t) rl[i];
+			max_rl_rows = std::max(max_rl_rows, rl[i]);
+		}
+	}
+	RC_TRY(j->seq.ensure((size_t) bytes + 256));
+	RC_TRY(j->pairs.ensure((size_t) n));
+	RC_TRY(j->rows.ensure((size_t) rows + 64));
+	RC_TRY(j->out.ensure((size_t) n));
+	if (!j->ev0) {
+		HIP_TRY(hipEventCreate(&j->ev0));
+		HIP_TRY(hipEventCreate(&j->ev1));
+		HIP_TRY(hipEventCreateWithFlags(&j->done, hipEventBlockingSync | hipEventDisableTiming));
+	}
+	hipStream_t st = h->s_main;
+	HIP_TRY(hipMemcpyAsync(j->seq.p, hseq, (size_t) ((bytes + 255) / 256 * 256), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(j->pairs.p, pairs, (size_t) n * sizeof(ScorePair), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipEventRecord(j->ev0, st));
+	static const int kRows[kScClasses] = {0, 1, 2, 4, 8, 16, 0};
+	for (int c = 0; c < kScClasses; ++c) {
+		if (!count[c]) continue;
+		const ScorePair *cp = j->pairs.p + first[c];
+		float *co = j->out.p + first[c];
+		const int cn = (int) count[c];
+		if (c == kScDiag) HIP_TRY(launch_score_diag(j->seq.p, cp, co, cn, st));
+		else if (c == kScRows) HIP_TRY(launch_score(j->seq.p, cp, j->rows.p, co, cn, (int) std::min<size_t>(std::max<size_t>(max_rl_rows, 513), 0x7fffffff), st));
+		else HIP_TRY(launch_score_wave(j->seq.p, cp, co, cn, kRows[c], st));
+	}
+	HIP_TRY(hipEventRecord(j->ev1, st));
+	HIP_TRY(hipMemcpyAsync(j->hout.p, j->out.p, (size_t) n * sizeof(float), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipEventRecord(j->done, st));
+	return CVX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int cvx_score_submit(cvx_handle h, int32_t n, const char *const *refs, const char *const *qrys, cvx_score_job *job) {
+	ABI_GUARD_BEGIN
+	if (!h || !job || n < 0 || (n > 0 && (!refs || !qrys))) { set_err("cvx_score_submit: bad argument"); return CVX_ERR_ARG; }
+	*job = nullptr;
+	cvx_score_job_s *j;
+	if (!h->sc_jobs_free.empty()) { j = h->sc_jobs_free.back(); h->sc_jobs_free.pop_back(); }
+	else j = new cvx_score_job_s();
+	j->h = h;
+	j->n = n;
+	h->sc_jobs_live.push_back(j);
+	if (n > 0) {
+		const int rc = score_job_enqueue(h, j, n, refs, qrys);
+		if (rc != CVX_OK) { score_job_recycle(j); return rc; }
+	}
+	*job = j;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_score_poll(cvx_score_job j) {
+	if (!j) { set_err("cvx_score_poll: NULL job"); return CVX_ERR_ARG; }
+	if (j->n == 0) return 1;
+	const hipError_t e = hipEventQuery(j->done);
+	if (e == hipSuccess) return 1;
+	if (e == hipErrorNotReady) return 0;
+	(void) hipGetLastError();
+	set_err("cvx_score_poll: %s", hipGetErrorString(e));
+	return CVX_ERR_HIP;
+}
+
+int cvx_score_wait(cvx_score_job j, float *scores) {
+	ABI_GUARD_BEGIN
+	if (!j || (j->n > 0 && !scores)) { set_err("cvx_score_wait: bad argument"); return CVX_ERR_ARG; }
+	int rc = CVX_OK;
+	if (j->n > 0) {
+		const hipError_t e = hipEventSynchronize(j->done);
+		if (e != hipSuccess) {
+			(void) hipGetLastError();
+			set_err("cvx_score_wait: %s", hipGetErrorString(e));
+			rc = CVX_ERR_HIP;
+		} else {
+			const float *o = j->hout.as<float>();
+			for (int32_t s = 0; s < j->n; ++s) scores[j->order[(size_t) s]] = o[s];
+			j->h->sc_kernel_ms = ev_ms(j->ev0, j->ev1);
+		}
+	}
+	score_job_recycle(j);
+	return rc;
+	ABI_GUARD_END
 }
 
 }  /* extern "C" */

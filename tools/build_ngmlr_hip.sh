@@ -29,6 +29,10 @@ mkdir -p "$REPO/oracle/_ref"
 #                      cs_search_binding.inc at the top of CS::RunBatch, src/CS.cpp:400): alignment, sub-read scoring, k-mer vote
 #                      and SAM records on the drop-ins (SURVEY 8 f1 + f2 + f3 + f4's search half)
 #                      -- and the k-mer table itself built by cvx_index_build (index_build_binding.inc in CompactPrefixTable::CreateTable)
+#   ngmlr_hip_checks   ngmlr_hip_all + the interval check (overlapCheckAligner, src/AlignmentBuffer.h:368) and the inversion check
+#                      (lqCheckAligner, src/AlignmentBuffer.cpp:1217) scored on the device: Convex::SharedScorer proxies in place of
+#                      their private StrippedSW, one BatchingScorer per device (batching_scorer.h); CVX_CHECK_SCORER=0 puts the
+#                      reference's StrippedSW back at run time (tests/test_gpu_e2e_checks.py)
 #   ngmlr_index_cpu    the reference's CPU code with only that table builder bound: the table file it writes against the unmodified
 #                      binary's, without a GPU (tests/test_index_cpu.py)
 #   ngmlr_pool_cpu     the reference's CPU aligners + the same pool: the pool's own correctness without a GPU (tests/test_pool_cpu.py)
@@ -36,16 +40,27 @@ mkdir -p "$REPO/oracle/_ref"
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" <<'PY'
 import re, sys
-T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8]
+T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
+if CHECKS:
+    # the interval and inversion checks through Convex::SharedScorer (ngmlr_amd/csrc/batching_scorer.h)
+    p = T + '/src/AlignmentBuffer.h'
+    s = open(p).read()
+    s = sub1(s, '#include "StrippedSW.h"', '#include "StrippedSW.h"\n#include "batching_scorer.h"', 'AlignmentBuffer.h include (checks)')
+    s = sub1(s, 'overlapCheckAligner = new StrippedSW();', 'overlapCheckAligner = new Convex::SharedScorer(Convex::SharedScorer::kIntervalCheck);', 'interval check')
+    open(p, 'w').write(s)
+    p = T + '/src/AlignmentBuffer.cpp'
+    s = open(p).read()
+    s = sub1(s, 'IAlignment * lqCheckAligner = new StrippedSW();', 'IAlignment * lqCheckAligner = new Convex::SharedScorer(Convex::SharedScorer::kInversionCheck);', 'inversion check')
+    open(p, 'w').write(s)
 if INDEX:
     # the k-mer table built by cvx_index_build (ngmlr_amd/csrc/index_build_binding.inc at the top of CompactPrefixTable::CreateTable)
     p = T + '/src/SequenceProvider.h'
@@ -177,7 +192,7 @@ if CLASS != 'cpu':
     open(p, 'w').write(s)
 p = T + '/src/CMakeLists.txt'
 c = open(p).read()
-c = c.replace('add_executable(ngmlr', ('add_definitions(-DCVX_IN_NGMLR_TREE)\ninclude_directories(${CMAKE_CURRENT_SOURCE_DIR} %s/include %s/ngmlr_amd/csrc REPO_TESTS_CPP)\nadd_executable(ngmlr\n%s/ngmlr_amd/csrc/convex_align_hip.cpp\n%s/ngmlr_amd/csrc/batching_aligner.cpp\n%s/ngmlr_amd/csrc/stripped_sw_hip.cpp\n%s/ngmlr_amd/csrc/candidate_search_hip.cpp\n%s/ngmlr_amd/csrc/cvx_fiber.cpp%s' % (REPO, REPO, REPO, REPO, REPO, REPO, REPO, ('\n%s/ngmlr_amd/csrc/align_pool.cpp' % REPO) if POOL else '')).replace('REPO_TESTS_CPP', REPO + '/tests/cpp'), 1)
+c = c.replace('add_executable(ngmlr', ('add_definitions(-DCVX_IN_NGMLR_TREE)\ninclude_directories(${CMAKE_CURRENT_SOURCE_DIR} %s/include %s/ngmlr_amd/csrc REPO_TESTS_CPP)\nadd_executable(ngmlr\n%s/ngmlr_amd/csrc/convex_align_hip.cpp\n%s/ngmlr_amd/csrc/batching_aligner.cpp\n%s/ngmlr_amd/csrc/stripped_sw_hip.cpp\n%s/ngmlr_amd/csrc/candidate_search_hip.cpp\n%s/ngmlr_amd/csrc/cvx_fiber.cpp%s' % (REPO, REPO, REPO, REPO, REPO, REPO, REPO, ('\n%s/ngmlr_amd/csrc/align_pool.cpp' % REPO) if POOL else '') + (('\n%s/ngmlr_amd/csrc/batching_scorer.cpp' % REPO) if CHECKS else '')).replace('REPO_TESTS_CPP', REPO + '/tests/cpp'), 1)
 c = c.replace('TARGET_LINK_LIBRARIES(ngmlr ${ZLIB_LIBRARIES})', 'TARGET_LINK_LIBRARIES(ngmlr ${ZLIB_LIBRARIES})\nTARGET_LINK_LIBRARIES(ngmlr %s/ngmlr_amd/libcvxalign.so)\nset_target_properties(ngmlr PROPERTIES BUILD_RPATH "\\$ORIGIN/../../ngmlr_amd;/opt/rocm/lib" SKIP_BUILD_RPATH FALSE)' % REPO, 1)
 open(p, 'w').write(c)
 PY
@@ -189,7 +204,7 @@ local BIN=$(ls "$T"/bin/ngmlr-*/ngmlr)
 cp "$BIN" "$REPO/oracle/_ref/$OUT_NAME"
 echo "built $REPO/oracle/_ref/$OUT_NAME"
 }
-# NGMLR_VARIANTS="ngmlr_pool_cpu ngmlr_hip_all" rebuilds only those (default: all nine)
+# NGMLR_VARIANTS="ngmlr_pool_cpu ngmlr_hip_all" rebuilds only those (default: all of them)
 want() { [ -z "${NGMLR_VARIANTS:-}" ] || [[ " $NGMLR_VARIANTS " == *" $1 "* ]]; }
 bv() { if want "$1"; then build_variant "$@" & fi; }
 bv ngmlr_hip Convex::ConvexAlignHip
@@ -200,10 +215,11 @@ bv ngmlr_hip_pool Convex::SharedAligner StrippedSWHip sam pool
 bv ngmlr_pool_cpu cpu "" "" pool
 bv ngmlr_pool_parked Convex::ParkingCpuAligner "" "" pool      # CPU aligner behind a park / wake per SingleAlign (tests/cpp/parking_cpu_aligner.h)
 bv ngmlr_hip_all Convex::SharedAligner StrippedSWHip sam pool search index
+bv ngmlr_hip_checks Convex::SharedAligner StrippedSWHip sam pool search index checks
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
