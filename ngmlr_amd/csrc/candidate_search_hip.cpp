@@ -20,7 +20,7 @@ struct PerDevice {
 	std::mutex laneMtx[kLanes];
 	cvx_handle handle[kLanes] = {0};
 	cvx_index index = 0;
-	bool ready = false;
+	std::atomic<bool> ready{false};     /* handles and table in place: stored last (release), read by Search without mtx (acquire) */
 	std::atomic<int> nextLane{0};
 	std::atomic<long> calls{0}, reads{0}, lists{0};
 	std::atomic<long long> ns{0};
@@ -67,7 +67,7 @@ static void prepare_device(int logical, int kmerLength, void const * refTableInd
 		for (int q = 0; q < kLanes; ++q) { cvx_destroy(d.handle[q]); d.handle[q] = 0; }
 		throw "CandidateSearchHip: the k-mer table could not be put on the device";
 	}
-	d.ready = true;
+	d.ready.store(true, std::memory_order_release);
 }
 
 void CandidateSearchHip::Shutdown() {
@@ -117,7 +117,7 @@ void CandidateSearchHip::Search(Batch & b, float sensitivity, float minKmerHits,
 	if (n == 0) return;
 	int const dv = ServiceDeviceOfThisThread();
 	PerDevice & d = g_dev[dv];
-	if (!d.ready) prepare_device(dv, kmerLength, refTableIndex, refTable, nLocations, unitOffset);
+	if (!d.ready.load(std::memory_order_acquire)) prepare_device(dv, kmerLength, refTableIndex, refTable, nLocations, unitOffset);
 	if (tl_lane < 0) tl_lane = d.nextLane.fetch_add(1) % kLanes;
 	std::chrono::steady_clock::time_point const t0 = std::chrono::steady_clock::now();
 	std::lock_guard<std::mutex> lane(d.laneMtx[tl_lane]);

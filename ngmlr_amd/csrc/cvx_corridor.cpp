@@ -29,6 +29,7 @@
 #include "cvx_align.h"
 #include "cvx_types.h"
 #include "cvx_host_logic.h"
+#include "cvx_rt_err.h"
 
 namespace {
 
@@ -153,6 +154,7 @@ void setRows(cvx_tile *f) {
 
 extern "C" int cvx_corridor_fit(const int32_t *row_offset, const int32_t *row_length, int32_t row_stride_bytes, int32_t n_rows,
 		int32_t ref_len, int32_t qry_len, cvx_tile *form) {
+	ABI_GUARD_BEGIN
 	if (form == 0) return CVX_ERR_ARG;
 	setRows(form);
 	if (n_rows < 0 || (n_rows > 0 && (row_offset == 0 || row_length == 0)) || (row_stride_bytes & 3) || row_stride_bytes < 4) return CVX_ERR_ARG;
@@ -240,15 +242,18 @@ extern "C" int cvx_corridor_fit(const int32_t *row_offset, const int32_t *row_le
 		cand = floatOf(oLo + (int32_t) (((int64_t) oHi - (int64_t) oLo) / 2));
 	}
 	return CVX_OK;                                 /* the caller's rows travel as they are */
+	ABI_GUARD_END
 }
 
 /* The same for a whole tile table on n_threads host threads (0 = all): every tile that carries rows (CVX_CORRIDOR_ROWS) gets its
  * closed form written in place when there is one -- what a binding does per SingleAlign (ConvexAlignHip::Prepare) done for a
  * batch that arrived as rows (bench.py's `binding_input_form`). */
 #include <atomic>
+#include <system_error>
 #include <thread>
 
 extern "C" int cvx_corridor_fit_batch(int32_t n_tiles, cvx_tile *tiles, int32_t n_threads, int32_t *n_fitted) {
+	ABI_GUARD_BEGIN
 	if (n_tiles < 0 || (n_tiles > 0 && tiles == 0)) return CVX_ERR_ARG;
 	int nt = n_threads > 0 ? n_threads : (int) std::thread::hardware_concurrency();
 	if (nt < 1) nt = 1;
@@ -271,9 +276,11 @@ extern "C" int cvx_corridor_fit_batch(int32_t n_tiles, cvx_tile *tiles, int32_t 
 		fitted += mine;
 	};
 	std::vector<std::thread> th;
-	for (int t = 1; t < nt; ++t) th.emplace_back(work);
+	th.reserve((size_t) nt - 1);      /* (no reallocation once threads run: a joinable std::thread destroyed by unwinding ends the process) */
+	for (int t = 1; t < nt; ++t) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }      /* (the others take its share) */
 	work();
 	for (auto &t : th) t.join();
 	if (n_fitted) *n_fitted = fitted.load();
 	return err.load();
+	ABI_GUARD_END
 }

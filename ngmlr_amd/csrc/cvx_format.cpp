@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "cvx_align.h"
+#include "cvx_rt_err.h"
 
 namespace {
 
@@ -90,6 +91,7 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 		int32_t ext_qstart, int32_t ext_qend,
 		char *cigar, int32_t cigar_cap, char *md, int32_t md_cap,
 		int32_t *nm_triples, int32_t nm_cap, cvx_alignment_text *out) {
+	ABI_GUARD_BEGIN
 	(void) qry_len;
 	if (!r || !out || cigar_cap < 0 || md_cap < 0 || (cigar_cap > 0 && !cigar) || (md_cap > 0 && !md))
 		return CVX_ERR_ARG;
@@ -217,16 +219,19 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 	}
 	out->sv_type = sv;
 	return CVX_OK;
+	ABI_GUARD_END
 }
 
 /* ---- batch form: a parallel-for over tiles (dynamic chunks of 16) ---- */
 #include <atomic>
+#include <system_error>
 #include <thread>
 #include <vector>
 
 extern "C" int cvx_format_batch(int32_t n, const cvx_result *results, const uint32_t *ops_arena,
 		const cvx_tile *tiles, const cvx_text_buffers *bufs, cvx_alignment_text *out,
 		int32_t n_threads) {
+	ABI_GUARD_BEGIN
 	if (n < 0 || (n > 0 && (!results || !tiles || !bufs || !out))) return CVX_ERR_ARG;
 	if (n == 0) return CVX_OK;
 	int nt = n_threads > 0 ? n_threads : (int) std::thread::hardware_concurrency();
@@ -248,8 +253,10 @@ extern "C" int cvx_format_batch(int32_t n, const cvx_result *results, const uint
 		}
 	};
 	std::vector<std::thread> th;
-	for (int t = 1; t < nt; ++t) th.emplace_back(work);
+	th.reserve((size_t) nt - 1);      /* (no reallocation once threads run: a joinable std::thread destroyed by unwinding ends the process) */
+	for (int t = 1; t < nt; ++t) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }      /* (the others take its share) */
 	work();
 	for (auto &t : th) t.join();
 	return err.load();
+	ABI_GUARD_END
 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "cvx_align.h"
+#include "cvx_rt_err.h"
 
 namespace {
 
@@ -48,6 +49,7 @@ uint64_t cvx_genome_encoded_bytes(int32_t n, const uint64_t *lengths) {
 
 int cvx_genome_encode(int32_t n, const char *const *seqs, const uint64_t *lengths, uint8_t *bin_ref,
 		uint64_t *n_nibbles, uint64_t *start_table, int32_t *n_starts) {
+	ABI_GUARD_BEGIN
 	if (n < 0 || (n > 0 && (!seqs || !lengths)) || !bin_ref || !n_nibbles || !start_table || !n_starts) return CVX_ERR_ARG;
 	const uint8_t spacer = (uint8_t) ((4u << 4) | 4u);
 	uint64_t at = 0;
@@ -71,6 +73,7 @@ int cvx_genome_encode(int32_t n, const char *const *seqs, const uint64_t *length
 	start_table[kept] = start_table[kept - 1] + last_len + 1000;   /* upper bound for positions on the last sequence */
 	*n_starts = kept + 1;
 	return CVX_OK;
+	ABI_GUARD_END
 }
 
 /*

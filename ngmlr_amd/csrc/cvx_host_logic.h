@@ -1,5 +1,5 @@
 /*
- * cvx_host_logic.h -- the device-independent half of the host runtime (cvx_runtime.cpp):
+ * cvx_host_logic.h -- the device-independent half of the host runtime (cvx_rt_align.cpp):
  * how a batch of cvx_tile is laid out and packed for upload, and how the corridor plans that
  * come back from plan_kernel are turned into kernel classes, arena offsets and work lists.
  * Header-only and free of HIP so that the CPU suite can exercise it (tests/cpp/host_logic_test.cpp).
@@ -15,6 +15,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -52,11 +53,11 @@ static const int kNumChainClasses = 3;
  * whatever its width), and its very long tiles are chained even if a ring would hold them. */
 static const int kSmallBatchTiles = 2048;
 static const int kLongTileSteps = 32768;
-/* whole tiles of at least this many steps are filled by the exact-tracking instantiation right away (cvx_runtime.cpp,
+/* whole tiles of at least this many steps are filled by the exact-tracking instantiation right away (cvx_rt_align.cpp,
  * stage_compute), as long as their class holds at most kExactDirectMaxTiles of them */
 static const int kExactDirectSteps = 65536;
 static const int kExactDirectMaxTiles = 4096;
-/* streaming jobs smaller than this alternate between the runtime's two stream sets (cvx_runtime.cpp, stage_compute) */
+/* streaming jobs smaller than this alternate between the runtime's two stream sets (cvx_rt_align.cpp, stage_compute) */
 static const int kSmallJobTiles = 2048;
 inline int chain_class_for(int need, bool small_batch) {
 	/* measured (C5 mix, 96 tiles): 64-row blocks 100 ms, 128-row 117 ms, 256-row 174 ms -- a tile's
@@ -113,7 +114,9 @@ private:
 		int hw = (int) std::thread::hardware_concurrency();
 		n_threads_ = std::max(1, std::min(hw > 0 ? hw : 1, 16));
 		if (const char *e = getenv("CVX_PACK_THREADS")) n_threads_ = std::max(1, atoi(e));
-		for (int i = 1; i < n_threads_; ++i) workers_.emplace_back([this] { loop(); });
+		/* (a worker that cannot be started is not an error: the callers of run take its tasks) */
+		workers_.reserve((size_t) n_threads_ - 1);
+		for (int i = 1; i < n_threads_; ++i) { try { workers_.emplace_back([this] { loop(); }); } catch (const std::system_error &) { break; } }
 	}
 	~PackPool() {
 		{ std::lock_guard<std::mutex> lk(m_); stop_ = true; }

@@ -1,4 +1,4 @@
-/* cvx_index_build.h -- the device build of ngmlr's k-mer table (cvx_index.hip), called by cvx_index_build_device (cvx_runtime.cpp) */
+/* cvx_index_build.h -- the device build of ngmlr's k-mer table (cvx_index.hip), called by cvx_index_build_device (cvx_rt_search.cpp) */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

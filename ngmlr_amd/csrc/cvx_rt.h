@@ -1,0 +1,366 @@
+/*
+ * cvx_rt.h -- what the files of the host runtime share (cvx_runtime.cpp and the cvx_rt_*.cpp of its subsystems): the HIP error
+ * macro, the grow-only device and page-locked buffers, the handle, job and genome structures, and the helpers more than one of
+ * those files calls.  Internal; the public boundary is include/cvx_align.h.
+ */
+#ifndef CVX_RT_H
+#define CVX_RT_H
+
+#include <hip/hip_runtime_api.h>
+
+#include <atomic>
+#include <cstdint>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "cvx_align.h"
+#include "cvx_host_logic.h"
+#include "cvx_launch.h"
+#include "cvx_rt_err.h"
+#include "cvx_types.h"
+
+using namespace cvx;      /* (only the runtime's own files include this header, and all of them work in namespace cvx) */
+
+#define HIP_TRY(expr)                                                              \
+	do {                                                                           \
+		hipError_t e_ = (expr);                                                    \
+		if (e_ != hipSuccess) {                                                    \
+			set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+			return (e_ == hipErrorOutOfMemory) ? CVX_ERR_OOM : CVX_ERR_HIP;        \
+		}                                                                          \
+	} while (0)
+
+struct cvx_search_state;         /* cvx_rt_search.cpp */
+struct cvx_score_state;          /* cvx_rt_score.cpp */
+
+namespace cvx {
+
+/* Buffers that grow while a handle streams jobs of changing size (ngmlr's pipeline: launches of 50 to 4 000 tiles on five job
+ * slots).  Two things made cvx_submit take 15-50 ms per call there (profiles/r06_e2e_submit_trace.txt, `upload stage`):
+ *   - hipFree / hipHostFree wait for everything in flight on the device.  An outgrown block is therefore not freed on the spot
+ *     but parked (defer_release) and given back when its handle has nothing in flight, or at cvx_destroy;
+ *   - every slot climbed to the size of the largest launch by itself.  Slots of one handle share a high-water mark per buffer
+ *     (bind): the first growth of a slot goes straight to the largest capacity any of them has had. */
+struct DeferredFrees {
+	std::mutex mtx;
+	std::vector<void *> dev, host;
+	void drain() {
+		std::vector<void *> d, h;
+		{
+			std::lock_guard<std::mutex> lk(mtx);
+			d.swap(dev);
+			h.swap(host);
+		}
+		for (void *p : d) (void) hipFree(p);
+		for (void *p : h) (void) hipHostFree(p);
+	}
+	bool empty() { std::lock_guard<std::mutex> lk(mtx); return dev.empty() && host.empty(); }
+};
+extern DeferredFrees g_deferred;
+
+template <typename T>
+struct DevBuf {
+	T *p = nullptr;
+	size_t cap = 0; /* elements */
+	size_t *hwm = nullptr;      /* shared by the same buffer of every job slot of the handle (bytes) */
+	int ensure(size_t n) {
+		if (n <= cap) return CVX_OK;
+		const size_t old = cap;
+		if (p) {
+			std::lock_guard<std::mutex> lk(g_deferred.mtx);
+			g_deferred.dev.push_back(p);
+			p = nullptr; cap = 0;
+		}
+		const size_t asked = n + n / 8 + 64;
+		size_t want = asked;
+		if (want < 2 * old) want = 2 * old;      /* a buffer that has to grow at least doubles; the first allocation stays close to what was asked for */
+		if (hwm && want * sizeof(T) < *hwm && *hwm / 16 <= asked * sizeof(T)) want = (*hwm + sizeof(T) - 1) / sizeof(T);      /* (never more than 16 x what was asked for) */
+		hipError_t e = hipMalloc((void **) &p, want * sizeof(T));
+		if (e != hipSuccess && want > asked) {      /* the generous size does not fit: give back what is parked, then what was asked for may */
+			(void) hipGetLastError();
+			g_deferred.drain();
+			want = asked;
+			e = hipMalloc((void **) &p, want * sizeof(T));
+		}
+		if (e != hipSuccess) {
+			set_err("hipMalloc(%zu bytes) failed: %s", want * sizeof(T), hipGetErrorString(e));
+			p = nullptr;
+			return CVX_ERR_OOM;
+		}
+		cap = want;
+		if (hwm && cap * sizeof(T) > *hwm) *hwm = cap * sizeof(T);
+		return CVX_OK;
+	}
+	void release() {
+		if (p) (void) hipFree(p);
+		p = nullptr;
+		cap = 0;
+	}
+};
+
+/* grow-only page-locked host buffer */
+struct PinBuf {
+	void *p = nullptr;
+	size_t cap = 0; /* bytes */
+	size_t *hwm = nullptr;
+	int ensure(size_t bytes) {
+		if (bytes <= cap) return CVX_OK;
+		const size_t old = cap;
+		if (p) {
+			std::lock_guard<std::mutex> lk(g_deferred.mtx);
+			g_deferred.host.push_back(p);
+			p = nullptr; cap = 0;
+		}
+		const size_t asked = bytes + bytes / 8 + 4096;
+		size_t want = asked;
+		if (want < 2 * old) want = 2 * old;                     /* (see DevBuf::ensure) */
+		if (hwm && want < *hwm && *hwm / 16 <= asked) want = *hwm;
+		hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+		if (e != hipSuccess && want > asked) {
+			(void) hipGetLastError();
+			g_deferred.drain();
+			want = asked;
+			e = hipHostMalloc(&p, want, hipHostMallocDefault);
+		}
+		if (e != hipSuccess) {
+			(void) hipGetLastError();
+			set_err("hipHostMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
+			p = nullptr;
+			return CVX_ERR_OOM;
+		}
+		cap = want;
+		if (hwm && cap > *hwm) *hwm = cap;
+		return CVX_OK;
+	}
+	void release() {
+		if (p) (void) hipHostFree(p);
+		p = nullptr;
+		cap = 0;
+	}
+	template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+bool in_pinned_block(const void *p, uint64_t bytes);      /* [p, p + bytes) lies inside one block of cvx_host_alloc */
+float ev_ms(hipEvent_t a, hipEvent_t b);
+int ensure_streams(cvx_context *c);
+/* the per-handle state of the search and of the scoring, owned by their files (cvx_destroy) */
+void search_state_free(cvx_search_state *ss);
+float search_kernel_ms(const cvx_search_state *ss);      /* of the handle's last search (cvx_stage_kernel_ms) */
+void score_state_free(cvx_score_state *ss);
+
+}  // namespace cvx
+
+/* Four streams per handle (io, main, post, one aux) and not more: the ROCm runtime multiplexes the streams of a process onto
+ * (by default) four hardware queues, and two streams that land on the same queue serialise --
+ * measured: with seven streams the 18-tile M = 4 launch ran alone for 11 ms in front of the
+ * 24 558-tile M = 3 launch instead of beside it. */
+static const int kAuxStreams = 2;      /* (round 5: a batch has up to four fill classes -- chained, gangs, M = 4, M = 3 -- and each wants a stream of its own) */
+
+enum BatchState { kFailed = -1, kEmpty = 0, kUploaded = 1, kPlanned = 2, kComputed = 3, kFinished = 4 };
+
+struct cvx_batch_s {
+	int n = 0;
+	int state = kEmpty;
+	bool in_flight = false;          /* submitted through the streaming API and not yet released */
+	hipStream_t s_run = nullptr;     /* the `main` stream of the set that carried this batch's kernels */
+	int fail_rc = CVX_OK;            /* state == kFailed: what went wrong with THIS job (cvx_wait returns it) */
+	std::string fail_msg;
+	uint64_t seq_total = 0, n_rows = 0, n_rowsx = 0;
+	uint64_t zero_copy_bytes = 0;    /* sequence bytes of the last upload that travelled straight from the caller's page-locked arena */
+	uint64_t ops_total = 0;          /* valid after the compute stage has been waited for */
+	uint64_t dense_cap = 0;
+	bool have_ops = false;           /* dense ops are in h_ops */
+
+	/* host side, page-locked */
+	PinBuf h_zero;                   /* zeros for the pads around blocks that travel straight from the caller's arena */
+	size_t zero_cap = 0;
+	PinBuf h_seq, h_delta, h_rsrc, h_rowsx, h_tin;     /* upload staging (owned by the batch: no wait before reuse by another batch):
+	                                                    * sequences, one step byte per corridor row, RowSrc[n], rows that need the verbatim form */
+	std::vector<RowDesc> chain_rows;                   /* scratch: expanded rows of a tile being chained */
+	PinBuf h_plan;                   /* TilePlan[n] */
+	PinBuf h_trun, h_tout, h_lists, h_goff;   /* what the host planning produces */
+	PinBuf h_res;                    /* ResultRec[n] + BatchSummary */
+	PinBuf h_ops;                    /* dense ops */
+
+	DevBuf<uint8_t> d_seq;
+	DevBuf<RowDesc> d_rows;          /* the expanded rows arena (expand_rows_kernel) */
+	DevBuf<uint8_t> d_delta;
+	DevBuf<RowSrc> d_rsrc;
+	DevBuf<RowDesc> d_rowsx;
+	DevBuf<TileIn> d_tin;
+	DevBuf<TilePlan> d_plan;
+	DevBuf<TileRun> d_trun;
+	DevBuf<TileOut> d_tout;
+	DevBuf<uint32_t> d_dirs;
+	DevBuf<int32_t> d_regions;
+	DevBuf<int32_t> d_lists;
+	DevBuf<int32_t> d_counters;
+	DevBuf<uint64_t> d_dstoff;
+	DevBuf<uint32_t> d_dense;
+	DevBuf<uint8_t> d_res;           /* ResultRec[n] + BatchSummary */
+	DevBuf<uint8_t> d_gscratch;      /* slot state of tiles taken by the catch-all kernel */
+	DevBuf<uint64_t> d_gscratch_off;
+	/* chained tiles (row blocks) */
+	/* device-side text stage (cvx_job_text) */
+	PinBuf h_ext, h_trec, h_toff, h_text;
+	DevBuf<int32_t> d_ext;
+	DevBuf<TextRec> d_trec;
+	DevBuf<unsigned long long> d_tlen;   /* lengths, offsets, total */
+	DevBuf<uint8_t> d_text;
+	bool text_done = false;          /* d_trec holds this job's text records (cvx_job_text ran) */
+	DevBuf<unsigned long long> d_nmoff;  /* nmPerPosition: entry counts, offsets, total of the requested tile range */
+	DevBuf<int32_t> d_nm;            /* ... and the triples */
+	PinBuf h_nmoff;
+	PinBuf h_nm;                     /* the triples on the host (cvx_job_nm_profile_resident) */
+	hipEvent_t ev_nm0 = nullptr, ev_nm1 = nullptr;
+	PinBuf h_win;                    /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
+	PinBuf h_refs;                   /* ... and the decoded windows back on the host (cvx_job_window_refs): the reference part of d_seq */
+	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
+	bool have_refs = false;
+	DevBuf<WindowDesc> d_win;
+	PinBuf h_chain;                  /* ChainTask[] of all chain classes, ChainBlk[], tile lists */
+	DevBuf<uint8_t> d_chain;
+	DevBuf<BoundaryRec> d_bnd;
+	uint32_t bnd_epoch = 0;          /* tag of the records the latest launch wrote (0: buffer freshly zeroed) */
+	DevBuf<ChainOut> d_chain_out;
+
+	hipEvent_t ev_bt0 = nullptr, ev_bt1 = nullptr;   /* fork / join of the long-read backtrack launch */
+	hipEvent_t ev_in = nullptr;      /* upload + plan records on the host */
+	hipEvent_t ev_res = nullptr;     /* result records on the host */
+	hipEvent_t ev_ops = nullptr;     /* dense ops on the host */
+	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* timing: plan begin/end, fills done, all done, fills may start */
+	std::vector<hipEvent_t> lev;     /* 4 events per fill class: start, two-phase pass done, exact pass done, the class's own backtrack done */
+	std::vector<cvx_launch_info> launches;
+	cvx_timing timing;
+
+	const TileIn *tin() const { return h_tin.as<TileIn>(); }
+	const TilePlan *plan() const { return h_plan.as<TilePlan>(); }
+	const ResultRec *res() const { return h_res.as<ResultRec>(); }
+	const BatchSummary *summary() const { return reinterpret_cast<const BatchSummary *>(h_res.as<uint8_t>() + (size_t) n * sizeof(ResultRec)); }
+
+	/* the buffers whose size follows the job's tile count or cells: the same buffer of every slot of a handle shares one mark */
+	static const int kSharedMarks = 32;
+	void bind(size_t *marks) {
+		int k = 0;
+		PinBuf *pins[] = { &h_seq, &h_delta, &h_rsrc, &h_tin, &h_plan, &h_trun, &h_tout, &h_lists, &h_res, &h_ops, &h_chain };
+		for (PinBuf *b_ : pins) b_->hwm = &marks[k++];
+		d_seq.hwm = &marks[k++]; d_rows.hwm = &marks[k++]; d_delta.hwm = &marks[k++]; d_rsrc.hwm = &marks[k++]; d_tin.hwm = &marks[k++];
+		d_plan.hwm = &marks[k++]; d_trun.hwm = &marks[k++]; d_tout.hwm = &marks[k++]; d_dirs.hwm = &marks[k++]; d_regions.hwm = &marks[k++];
+		d_lists.hwm = &marks[k++]; d_dstoff.hwm = &marks[k++]; d_dense.hwm = &marks[k++]; d_res.hwm = &marks[k++];
+		d_chain.hwm = &marks[k++]; d_bnd.hwm = &marks[k++]; d_chain_out.hwm = &marks[k++];
+		/* the big buffers of the text stage (strings, profile triples: 125 kB per 10 kb alignment); written by the one thread that
+		 * runs a handle's text stages -- never the thread that submits, and these entries are nobody else's */
+		h_text.hwm = &marks[k++]; h_nm.hwm = &marks[k++]; d_text.hwm = &marks[k++]; d_nm.hwm = &marks[k++];
+		static_assert(11 + 17 + 4 <= kSharedMarks, "marks");
+	}
+	int make_events() {
+		if (!ev_in) HIP_TRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
+		if (!ev_res) HIP_TRY(hipEventCreateWithFlags(&ev_res, hipEventDisableTiming));
+		if (!ev_ops) HIP_TRY(hipEventCreateWithFlags(&ev_ops, hipEventDisableTiming));
+		if (!ev_bt0) HIP_TRY(hipEventCreateWithFlags(&ev_bt0, hipEventDisableTiming));
+		if (!ev_bt1) HIP_TRY(hipEventCreateWithFlags(&ev_bt1, hipEventDisableTiming));
+		for (auto &e : ev) if (!e) HIP_TRY(hipEventCreate(&e));
+		return CVX_OK;
+	}
+	void release() {
+		h_zero.release(); zero_cap = 0;
+		h_seq.release(); h_delta.release(); h_rsrc.release(); h_rowsx.release(); h_tin.release();
+		d_delta.release(); d_rsrc.release(); d_rowsx.release(); h_plan.release(); h_trun.release(); h_tout.release();
+		h_lists.release(); h_goff.release(); h_res.release(); h_ops.release();
+		d_seq.release(); d_rows.release(); d_tin.release(); d_plan.release(); d_trun.release();
+		d_tout.release(); d_dirs.release(); d_regions.release(); d_lists.release();
+		d_counters.release(); d_dstoff.release(); d_dense.release(); d_res.release();
+		d_gscratch.release(); d_gscratch_off.release();
+		h_win.release(); d_win.release(); h_refs.release();
+		h_ext.release(); h_trec.release(); h_toff.release(); h_text.release();
+		d_ext.release(); d_trec.release(); d_tlen.release(); d_text.release();
+		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
+		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
+		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
+		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();
+		if (ev_in) { (void) hipEventDestroy(ev_in); ev_in = nullptr; }
+		if (ev_res) { (void) hipEventDestroy(ev_res); ev_res = nullptr; }
+		if (ev_ops) { (void) hipEventDestroy(ev_ops); ev_ops = nullptr; }
+		if (ev_bt0) { (void) hipEventDestroy(ev_bt0); ev_bt0 = nullptr; }
+		if (ev_bt1) { (void) hipEventDestroy(ev_bt1); ev_bt1 = nullptr; }
+		for (auto &e : ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
+		for (auto &e : lev) if (e) (void) hipEventDestroy(e);
+		lev.clear();
+	}
+};
+
+struct cvx_context {
+	int device = 0;
+	hipStream_t s_io = nullptr;      /* uploads, plan, downloads (high priority: its short kernels and copies
+	                                  * must not queue behind the fill's workgroups) */
+	hipStream_t s_main = nullptr;    /* forward fills (and the small input copies in front of them) */
+	hipStream_t s_text = nullptr;    /* the text stage of FINISHED jobs (cvx_job_text, nm profile): its own stream, never queued behind the
+	                                  * fills of the batches that follow */
+	hipStream_t s_post = nullptr;    /* backtrack, finalize, compaction, result download: runs beside the NEXT batch's fill */
+	hipStream_t aux[kAuxStreams] = {nullptr};  /* concurrent fill classes */
+	bool service = false;                      /* cvx_create_ex(CVX_CREATE_SERVICE): short search / scoring / decode calls only */
+	bool owns_main = true;                     /* false: s_main is one of the process's shared service streams */
+	std::mutex streams_mtx;                    /* ensure_streams */
+	std::atomic<bool> streams_ready{false};    /* ensure_streams: the whole set exists (stored last, with release: read without the mutex) */
+	/* a second set (main, post, aux) for small streaming jobs (experiment, off by default: see single_lane): the jobs of a
+	 * batching driver (tens of tiles each) are latency-bound chains of small kernels on an otherwise empty device;
+	 * consecutive ones can alternate between the two sets */
+	hipStream_t s_main2 = nullptr, s_post2 = nullptr, aux2[kAuxStreams] = {nullptr};
+	unsigned small_jobs = 0;         /* small streaming jobs queued so far (their parity picks the set) */
+	ScoreParams sp;
+	uint64_t max_matrix_mb = 10000;
+	int num_cus = 256;
+	int pack_threads = 16;
+	int tune_min_slots = 0;   /* tuning knob (env CVX_TUNE_MIN_M): smallest M*NW a tile may use */
+	int tune_late_min = kLateMinGroups;  /* test knob (env CVX_TUNE_LATE_MIN): groups of the exactly tracked tail (huge: exact everywhere) */
+	int tune_late_shift = kLateShift;    /* tuning knob (env CVX_TUNE_LATE_SHIFT): the exactly tracked tail is groups >> this (at least tune_late_min) */
+	int tune_max_slots = 0;   /* tuning knob (env CVX_TUNE_MAX_M): largest whole-tile ring class; wider tiles are chained */
+	int tune_long_need = 0;   /* tuning knob (env CVX_TUNE_LONG_NEED): see PlanTuning */
+	int tune_gang_prio = 0;   /* tuning knob (env CVX_TUNE_GANG_PRIO = 0 / 1): gang tiles at raised wave priority (measured: 26.9 against 24.0 ms, a loss) */
+	int tune_gangs = 0;       /* tuning knob (env CVX_TUNE_GANGS = 0 / 1): rings of 384 / 576 slots as gangs of two / three waves instead of chained row
+	                           * blocks.  Off: measured, the gangs lose -- the ONT mix's retry tiles alone 24.0 ms against 21.4 ms chained, the whole mix
+	                           * equal within noise (profiles/r05_gang_ab.txt): short tiles leave a 576-slot ring idle through its ramps (60 % slot use
+	                           * against 85 % for 64-row blocks), which eats the 1.6 x cheaper cell update, and three waves in lock step on three SIMDs
+	                           * wait for the slowest of them every step */
+	int tune_long_steps = 0, tune_small_batch = 0;   /* tuning knobs (env CVX_TUNE_LONG_STEPS / CVX_TUNE_SMALL_BATCH): see PlanTuning */
+	bool single_lane = true;  /* experiment (env CVX_TUNE_TWO_LANES=1 clears it): small streaming jobs alternate between two stream sets.
+	                           * Measured with the batching dispatcher at four launches in flight: no gain -- 20 000 reads 25.1 s against
+	                           * 21.2 s, launches get smaller and each still lasts as long as its slowest tile -- so it stays off. */
+	int tune_exact_steps = kExactDirectSteps;   /* tuning knob (env CVX_TUNE_EXACT_STEPS, 0 = off): tiles of this many steps go straight to the exact fill */
+	int tune_wide_prio = 1;   /* tuning knob (env CVX_TUNE_WIDE_PRIO = 0 / 1 / 2: off, priority 1, priority 2): the widest ring class of a batch of several one priority notch up */
+	int tune_chain_prio = -1; /* tuning knob (env CVX_TUNE_CHAIN_PRIO = 0 / 1): wave priority of chained blocks; -1 = the default (raised) */
+	int tune_chain_lds_kb = 48; /* tuning knob (env CVX_TUNE_CHAIN_LDS_KB): LDS per CU the residency cap of a chained class may hold while ring classes
+	                           * of the same batch run beside it (0 = no limit: round 5's rule) */
+	int tune_chain_m = 0;     /* test knob (env CVX_TUNE_CHAIN_M): row-block height class (1, 2, 4) of chained tiles */
+	int tune_force_wrap = 0;  /* test knob (env CVX_TUNE_FORCE_WRAP16): route every tile to the int16-run kernels */
+	int tune_pen_table = 1;   /* tuning knob (env CVX_TUNE_PEN_TABLE = 0 / 1): convex penalty from the LDS table in the two-phase float-score fills */
+	int test_fail_compute = 0; /* test knob (env CVX_TUNE_FAIL_COMPUTE = k): the k-th compute stage of this handle fails (error-path tests) */
+	int bt_group = 0;          /* lanes per tile in the backtrack: 0 = auto (by the number of tiles walked together: 64 / 32 / 16 / 8, and 32 for
+	                            * the much-longer-than-average reads of a bulk walked at 8 or 16), 8 / 16 / 32 = that many for all, 64 = the
+	                            * one-wave-per-tile walk, -1 = round 4's rule (64 below 4 096 tiles, else 8 + 32) (env CVX_TUNE_BT_GROUP) */
+	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
+	bool sse_variant = false; /* scoring outside the regime where the reference's SSE path equals the scalar recurrence:
+	                           * every tile goes to the catch-all kernel's SSE-variant instantiation */
+	/* freed batches keep their device arenas and pinned staging and wait here for the next upload
+	 * (at most kPoolBatches): hipMalloc / hipFree of multi-GB arenas per call are slow, and hipFree
+	 * synchronises the whole device, which would serialise handles that work side by side */
+	size_t marks[cvx_batch_s::kSharedMarks] = {0};   /* high-water marks of the streaming slots' buffers (cvx_batch_s::bind) */
+	std::vector<cvx_batch_s *> pool;
+	std::vector<cvx_batch_s *> pending;      /* streaming jobs whose compute stage is not queued yet */
+	std::vector<cvx_batch_s *> live;         /* every streaming job the caller has not released yet (cvx_destroy frees what is left) */
+	float decode_kernel_ms = 0.0f;     /* decode_windows_kernel of the last cvx_genome_decode (cvx_stage_kernel_ms) */
+	bool score_no_diag = false;   /* test knob (env CVX_TUNE_SCORE_NO_DIAG): always the row-by-row kernels */
+	struct cvx_score_state *score = nullptr;   /* sub-read scoring (cvx_score_batch, cvx_score_submit): jobs kept for reuse once waited for */
+	struct cvx_search_state *search = nullptr;   /* candidate search (cvx_search_batch): persistent staging and device buffers */
+};
+
+struct cvx_genome_s {            /* an encoded reference genome resident in HBM (cvx_genome.hip) */
+	int device = 0;
+	uint64_t n_nibbles = 0;
+	int32_t n_starts = 0;
+	DevBuf<uint8_t> d_bin;
+	DevBuf<uint64_t> d_starts;
+};
+
+#endif

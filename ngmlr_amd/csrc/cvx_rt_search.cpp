@@ -1,0 +1,636 @@
+/*
+ * cvx_rt_search.cpp -- the search side of libcvxalign.so: the reference genome resident in HBM and the decode of
+ * its windows (cvx_genome.hip), ngmlr's k-mer table on the device, uploaded or built there (cvx_index.hip), and the candidate
+ * search of a batch of reads over it (cvx_search.hip).
+ */
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "cvx_index_build.h"
+#include "cvx_rt.h"
+
+/* Per-handle state of the candidate search: staging and device buffers live as long as the handle, so that the steady
+ * state of a caller that searches batch after batch (ngmlr's CS threads: a few hundred sub-reads per call) allocates
+ * nothing, copies through page-locked memory and sleeps on a blocking event while the device works. */
+struct cvx_search_state {
+	PinBuf h_seq, h_meta, h_out;       /* reads; offsets + lengths + list offsets + work list + dense begins; results coming back */
+	DevBuf<uint8_t> d_seq;
+	DevBuf<uint64_t> d_off, d_listoff, d_begin, d_srcoff;
+	PinBuf h_srcoff;
+	DevBuf<int32_t> d_len, d_ncand, d_work, d_miss;
+	DevBuf<unsigned long long> d_events;
+	DevBuf<float> d_maxhit, d_scores;
+	DevBuf<uint32_t> d_rlist, d_undo;
+	DevBuf<unsigned int> d_ticket;
+	size_t tables_clean_words = 0;     /* this much of d_keys is known to hold nothing but empty slots (search_wave_hbm_kernel's tables) */
+	DevBuf<SearchCandidate> d_cand, d_dense;
+	DevBuf<uint64_t> d_keys;
+	hipEvent_t done = nullptr;
+	/* kernel time of the last call (cvx_stage_kernel_ms): an event pair around every kernel launch of the call, summed when it ends */
+	std::vector<int32_t> attempts;     /* per read of the last call: table sizes tried (cvx_search_last_attempts) */
+	std::vector<hipEvent_t> kev;
+	size_t kev_used = 0;
+	float kernel_ms = 0.0f;
+	int kmark(hipStream_t st) {
+		if (kev_used == kev.size()) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); kev.push_back(e); }
+		HIP_TRY(hipEventRecord(kev[kev_used++], st));
+		return CVX_OK;
+	}
+	void release() {
+		for (hipEvent_t e : kev) (void) hipEventDestroy(e);
+		kev.clear(); kev_used = 0;
+		h_seq.release(); h_meta.release(); h_out.release();
+		d_seq.release(); d_off.release(); d_listoff.release(); d_begin.release(); d_srcoff.release(); h_srcoff.release(); d_len.release(); d_ncand.release(); d_work.release(); d_miss.release();
+		d_events.release(); d_maxhit.release(); d_scores.release(); d_rlist.release(); d_undo.release(); d_ticket.release(); d_cand.release(); d_dense.release(); d_keys.release();
+		if (done) { (void) hipEventDestroy(done); done = nullptr; }
+	}
+};
+
+namespace {
+/* everything queued on `st` so far is done; the calling thread sleeps meanwhile (hipStreamSynchronize spins) */
+int search_wait(cvx_search_state *ss, hipStream_t st) {
+	if (!ss->done) HIP_TRY(hipEventCreateWithFlags(&ss->done, hipEventBlockingSync | hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(ss->done, st));
+	HIP_TRY(hipEventSynchronize(ss->done));
+	return CVX_OK;
+}
+}  // namespace
+
+namespace cvx {
+void search_state_free(cvx_search_state *ss) {
+	if (!ss) return;
+	ss->release();
+	delete ss;
+}
+
+float search_kernel_ms(const cvx_search_state *ss) { return ss ? ss->kernel_ms : 0.0f; }
+}  // namespace cvx
+
+extern "C" {
+
+/* ------------------------------------------------------------------ resident genome (decode half) */
+
+int cvx_genome_upload(cvx_handle h, const uint8_t *bin_ref, uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts, cvx_genome *out) {
+	ABI_GUARD_BEGIN
+	if (!h || !out || !bin_ref || !start_table || n_starts < 2 || n_nibbles < 2) { set_err("cvx_genome_upload: bad argument"); return CVX_ERR_ARG; }
+	*out = nullptr;
+	for (int32_t i = 1; i < n_starts; ++i)
+		if (start_table[i] <= start_table[i - 1]) { set_err("cvx_genome_upload: start table not ascending at %d", i); return CVX_ERR_ARG; }
+	HIP_TRY(hipSetDevice(h->device));
+	cvx_genome_s *g = new (std::nothrow) cvx_genome_s();
+	if (!g) return CVX_ERR_OOM;
+	g->device = h->device;
+	g->n_nibbles = n_nibbles;
+	g->n_starts = n_starts;
+	/* a window may start or end in the last spacer: decode() reads up to a byte past the last nibble pair */
+	const size_t bytes = (size_t) ((n_nibbles + 1) / 2);
+	int rc = g->d_bin.ensure(bytes + 64);
+	if (rc == CVX_OK) rc = g->d_starts.ensure((size_t) n_starts);
+	if (rc != CVX_OK) { g->d_bin.release(); g->d_starts.release(); delete g; return rc; }
+	hipError_t e = hipMemset(g->d_bin.p, 0x44, g->d_bin.cap);        /* beyond the genome: N */
+	if (e == hipSuccess) e = hipMemcpy(g->d_bin.p, bin_ref, bytes, hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMemcpy(g->d_starts.p, start_table, (size_t) n_starts * sizeof(uint64_t), hipMemcpyHostToDevice);
+	if (e != hipSuccess) {
+		set_err("cvx_genome_upload: %s", hipGetErrorString(e));
+		g->d_bin.release(); g->d_starts.release(); delete g;
+		return CVX_ERR_HIP;
+	}
+	*out = g;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+void cvx_genome_free(cvx_handle h, cvx_genome g) {
+	ABI_GUARD_BEGIN
+	if (!g) return;
+	if (h) { (void) hipSetDevice(h->device); (void) hipDeviceSynchronize(); }
+	g->d_bin.release();
+	g->d_starts.release();
+	delete g;
+	ABI_GUARD_END_VOID
+}
+
+int cvx_genome_decode(cvx_handle h, cvx_genome g, int32_t n, const uint64_t *position, const int32_t *length,
+		const uint64_t *out_offset, char *out) {
+	ABI_GUARD_BEGIN
+	if (!h || !g || n < 0 || (n > 0 && (!position || !length || !out_offset || !out))) { set_err("cvx_genome_decode: bad argument"); return CVX_ERR_ARG; }
+	if (n == 0) return CVX_OK;
+	HIP_TRY(hipSetDevice(h->device));
+	std::vector<WindowDesc> win((size_t) n);
+	uint64_t total = 0;
+	for (int i = 0; i < n; ++i) {
+		if (length[i] < 1) { set_err("cvx_genome_decode: window %d has length %d", i, length[i]); return CVX_ERR_ARG; }
+		win[(size_t) i].position = position[i];
+		win[(size_t) i].dst_off = total;
+		win[(size_t) i].n_chars = (int64_t) length[i] - 1;           /* the reference's last byte is the NUL */
+		total += (uint64_t) length[i];
+	}
+	DevBuf<uint8_t> d_out;
+	DevBuf<WindowDesc> d_win;
+	RC_TRY(d_out.ensure((size_t) total + 64));
+	int rc = d_win.ensure((size_t) n);
+	if (rc != CVX_OK) { d_out.release(); return rc; }
+	std::vector<uint8_t> host((size_t) total);
+	hipStream_t st = h->s_main;
+	hipError_t e = hipMemsetAsync(d_out.p, 0, (size_t) total, st);   /* the NUL that ends every window */
+	if (e == hipSuccess) e = hipMemcpyAsync(d_win.p, win.data(), (size_t) n * sizeof(WindowDesc), hipMemcpyHostToDevice, st);
+	hipEvent_t k0 = nullptr, k1 = nullptr;      /* the kernel alone, on its own stream */
+	if (e == hipSuccess) e = hipEventCreate(&k0);
+	if (e == hipSuccess) e = hipEventCreate(&k1);
+	if (e == hipSuccess) e = hipEventRecord(k0, st);
+	if (e == hipSuccess) e = launch_decode_windows(g->d_bin.p, g->d_starts.p, g->n_starts, d_win.p, n, d_out.p, st);
+	if (e == hipSuccess) e = hipEventRecord(k1, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out.p, (size_t) total, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess) h->decode_kernel_ms = ev_ms(k0, k1);
+	if (k0) (void) hipEventDestroy(k0);
+	if (k1) (void) hipEventDestroy(k1);
+	d_out.release();
+	d_win.release();
+	if (e != hipSuccess) { set_err("cvx_genome_decode: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
+	for (int i = 0; i < n; ++i) memcpy(out + out_offset[i], host.data() + win[(size_t) i].dst_off, (size_t) length[i]);
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+/* ------------------------------------------------------------------ candidate search (search half) */
+
+struct cvx_index_s {             /* one unit of ngmlr's CompactPrefixTable, resident in HBM (cvx_search.hip) */
+	int device = 0;
+	int32_t k = 0;
+	uint64_t n_index = 0;        /* 4^k + 2 */
+	uint64_t unit_offset = 0;
+	uint32_t n_locs = 0;
+	DevBuf<uint2> d_rows;            /* (row start, row length | used << 31) per prefix: SearchArgs::rows */
+	DevBuf<uint32_t> d_locs;
+};
+
+/* a table cvx_index_build_device(CVX_INDEX_KEEP_RESIDENT) left on its device: the next cvx_index_upload of these very host
+ * arrays on that device takes it over instead of reading 4^k records on the host and copying a gigabyte back up */
+struct ResidentTable {
+	std::mutex mtx;
+	int device = -1;
+	int32_t k = 0;
+	const void *index = nullptr;
+	const uint32_t *locs = nullptr;
+	uint64_t n_locs = 0;
+	void *d_rows = nullptr;
+	uint32_t *d_locs = nullptr;
+	void drop() {      /* (mtx held) */
+		if (device >= 0 && (d_rows || d_locs)) { (void) hipSetDevice(device); if (d_rows) (void) hipFree(d_rows); if (d_locs) (void) hipFree(d_locs); }
+		device = -1; d_rows = nullptr; d_locs = nullptr; index = nullptr; locs = nullptr;
+	}
+} g_resident_table;
+
+int cvx_index_upload(cvx_handle h, int32_t k, const void *index, const uint32_t *locs, uint32_t n_locs, uint64_t unit_offset, cvx_index *out) {
+	ABI_GUARD_BEGIN
+	if (!h || !out || !index || (n_locs > 0 && !locs) || k < 4 || k > 15) { set_err("cvx_index_upload: bad argument (kmer_len 4..15)"); return CVX_ERR_ARG; }
+	*out = nullptr;
+	HIP_TRY(hipSetDevice(h->device));
+	const uint64_t n_index = (1ull << (2 * k)) + 2ull;
+	{
+		std::lock_guard<std::mutex> lk(g_resident_table.mtx);
+		ResidentTable &r = g_resident_table;
+		if (r.device == h->device && r.k == k && r.index == index && r.locs == locs && r.n_locs == n_locs && r.d_rows && r.d_locs) {
+			cvx_index_s *ix = new (std::nothrow) cvx_index_s();
+			if (!ix) return CVX_ERR_OOM;
+			ix->device = h->device; ix->k = k; ix->n_index = n_index; ix->unit_offset = unit_offset; ix->n_locs = n_locs;
+			ix->d_rows.p = static_cast<uint2 *>(r.d_rows); ix->d_rows.cap = (size_t) n_index - 1;
+			ix->d_locs.p = r.d_locs; ix->d_locs.cap = (size_t) n_locs + 1;
+			r.device = -1; r.d_rows = nullptr; r.d_locs = nullptr; r.index = nullptr; r.locs = nullptr;
+			*out = ix;
+			return CVX_OK;
+		}
+	}
+	/* the 5-byte Index records (uint m_TabIndex; char m_RevCompIndex, #pragma pack(1): src/PrefixTable.h:15-31) as one 8-byte
+	 * record per prefix: where GetRefEntry's row starts (m_TabIndex - 1), how long it is (the next record's m_TabIndex - this
+	 * one's, PrefixTable.cpp:476-532) and Index::used() */
+	const uint8_t *p = static_cast<const uint8_t *>(index);
+	auto tab_at = [&](uint64_t i) { uint32_t t; memcpy(&t, p + 5 * i, 4); return t; };
+	std::vector<uint2> rows;
+	try { rows.resize((size_t) n_index - 1); } catch (const std::bad_alloc &) { set_err("cvx_index_upload: out of host memory"); return CVX_ERR_OOM; }
+	for (uint64_t i = 0; i + 1 < n_index; ++i) {
+		const uint32_t t0 = tab_at(i), t1 = tab_at(i + 1);
+		const bool used = p[5 * i + 4] != 0;                  /* Index::used() */
+		if (used && (t0 == 0 || t1 < t0 || (uint64_t) t1 - 1 > n_locs || t1 - t0 > 0x7FFFFFFFu)) {
+			set_err("cvx_index_upload: index entry %llu points outside the %u locations", (unsigned long long) i, n_locs);
+			return CVX_ERR_ARG;
+		}
+		rows[(size_t) i] = make_uint2(used ? t0 - 1u : 0u, used ? ((t1 - t0) | 0x80000000u) : 0u);
+	}
+	cvx_index_s *ix = new (std::nothrow) cvx_index_s();
+	if (!ix) return CVX_ERR_OOM;
+	ix->device = h->device; ix->k = k; ix->n_index = n_index; ix->unit_offset = unit_offset; ix->n_locs = n_locs;
+	int rc = ix->d_rows.ensure(rows.size());
+	if (rc == CVX_OK) rc = ix->d_locs.ensure((size_t) n_locs + 1);
+	hipError_t e = hipSuccess;
+	if (rc == CVX_OK) {
+		e = hipMemcpy(ix->d_rows.p, rows.data(), rows.size() * sizeof(uint2), hipMemcpyHostToDevice);
+		if (e == hipSuccess && n_locs) e = hipMemcpy(ix->d_locs.p, locs, (size_t) n_locs * 4, hipMemcpyHostToDevice);
+	}
+	if (rc != CVX_OK || e != hipSuccess) {
+		if (e != hipSuccess) { set_err("cvx_index_upload: %s", hipGetErrorString(e)); rc = CVX_ERR_HIP; }
+		ix->d_rows.release(); ix->d_locs.release(); delete ix;
+		return rc;
+	}
+	*out = ix;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_index_build_device(int32_t device_id, const uint8_t *bin_ref, uint64_t n_nibbles, const uint64_t *start_table, const uint64_t *seq_lengths, int32_t n_seqs,
+		int32_t kmer_len, int32_t ref_skip, int32_t bin_shift, void *ref_table_index, uint32_t *ref_table, uint64_t ref_table_capacity,
+		uint64_t *n_locations, uint32_t flags) {
+	ABI_GUARD_BEGIN
+	if (!bin_ref || !start_table || !seq_lengths || n_seqs <= 0 || kmer_len < 4 || kmer_len > 15 || ref_skip < 0 || bin_shift < 0 || bin_shift > 30 ||
+			!ref_table_index || !n_locations) { set_err("cvx_index_build_device: bad argument (kmer_len 4..15, bin_shift 0..30)"); return CVX_ERR_ARG; }
+	for (int32_t s = 0; s < n_seqs; ++s) {
+		if ((start_table[s] & 1ull) || start_table[s] + seq_lengths[s] > n_nibbles) { set_err("cvx_index_build_device: sequence %d does not start on a byte or leaves the genome", s); return CVX_ERR_ARG; }
+		if (s > 0 && start_table[s] < start_table[s - 1]) { set_err("cvx_index_build_device: sequences out of order (a row lists its locations in walk order)"); return CVX_ERR_ARG; }
+	}
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void) hipGetLastError(); set_err("cvx_index_build_device: no HIP device"); return CVX_ERR_NO_DEVICE; }
+	if (device_id < 0 || device_id >= ndev) { set_err("cvx_index_build_device: device %d of %d", device_id, ndev); return CVX_ERR_ARG; }
+	HIP_TRY(hipSetDevice(device_id));
+	hipStream_t st = nullptr;
+	HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+	char err[320];
+	err[0] = 0;
+	const bool keep = (flags & CVX_INDEX_KEEP_RESIDENT) != 0u;
+	void *d_rows = nullptr;
+	uint32_t *d_locs = nullptr;
+	const int rc = index_build_device(bin_ref, n_nibbles, start_table, seq_lengths, n_seqs, kmer_len, ref_skip, bin_shift, ref_table_index, ref_table,
+			ref_table_capacity, n_locations, st, err, sizeof(err), keep ? &d_rows : nullptr, keep ? &d_locs : nullptr);
+	(void) hipStreamSynchronize(st);
+	(void) hipStreamDestroy(st);
+	if (rc != CVX_OK) set_err("cvx_index_build_device: %s", err);
+	if (keep) {
+		std::lock_guard<std::mutex> lk(g_resident_table.mtx);
+		g_resident_table.drop();                                  /* one table waits at a time */
+		if (rc == CVX_OK && d_rows && d_locs) {
+			g_resident_table.device = device_id; g_resident_table.k = kmer_len; g_resident_table.index = ref_table_index; g_resident_table.locs = ref_table;
+			g_resident_table.n_locs = *n_locations; g_resident_table.d_rows = d_rows; g_resident_table.d_locs = d_locs;
+		}
+	}
+	return rc;
+	ABI_GUARD_END
+}
+
+void cvx_index_free(cvx_handle h, cvx_index ix) {
+	ABI_GUARD_BEGIN
+	if (!ix) return;
+	if (h) { (void) hipSetDevice(h->device); (void) hipDeviceSynchronize(); }
+	ix->d_rows.release(); ix->d_locs.release();
+	delete ix;
+	ABI_GUARD_END_VOID
+}
+
+} /* extern "C" */
+
+/* the reads either as n NUL-terminated strings (seqs / lens) or back to back in one block (arena / offsets: read i =
+ * arena[offsets[i] .. offsets[i + 1] - 1) with a NUL at offsets[i + 1] - 1) */
+static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *const *seqs, const int32_t *lens, const uint8_t *arena, const uint64_t *offsets,
+		float sensitivity, float min_hits, int32_t bin_shift, int32_t first_bits,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+		float *max_hit, int32_t *kmer_misses) {
+	static_assert(sizeof(SearchCandidate) == sizeof(cvx_candidate), "SearchCandidate mirrors cvx_candidate");
+	/* bin_shift >= 1: the "bin is listed" flag lives in bit 63 of the vote table's key, and with a shift of 0 a vote near the
+	 * start of the genome (location - offset in the read < 0) would set that bit itself; ngmlr's bin size is 4 */
+	if (!h || !ix || n < 0 || (n > 0 && ((!arena && (!seqs || !lens)) || (arena && !offsets) || !n_candidates || !cand_begin)) || bin_shift < 1 || bin_shift > 30 ||
+			(first_bits != 0 && (first_bits < 8 || first_bits > 20))) {
+		set_err("cvx_search_batch: bad argument (bin_shift 1..30, first_bits 0 or 8..20)"); return CVX_ERR_ARG;
+	}
+	if (ix->device != h->device) { set_err("cvx_search_batch: the index lives on device %d, the handle on %d", ix->device, h->device); return CVX_ERR_ARG; }
+	if (cand_used) *cand_used = 0;
+	if (n == 0) return CVX_OK;
+	HIP_TRY(hipSetDevice(h->device));
+	if (!h->search) { h->search = new (std::nothrow) cvx_search_state(); if (!h->search) return CVX_ERR_OOM; }
+	cvx_search_state *ss = h->search;
+	hipStream_t st = h->s_main;
+	/* the reads, a NUL behind each (the N-run scan of PrefixIteration relies on the terminator), in page-locked staging */
+	uint64_t bytes = 0;
+	if (arena) {
+		for (int i = 0; i < n; ++i) {
+			if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 0x7FFFFFFFull || arena[offsets[i + 1] - 1] != 0) {
+				set_err("cvx_search_batch_arena: read %d is not [offsets[i], offsets[i + 1] - 1) followed by a NUL", i); return CVX_ERR_ARG;
+			}
+		}
+		bytes = offsets[n] - offsets[0];
+	} else {
+		for (int i = 0; i < n; ++i) {
+			if (!seqs[i] || lens[i] < 0) { set_err("cvx_search_batch: bad read %d", i); return CVX_ERR_ARG; }
+			bytes += (uint64_t) lens[i] + 1;
+		}
+	}
+	const size_t n1 = (size_t) n;
+	/* a block that lies in memory from cvx_host_alloc travels as it is: the host touches no base (the 64 bytes behind the last read
+	 * that the kernels may read are cleared on the device) */
+	const uint8_t *src = arena ? arena + offsets[0] : nullptr;
+	const bool zero_copy = arena && in_pinned_block(reinterpret_cast<const char *>(src), bytes + 4);
+	if (!zero_copy) RC_TRY(ss->h_seq.ensure((size_t) bytes + 64));
+	/* meta: [off u64 n][list_off u64 n][begin u64 n][len i32 n][work i32 n] */
+	RC_TRY(ss->h_meta.ensure(n1 * (8 + 8 + 8 + 4 + 4) + 64));
+	/* out: [events u64 n][ncand i32 n][miss i32 n][maxhit f32 n] (the dense candidates get their own buffer below) */
+	RC_TRY(ss->h_out.ensure(n1 * (8 + 4 + 4 + 4) + 64));
+	uint8_t *hseq = zero_copy ? nullptr : ss->h_seq.as<uint8_t>();
+	uint64_t *h_off = ss->h_meta.as<uint64_t>(), *h_listoff = h_off + n1, *h_begin = h_listoff + n1;
+	int32_t *h_len = reinterpret_cast<int32_t *>(h_begin + n1), *h_work = h_len + n1;
+	unsigned long long *h_events = ss->h_out.as<unsigned long long>();
+	int32_t *h_ncand = reinterpret_cast<int32_t *>(h_events + n1), *h_miss = h_ncand + n1;
+	float *h_maxhit = reinterpret_cast<float *>(h_miss + n1);
+	if (arena) {
+		for (int i = 0; i < n; ++i) { h_off[i] = offsets[i] - offsets[0]; h_len[i] = (int32_t) (offsets[i + 1] - offsets[i] - 1); }
+		if (!zero_copy) { memcpy(hseq, src, (size_t) bytes); memset(hseq + bytes, 0, 64); }
+	} else {
+		uint64_t at = 0;
+		for (int i = 0; i < n; ++i) {
+			h_off[i] = at;
+			memcpy(hseq + at, seqs[i], (size_t) lens[i]);
+			hseq[at + (uint64_t) lens[i]] = 0;
+			at += (uint64_t) lens[i] + 1;
+			h_len[i] = lens[i];
+		}
+		memset(hseq + at, 0, 64);
+	}
+	RC_TRY(ss->d_seq.ensure((size_t) bytes + 64));
+	RC_TRY(ss->d_off.ensure(n1)); RC_TRY(ss->d_listoff.ensure(n1)); RC_TRY(ss->d_begin.ensure(n1));
+	RC_TRY(ss->d_len.ensure(n1)); RC_TRY(ss->d_ncand.ensure(n1)); RC_TRY(ss->d_work.ensure(n1)); RC_TRY(ss->d_miss.ensure(n1));
+	RC_TRY(ss->d_events.ensure(n1)); RC_TRY(ss->d_maxhit.ensure(n1));
+	SearchArgs a;
+	memset(&a, 0, sizeof(a));
+	a.rows = ix->d_rows.p; a.locs = ix->d_locs.p; a.unit_offset = ix->unit_offset; a.k = ix->k;
+	a.seq = ss->d_seq.p; a.seq_off = ss->d_off.p; a.seq_len = ss->d_len.p; a.n = n;
+	a.events = ss->d_events.p; a.list_off = ss->d_listoff.p; a.n_cand = ss->d_ncand.p; a.max_hit = ss->d_maxhit.p; a.kmer_misses = ss->d_miss.p;
+	a.sensitivity = sensitivity; a.min_hits = min_hits; a.bin_shift = bin_shift;
+	if (zero_copy) {
+		HIP_TRY(hipMemsetAsync(ss->d_seq.p + bytes / 4 * 4, 0, 68, st));      /* what lies behind the block, first: the copy below is rounded up to whole dwords */
+		HIP_TRY(hipMemcpyAsync(ss->d_seq.p, src, (size_t) ((bytes + 3) / 4 * 4), hipMemcpyHostToDevice, st));
+	} else {
+		HIP_TRY(hipMemcpyAsync(ss->d_seq.p, hseq, (size_t) ((bytes + 63) / 4 * 4), hipMemcpyHostToDevice, st));
+	}
+	HIP_TRY(hipMemcpyAsync(ss->d_off.p, h_off, n1 * 8, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(ss->d_len.p, h_len, n1 * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemsetAsync(ss->d_miss.p, 0, n1 * 4, st));
+	HIP_TRY(hipMemsetAsync(ss->d_maxhit.p, 0, n1 * 4, st));
+	/* A read starts on the wave-per-read kernel with its vote map in LDS (cvx_search.hip), in the smallest map that certainly holds
+	 * it: a call of CVX_TUNE_SEARCH_CLASSIFY (2 048) reads or more counts every read's votes first (one cheap kernel and one round
+	 * trip) and sorts the reads into launches by map size -- 6 KB of LDS for a read of <= 384 votes, 24 KB for <= 1 536, 48 KB
+	 * above -- so that as many reads as possible share a CU; a smaller call takes the 2^11-slot map for every read without
+	 * counting (its reads do not fill the device anyway).  A read that does not fit its map after all (more than 3 072 bins; a bin
+	 * beyond 32 bits; longer than the sequence buffer) is redone -- the same attempt, then the rest of the ladder -- by the same
+	 * kernel over the real table in HBM, which needs the vote count to size its lists.  Candidates of read i lie at d_cand +
+	 * src_off[i]: two per bin its map can hold (or per vote, when that is fewer) for an LDS-map read, the sparse region behind all
+	 * of those (two slots per vote) for the others.  CVX_TUNE_SEARCH_WAVE=2 sends every read to the HBM-table form, =0 to the
+	 * lane-per-read kernel (one serial chain of votes per read; an independent implementation: tests, A/B);
+	 * CVX_TUNE_SEARCH_LOG2=9..12 forces one map size (tests: a small one sends most reads through the fall-back). */
+	const char *wave_env = getenv("CVX_TUNE_SEARCH_WAVE");      /* (read per call: the parity tests switch it inside one process) */
+	const int wave_mode = wave_env ? atoi(wave_env) : 1;
+	const bool use_wave = wave_mode == 1;
+	const bool lane_serial = wave_mode == 0;
+	const char *cls_env = getenv("CVX_TUNE_SEARCH_CLASSIFY"), *log2_env = getenv("CVX_TUNE_SEARCH_LOG2"), *slot8_env = getenv("CVX_TUNE_SEARCH_SLOT8");
+	const int classify_min = cls_env ? atoi(cls_env) : 2048;
+	const int forced_log2 = log2_env ? std::min(kSearchWaveLog2Max, std::max(kSearchWaveLog2Min, atoi(log2_env))) : 0;
+	/* (a table with three locations per k-mer and more -- a genome of 600 Mbp and up at ngmlr's defaults -- gives a 256-base read
+	 * 1 500 votes and more: the one-size map of a small call would not hold it, so its reads are counted and sorted as well) */
+	const bool big_table = (uint64_t) ix->n_locs >= 3ull * (ix->n_index - 2ull);
+	const bool classify = use_wave && !forced_log2 && (n >= classify_min || big_table);
+	bool counted = false;
+	uint64_t total = 0;             /* votes of the reads that took the HBM-table form so far: their rList / candidate regions */
+	std::vector<uint8_t> has_region(n1, 0);
+	ss->kev_used = 0;
+	ss->kernel_ms = 0.0f;
+	auto count_votes = [&]() -> int {      /* votes per read (all reads: the pass is cheap): map sizes, sizes of the HBM kernel's lists */
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(launch_search_count(a, st));
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(hipMemcpyAsync(h_events, ss->d_events.p, n1 * 8, hipMemcpyDeviceToHost, st));
+		RC_TRY(search_wait(ss, st));
+		counted = true;
+		return CVX_OK;
+	};
+	if (classify) RC_TRY(count_votes());
+	std::vector<uint8_t> map_log2(n1, 0);      /* 0: not an LDS-map read */
+	RC_TRY(ss->d_srcoff.ensure(n1));
+	RC_TRY(ss->h_srcoff.ensure(n1 * 8));
+	uint64_t *h_srcoff = ss->h_srcoff.as<uint64_t>();
+	uint64_t fixed_total = 0;
+	for (int i = 0; i < n; ++i) {
+		h_srcoff[i] = fixed_total;
+		if (!use_wave || h_len[i] + 1 > kSearchWaveSeq) continue;
+		const int l = forced_log2 ? forced_log2 : classify ? search_wave_log2(h_events[i]) : kSearchWaveLog2Default;
+		map_log2[(size_t) i] = (uint8_t) l;
+		uint64_t bins = (uint64_t) search_wave_entries(l);
+		if (classify && h_events[i] < bins) bins = h_events[i];
+		fixed_total += 2 * bins;
+	}
+	RC_TRY(ss->d_cand.ensure((size_t) fixed_total + 64));
+	HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
+	/* Regions only for the reads that really go to the HBM-table form, handed out when a read first gets there and kept for its
+	 * retries (sizing them by the votes of all n reads cost a repeat-rich call gigabytes per handle).  The
+	 * candidate arena grows without losing the lists already in it. */
+	auto give_regions = [&](const std::vector<int32_t> &reads) -> int {
+		bool grew = false;
+		for (int32_t i : reads) {
+			if (has_region[(size_t) i]) continue;
+			has_region[(size_t) i] = 1;
+			h_listoff[i] = total;
+			total += h_events[i];
+			grew = true;
+		}
+		if (!grew) return CVX_OK;
+		RC_TRY(ss->d_rlist.ensure((size_t) total + 64));
+		if (ss->d_cand.cap < (size_t) (fixed_total + 2 * total) + 64) {
+			DevBuf<SearchCandidate> bigger;
+			RC_TRY(bigger.ensure((size_t) (fixed_total + 2 * total) + (size_t) total / 2 + 64));
+			hipError_t e = hipMemcpyAsync(bigger.p, ss->d_cand.p, ss->d_cand.cap * sizeof(SearchCandidate), hipMemcpyDeviceToDevice, st);
+			int rc = CVX_OK;
+			if (e != hipSuccess) { set_err("cvx_search_batch: %s", hipGetErrorString(e)); rc = CVX_ERR_HIP; }
+			if (rc == CVX_OK) rc = search_wait(ss, st);
+			if (rc != CVX_OK) { bigger.release(); return rc; }      /* (this buffer leaked on the error paths) */
+			ss->d_cand.release();
+			ss->d_cand = bigger;
+		}
+		HIP_TRY(hipMemcpyAsync(ss->d_listoff.p, h_listoff, n1 * 8, hipMemcpyHostToDevice, st));
+		return CVX_OK;
+	};
+	/* the reference's retry ladder (CS.cpp:345-394): the current table size with a probe budget of a third of the table, then
+	 * that + 2, + 3, ... up to 2^20 entries with 0.777; first_bits = CS::c_SrchTableBitLen (16 when the thread starts; the
+	 * reference adapts it per batch, CS.cpp:482-489 -- the size only decides WHEN an attempt runs out of budget, a successful
+	 * attempt returns the same list at every size). */
+	const int bits0 = first_bits ? first_bits : 16;
+	const bool trace = getenv("CVX_SEARCH_TRACE") != nullptr;      /* one line per call on stderr: who ran where, for how long (read per call: tests switch it on inside a process) */
+	const std::chrono::steady_clock::time_point tr0 = std::chrono::steady_clock::now();
+	std::string tr;
+	auto tr_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
+	std::vector<int32_t> work_wave, work_hbm;
+	for (int i = 0; i < n; ++i) (map_log2[(size_t) i] ? work_wave : work_hbm).push_back(i);
+	ss->attempts.assign(n1, 0);
+	for (int attempt = 0; !work_wave.empty() || !work_hbm.empty(); ++attempt) {
+		const int bits = attempt == 0 ? bits0 : bits0 + 1 + attempt;
+		if (bits > 20) break;
+		for (int32_t i : work_wave) ss->attempts[(size_t) i] += 1;
+		for (int32_t i : work_hbm) ss->attempts[(size_t) i] += 1;
+		a.bits = bits;
+		a.hpoc_factor = attempt == 0 ? 0.333f : 0.777f;
+		std::vector<int32_t> next_wave, next_hbm, hbm_now(work_hbm);
+		if (!work_wave.empty()) {
+			/* one launch per map size, back to back (the work list holds the sizes' reads one after the other) */
+			size_t at = 0;
+			a.cand = ss->d_cand.p; a.cand_off = ss->d_srcoff.p;
+			for (int l = kSearchWaveLog2Min; l <= kSearchWaveLog2Max; ++l) {
+				const size_t first = at;
+				int longest = 0;
+				for (int32_t i : work_wave) if (map_log2[(size_t) i] == l) { h_work[at++] = i; longest = std::max(longest, h_len[i]); }
+				if (at == first) continue;
+				HIP_TRY(hipMemcpyAsync(ss->d_work.p + first, h_work + first, (at - first) * 4, hipMemcpyHostToDevice, st));
+				a.work = ss->d_work.p + first;
+				a.n_work = (int32_t) (at - first);
+				RC_TRY(ss->kmark(st));
+				/* the 8-byte map where it applies: the reference's default table size or below, sub-reads (a count of 255 is out of
+				 * reach of a read's 256 k-mers unless a row repeats inside a bin), not the largest map; CVX_TUNE_SEARCH_SLOT8=0 / 1 */
+				const bool slot8 = slot8_env ? atoi(slot8_env) != 0 && bits <= 16 && l < kSearchWaveLog2Max : (bits <= 16 && l < kSearchWaveLog2Max && longest <= 268);
+				HIP_TRY(launch_search_wave(a, l, (longest + 65 + 63) / 64 * 64, slot8, st));
+				RC_TRY(ss->kmark(st));
+				if (trace) { char b[96]; snprintf(b, sizeof(b), " [2^%d-slot maps: %zu reads]", l, at - first); tr += b; }
+			}
+			a.work = ss->d_work.p;
+			HIP_TRY(hipMemcpyAsync(h_ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
+			RC_TRY(search_wait(ss, st));
+			for (int32_t i : work_wave) {
+				if (h_ncand[i] == kSearchNeedsHbm) hbm_now.push_back(i);
+				else if (h_ncand[i] < 0) next_wave.push_back(i);
+			}
+			if (trace) { char b[160]; snprintf(b, sizeof(b), " [bits %d wave %zu -> %zu to hbm, %zu retry, at %.2f ms]", bits, work_wave.size(), hbm_now.size() - work_hbm.size(), next_wave.size(), tr_ms()); tr += b; }
+		}
+		if (!hbm_now.empty()) {
+			a.work = ss->d_work.p;
+			if (!counted) RC_TRY(count_votes());
+			RC_TRY(give_regions(hbm_now));
+			for (int32_t i : hbm_now) h_srcoff[i] = fixed_total + 2 * h_listoff[i];
+			const size_t per_read = (size_t) 1 << bits;
+			a.rlist = ss->d_rlist.p; a.cand = ss->d_cand.p + fixed_total;
+			if (!lane_serial) {
+				/* the wave kernel's tables belong to the waves: as many as can be resident (or as 8 GB hold), each 2^bits entries of 16
+				 * bytes, empty between launches -- a wave frees the slots a read opened when the read is done -- so they are cleared
+				 * when they are allocated, when the table size changes and after a launch that failed, not per read */
+				RC_TRY(ss->d_undo.ensure((size_t) total + 64));
+				a.undo = ss->d_undo.p;
+				const size_t n_tables = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(hbm_now.size(), 8192), ((size_t) 8 << 30) / (per_read * 16)));
+				const size_t need_words = n_tables * per_read * 2;
+				if (ss->d_keys.cap < need_words) { RC_TRY(ss->d_keys.ensure(need_words)); ss->tables_clean_words = 0; }
+				if (ss->tables_clean_words < need_words) {
+					HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, ss->d_keys.cap * 8, st));      /* (scores of a free slot are never read) */
+					ss->tables_clean_words = ss->d_keys.cap;
+				}
+				RC_TRY(ss->d_ticket.ensure(16));
+				HIP_TRY(hipMemsetAsync(ss->d_ticket.p, 0, 4, st));
+				a.keys = ss->d_keys.p;
+				memcpy(h_work, hbm_now.data(), hbm_now.size() * 4);
+				HIP_TRY(hipMemcpyAsync(ss->d_work.p, h_work, hbm_now.size() * 4, hipMemcpyHostToDevice, st));
+				a.n_work = (int32_t) hbm_now.size();
+				ss->tables_clean_words = 0;                     /* until the launch is known to have ended */
+				RC_TRY(ss->kmark(st));
+				HIP_TRY(launch_search_wave_hbm(a, (int) n_tables, ss->d_ticket.p, st));
+				RC_TRY(ss->kmark(st));
+			} else {
+			const size_t chunk = std::max<size_t>(1, std::min<size_t>(hbm_now.size(), ((size_t) 8 << 30) / (per_read * 16)));
+			ss->tables_clean_words = 0;                         /* the lane-per-read kernel leaves its tables as they are */
+			RC_TRY(ss->d_keys.ensure(chunk * per_read));
+			RC_TRY(ss->d_scores.ensure(chunk * per_read * 2));
+			a.keys = ss->d_keys.p; a.scores = ss->d_scores.p;
+			for (size_t w0 = 0; w0 < hbm_now.size(); w0 += chunk) {
+				const size_t m = std::min(chunk, hbm_now.size() - w0);
+				memcpy(h_work, hbm_now.data() + w0, m * 4);
+				HIP_TRY(hipMemcpyAsync(ss->d_work.p, h_work, m * 4, hipMemcpyHostToDevice, st));
+				HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, m * per_read * 8, st));          /* every slot empty */
+				a.n_work = (int32_t) m;
+				RC_TRY(ss->kmark(st));
+				HIP_TRY(launch_search(a, st));
+				RC_TRY(ss->kmark(st));
+				if (w0 + chunk < hbm_now.size()) RC_TRY(search_wait(ss, st));      /* (the work list is reused by the next chunk) */
+			}
+			}
+			HIP_TRY(hipMemcpyAsync(h_ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
+			RC_TRY(search_wait(ss, st));
+			if (!lane_serial) ss->tables_clean_words = ss->d_keys.cap;      /* the launch ended: every wave left its table empty */
+			for (int32_t i : hbm_now) if (h_ncand[i] < 0) next_hbm.push_back(i);
+			if (trace) { char b[160]; snprintf(b, sizeof(b), " [bits %d hbm %zu (%llu votes in the call) -> %zu retry, at %.2f ms]", bits, hbm_now.size(), (unsigned long long) total, next_hbm.size(), tr_ms()); tr += b; }
+		}
+		work_wave.swap(next_wave);
+		work_hbm.swap(next_hbm);
+	}
+	/* (a read that left the ladder without a list keeps -1; one still flagged for the HBM kernel cannot remain: it was redone in its attempt) */
+	/* dense candidate list in read order, compacted on the device: only the entries come back (the sparse arena is
+	 * two slots per vote) */
+	uint64_t need = 0;
+	for (int i = 0; i < n; ++i) { h_begin[i] = need; cand_begin[i] = need; n_candidates[i] = h_ncand[i]; if (h_ncand[i] > 0) need += (uint64_t) h_ncand[i]; }
+	if (cand_used) *cand_used = need;
+	if (max_hit || kmer_misses) {
+		HIP_TRY(hipMemcpyAsync(h_maxhit, ss->d_maxhit.p, n1 * 4, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(h_miss, ss->d_miss.p, n1 * 4, hipMemcpyDeviceToHost, st));
+	}
+	if (need > cand_capacity || (need > 0 && !cands)) {
+		if (max_hit || kmer_misses) RC_TRY(search_wait(ss, st));
+		set_err("cvx_search_batch: candidate arena too small (%llu needed, %llu given)", (unsigned long long) need, (unsigned long long) cand_capacity);
+		return CVX_ERR_CAPACITY;
+	}
+	if (need) {
+		RC_TRY(ss->d_dense.ensure((size_t) need + 64));
+		HIP_TRY(hipMemcpyAsync(ss->d_begin.p, h_begin, n1 * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(launch_search_compact(ss->d_cand.p, ss->d_srcoff.p, ss->d_ncand.p, ss->d_begin.p, ss->d_dense.p, n, st));
+		RC_TRY(ss->kmark(st));
+		/* (straight into the caller's memory: pageable unless it came from cvx_host_alloc, then the copy is staged by the runtime) */
+		HIP_TRY(hipMemcpyAsync(cands, ss->d_dense.p, (size_t) need * sizeof(SearchCandidate), hipMemcpyDeviceToHost, st));
+	}
+	RC_TRY(search_wait(ss, st));
+	for (size_t q = 0; q + 1 < ss->kev_used; q += 2) ss->kernel_ms += ev_ms(ss->kev[q], ss->kev[q + 1]);
+	if (trace) fprintf(stderr, "cvx_search_batch: %d reads, %llu bases, %llu candidates, %.2f ms:%s\n", n, (unsigned long long) bytes - (unsigned long long) n, (unsigned long long) need, tr_ms(), tr.c_str());
+	if (max_hit) memcpy(max_hit, h_maxhit, n1 * 4);
+	if (kmer_misses) memcpy(kmer_misses, h_miss, n1 * 4);
+	return CVX_OK;
+}
+
+extern "C" {
+
+int cvx_search_batch_ex(cvx_handle h, cvx_index ix, int32_t n, const char *const *seqs, const int32_t *lens,
+		float sensitivity, float min_hits, int32_t bin_shift, int32_t first_bits,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+		float *max_hit, int32_t *kmer_misses) {
+	ABI_GUARD_BEGIN return search_common(h, ix, n, seqs, lens, nullptr, nullptr, sensitivity, min_hits, bin_shift, first_bits, n_candidates, cand_begin, cands, cand_capacity, cand_used, max_hit, kmer_misses); ABI_GUARD_END
+}
+
+int cvx_search_batch_arena(cvx_handle h, cvx_index ix, int32_t n, const uint8_t *arena, const uint64_t *offsets,
+		float sensitivity, float min_hits, int32_t bin_shift, int32_t first_bits,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+		float *max_hit, int32_t *kmer_misses) {
+	ABI_GUARD_BEGIN
+	if (n > 0 && (!arena || !offsets)) { set_err("cvx_search_batch_arena: NULL arena"); return CVX_ERR_ARG; }
+	return search_common(h, ix, n, nullptr, nullptr, arena ? arena : reinterpret_cast<const uint8_t *>(""), offsets, sensitivity, min_hits, bin_shift, first_bits, n_candidates, cand_begin, cands, cand_capacity, cand_used, max_hit, kmer_misses);
+	ABI_GUARD_END
+}
+
+int cvx_search_last_attempts(cvx_handle h, int32_t n, int32_t *attempts) {
+	ABI_GUARD_BEGIN
+	if (!h || n < 0 || (n > 0 && !attempts)) { set_err("cvx_search_last_attempts: bad argument"); return CVX_ERR_ARG; }
+	if (!h->search || (size_t) n > h->search->attempts.size()) { set_err("cvx_search_last_attempts: the handle's last search had fewer than %d reads", n); return CVX_ERR_ARG; }
+	if (n) memcpy(attempts, h->search->attempts.data(), (size_t) n * sizeof(int32_t));
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_search_batch(cvx_handle h, cvx_index ix, int32_t n, const char *const *seqs, const int32_t *lens,
+		float sensitivity, float min_hits, int32_t bin_shift,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used) {
+	ABI_GUARD_BEGIN return cvx_search_batch_ex(h, ix, n, seqs, lens, sensitivity, min_hits, bin_shift, 0, n_candidates, cand_begin, cands, cand_capacity, cand_used, nullptr, nullptr); ABI_GUARD_END
+}
+
+}  /* extern "C" */

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "cvx_align.h"
+#include "cvx_rt_err.h"
 
 namespace cvx { void pack_pool_run(int n_tasks, const std::function<void(int)> &fn); }
 
@@ -195,6 +196,7 @@ void reverse_in_place(char *q, int n) {
 }  // namespace
 
 extern "C" int cvx_sam_record_text(cvx_sam_record *r, char *out, uint64_t cap, uint64_t *len) {
+	ABI_GUARD_BEGIN
 	if (!r || !len || (cap > 0 && !out) || !r->read_name || !r->seq || !r->cigar || !r->md || !r->mate_ref_name ||
 			(r->ref_name_len > 0 && !r->ref_name) || r->read_length <= 0 || (r->n_others > 0 && !r->others)) return CVX_ERR_ARG;
 	/* the reference reverses first and prints afterwards; a call that does not fit must not leave the buffer reversed
@@ -205,17 +207,21 @@ extern "C" int cvx_sam_record_text(cvx_sam_record *r, char *out, uint64_t cap, u
 	if (o.n > cap) return CVX_ERR_CAPACITY;
 	if (reverses_qual(*r)) reverse_in_place(r->qual, r->read_length);
 	return CVX_OK;
+	ABI_GUARD_END
 }
 
 extern "C" int cvx_sam_unmapped_text(const cvx_sam_unmapped *r, char *out, uint64_t cap, uint64_t *len) {
+	ABI_GUARD_BEGIN
 	if (!r || !len || (cap > 0 && !out) || !r->read_name || !r->seq || r->read_length < 0) return CVX_ERR_ARG;
 	Out o{out, cap, 0};
 	unmapped(*r, o);
 	*len = o.n;
 	return o.n > cap ? CVX_ERR_CAPACITY : CVX_OK;
+	ABI_GUARD_END
 }
 
 extern "C" int cvx_sam_batch(int32_t n, cvx_sam_record *recs, char *out, uint64_t cap, uint64_t *offsets) {
+	ABI_GUARD_BEGIN
 	if (n < 0 || (n > 0 && (!recs || !offsets)) || (cap > 0 && !out)) return CVX_ERR_ARG;
 	if (n == 0) { if (offsets) offsets[0] = 0; return CVX_OK; }
 	for (int i = 0; i < n; ++i) {
@@ -260,4 +266,5 @@ extern "C" int cvx_sam_batch(int32_t n, cvx_sam_record *recs, char *out, uint64_
 		for (int i = 0; i < n; ++i) if (recs[i].qual == kv.first) { reverse_in_place(recs[i].qual, recs[i].read_length); break; }
 	}
 	return CVX_OK;
+	ABI_GUARD_END
 }

@@ -105,7 +105,7 @@ def test_corridorline_stride_is_accepted(hip_aligner, port_oracle):
 def test_more_ops_than_the_dense_arena_was_sized_for(built):
     """The dense ops arena is sized for a third of H + W per tile; with a mild mismatch penalty an alignment
     can alternate match / mismatch base by base (one op per base).  The batch summary then reports the
-    overflow and the ops are compacted again into a larger arena (cvx_runtime.cpp stage_ops) -- same results."""
+    overflow and the ops are compacted again into a larger arena (cvx_rt_align.cpp stage_ops) -- same results."""
     from ngmlr_amd import synth
     from ngmlr_amd.aligner import ConvexAlignHip
     from oracle.pyoracle import Oracle, same_alignment
