@@ -32,6 +32,8 @@
  * cvx_format_alignment        convertCigar + N-clip flags    src/ConvexAlignFast.cpp:112-333,493-528
  * cvx_job_text                the same for a whole finished job, on the device (next-row f3)
  * cvx_job_nm_profile          addPosition / nmPerPosition    src/ConvexAlignFast.cpp:76-98,186-269, on the device
+ * cvx_job_nm_regions / cvx_nm_regions_ops / cvx_nm_regions_host  the peak finder over that profile at the top of
+ *                             detectMisalignment  src/AlignmentBuffer.cpp:1143-1148,1316-1395 (device: no profile leaves HBM)
  * cvx_sam_record_text / cvx_sam_batch  SAMWriter::DoWriteReadGeneric  src/SAMWriter.cpp:87-224 (f3: SAM record assembly)
  * cvx_sam_unmapped_text       SAMWriter::DoWriteUnmappedReadGeneric  src/SAMWriter.cpp:308-357
  * cvx_score_batch             StrippedSW::BatchScore/SingleScore  src/StrippedSW.cpp:118-203 (next-row f2)
@@ -565,6 +567,47 @@ int cvx_job_nm_sizes(cvx_handle h, cvx_job job, int32_t first, int32_t count, ui
  * triples == NULL: sizes only. */
 int cvx_nm_profile_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
 		uint64_t *entry_off, int32_t *triples, uint64_t cap_entries);
+
+/* The low-identity regions of that profile (ABI 9, additive): what the peak finder at the top of detectMisalignment
+ * (reference src/AlignmentBuffer.cpp:1316-1395, isInversion :1143-1148) reduces nmPerPosition to, and all that
+ * checkForSV is called with.  The finder walks alignmentLength rows -- the profile's entries, then zeros -- and marks a
+ * row iff 0 < (32 - nm) / 32.0f < 0.75, which for an integer nm is 9 <= nm <= 31.  A region starts at the first marked row
+ * and at every marked row with 21 or more unmarked rows in front of it, ends at the last marked row in front of such a
+ * break, and is emitted when the 21st unmarked row behind it is reached; a run that is still open when the rows end is
+ * dropped.  A region is the refPosition / readPosition of its first and its last marked row. */
+typedef struct {
+	int32_t ref_start, ref_stop;      /* startInv, stopInv */
+	int32_t read_start, read_stop;    /* startInvRead, stopInvRead */
+} cvx_nm_region;
+/* The state the finder's loop ends in.  open = 0: no run is open, distance = 20, r = -1s.  open = 1: r is the run that was
+ * dropped and distance the reference's countdown (20 - the unmarked rows seen behind r's last mark; 0 = the next unmarked
+ * row emits r).  A caller whose rows past the entries are not zeros finishes the scan from here. */
+typedef struct {
+	int32_t open, distance;
+	cvx_nm_region r;
+} cvx_nm_open;
+
+/* The regions of the tiles [first, first + count) of a finished job, found on the device from the resident ops: no profile
+ * is written or copied anywhere, so the range may be the whole job (16 bytes per region instead of 12 per alignment
+ * column).  Needs what cvx_job_nm_profile needs -- after cvx_job_text, before cvx_job_release, one text-stage call on a
+ * handle at a time -- and answers the same misuse the same way (CVX_ERR_ARG before the text stage and for a range past the
+ * job).  region_off[count + 1]: tile first + i owns (*regions)[region_off[i] .. region_off[i + 1]); a tile without a
+ * valid alignment owns none.  *regions points at page-locked memory owned by the job, valid until the next call of this
+ * entry on the job or cvx_job_release.  open (may be NULL): count records, the end state of every tile's scan.
+ * *kernel_ms (may be NULL): the kernels' own duration (both passes and the offset scan). */
+int cvx_job_nm_regions(cvx_handle h, cvx_job job, int32_t first, int32_t count, uint64_t *region_off,
+		const cvx_nm_region **regions, cvx_nm_open *open, double *kernel_ms);
+/* The same kernel over op lists the caller holds (the twin of cvx_nm_profile_ops).  regions: room for cap_regions
+ * (CVX_ERR_CAPACITY, with region_off and open filled in, when that is too little) -- or NULL: sizes (and open) only.
+ * CVX_ERR_ARG for ops outside the arena. */
+int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
+		uint64_t *region_off, cvx_nm_region *regions, uint64_t cap_regions, cvx_nm_open *open);
+/* The finder on the host, over a profile the caller holds (the host text stage's, cvx_format_alignment): n_entries
+ * triples (refPosition, readPosition, nm) followed by zero rows up to scan_len = alignmentLength (rows past scan_len are
+ * not looked at).  Pure host code, no device needed.  *n_regions = the regions found; the first min(cap, *n_regions) are
+ * written, CVX_ERR_CAPACITY when cap is smaller -- or regions == NULL (cap 0): the count and open only.  open may be NULL. */
+int cvx_nm_regions_host(const int32_t *triples, int64_t n_entries, int64_t scan_len, cvx_nm_region *regions, int64_t cap,
+		int64_t *n_regions, cvx_nm_open *open);
 
 /* ---- SAM record assembly (reference src/SAMWriter.cpp:87-224, :308-357) ----
  *

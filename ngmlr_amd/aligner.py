@@ -132,6 +132,23 @@ class ConvexAlignHip:
         capi.check(self.lib.cvx_submit(self.h, n, arr, C.byref(j)))
         return Job(self, j, n, keep)
 
+    def nm_regions_ops(self, results, ops_arena, want_regions: bool = True):
+        """cvx_nm_regions_ops: the low-identity regions of op lists the caller holds (a capi.CvxResult array or sequence, and
+        the uint32 ops arena its ops_begin / n_ops point into), found on the device.
+        -> (offsets uint64[n + 1], regions int32[r, 4] or None when want_regions is False, open records NM_OPEN_DTYPE[n])"""
+        n = len(results)
+        res = results if isinstance(results, C.Array) else (capi.CvxResult * max(n, 1))(*results)
+        arena = np.ascontiguousarray(ops_arena, dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        opn = np.zeros(n, dtype=NM_OPEN_DTYPE)
+        lib = self.lib
+        capi.check(lib.cvx_nm_regions_ops(self.h, n, res, arena.ctypes.data, len(arena), off.ctypes.data, None, 0, opn.ctypes.data))
+        if not want_regions:
+            return off, None, opn
+        reg = np.zeros((int(off[n]), 4), dtype=np.int32)
+        capi.check(lib.cvx_nm_regions_ops(self.h, n, res, arena.ctypes.data, len(arena), off.ctypes.data, reg.ctypes.data, len(reg), opn.ctypes.data))
+        return off, reg, opn
+
     # ------------------------------------------------------------------ reference-shaped API
     def batch_align(self, tiles: Sequence, want_nm: bool = True, closed_form: bool = False) -> List[dict]:
         """N x SingleAlign: returns one Align-like dict per tile (keys = the Align fields)."""
@@ -150,6 +167,24 @@ RESULT_DTYPE = np.dtype([("score", np.float32), ("status", np.int32), ("best_ref
                          ("best_read_index", np.int32), ("ref_position", np.int32), ("qstart", np.int32),
                          ("qend", np.int32), ("n_ops", np.int32), ("ops_begin", np.uint64), ("cells", np.uint64)])
 assert RESULT_DTYPE.itemsize == C.sizeof(capi.CvxResult)
+# cvx_nm_open: the state detectMisalignment's peak finder ends in; a region is (ref_start, ref_stop, read_start, read_stop)
+NM_OPEN_DTYPE = np.dtype([("open", np.int32), ("distance", np.int32), ("region", np.int32, (4,))])
+assert NM_OPEN_DTYPE.itemsize == C.sizeof(capi.CvxNmOpen)
+
+
+def nm_regions_host(triples, scan_len: int, lib=None):
+    """cvx_nm_regions_host: the peak finder at the top of detectMisalignment over a profile on the host (no device).
+    triples: int32[entries, 3] (refPosition, readPosition, nm); scan_len: alignmentLength (rows past the entries are zeros).
+    -> (regions int32[r, 4], open record NM_OPEN_DTYPE scalar)"""
+    lib = lib or capi.load()
+    tri = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+    n = C.c_int64()
+    opn = np.zeros(1, dtype=NM_OPEN_DTYPE)
+    capi.check(lib.cvx_nm_regions_host(tri.ctypes.data, len(tri), int(scan_len), None, 0, C.byref(n), opn.ctypes.data))
+    reg = np.zeros((int(n.value), 4), dtype=np.int32)
+    if n.value:
+        capi.check(lib.cvx_nm_regions_host(tri.ctypes.data, len(tri), int(scan_len), reg.ctypes.data, len(reg), C.byref(n), opn.ctypes.data))
+    return reg, opn[0]
 
 
 class Job:
@@ -280,6 +315,21 @@ class Job:
         n = int(off[count])
         tri = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), shape=(n * 3,)).reshape(n, 3).copy() if n else np.zeros((0, 3), dtype=np.int32)
         return off, tri, ms.value
+
+    def nm_regions(self, first: int = 0, count: Optional[int] = None):
+        """cvx_job_nm_regions (after text()/text_raw()): the low-identity regions of the NM profile of the tiles
+        [first, first + count) -- by default the whole job -- found on the device; no profile is written or copied.
+        -> (offsets uint64[count + 1], regions int32[r, 4] = (ref_start, ref_stop, read_start, read_stop), open records
+        NM_OPEN_DTYPE[count], kernel ms)"""
+        count = self.n - first if count is None else count
+        off = np.zeros(count + 1, dtype=np.uint64)
+        opn = np.zeros(max(count, 0), dtype=NM_OPEN_DTYPE)
+        ms = C.c_double()
+        ptr = C.c_void_p()
+        capi.check(self.al.lib.cvx_job_nm_regions(self.al.h, self.j, first, count, off.ctypes.data, C.byref(ptr), opn.ctypes.data, C.byref(ms)))
+        n = int(off[count]) if count > 0 else 0
+        reg = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), dtype=np.int32)
+        return off, reg, opn, ms.value
 
     def release(self) -> None:
         if self.j:

@@ -28,6 +28,7 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_genome_decode", "cvx_submit_windows", "cvx_job_text",
            "cvx_host_alloc", "cvx_host_free", "cvx_corridor_rows", "cvx_pack_probe", "cvx_build_id", "cvx_job_poll", "cvx_score_kernel_ms",
            "cvx_index_upload", "cvx_index_free", "cvx_search_batch", "cvx_search_batch_ex", "cvx_job_nm_profile", "cvx_job_nm_profile_resident", "cvx_job_text_all", "cvx_job_window_refs", "cvx_job_nm_sizes", "cvx_nm_profile_ops",
+           "cvx_job_nm_regions", "cvx_nm_regions_ops", "cvx_nm_regions_host",
            "cvx_sam_record_text", "cvx_sam_unmapped_text", "cvx_sam_batch", "cvx_stage_kernel_ms", "cvx_search_last_attempts", "cvx_index_build", "cvx_index_build_device",
            "cvx_corridor_fit", "cvx_corridor_fit_batch", "cvx_create_ex", "cvx_runtime_regime", "cvx_search_batch_arena",
            "cvx_score_submit", "cvx_score_poll", "cvx_score_wait")
@@ -83,6 +84,14 @@ class CvxAlignmentText(C.Structure):
                 ("first_ref", C.c_int32), ("first_read", C.c_int32), ("last_ref", C.c_int32),
                 ("last_read", C.c_int32), ("nm_count", C.c_int32), ("cigar_len", C.c_int32),
                 ("md_len", C.c_int32)]
+
+
+class CvxNmRegion(C.Structure):
+    _fields_ = [("ref_start", C.c_int32), ("ref_stop", C.c_int32), ("read_start", C.c_int32), ("read_stop", C.c_int32)]
+
+
+class CvxNmOpen(C.Structure):
+    _fields_ = [("open", C.c_int32), ("distance", C.c_int32), ("r", CvxNmRegion)]
 
 
 class CvxSamOther(C.Structure):
@@ -182,6 +191,9 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_job_text_all.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CvxAlignmentText), C.c_void_p,
                                      C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_void_p)]
     lib.cvx_nm_profile_ops.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.cvx_job_nm_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(C.c_double)]
+    lib.cvx_nm_regions_ops.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.cvx_nm_regions_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
     lib.cvx_sam_record_text.argtypes = [C.POINTER(CvxSamRecord), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.cvx_sam_unmapped_text.argtypes = [C.POINTER(CvxSamUnmapped), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.cvx_sam_batch.argtypes = [C.c_int32, C.POINTER(CvxSamRecord), C.c_void_p, C.c_uint64, C.c_void_p]

@@ -260,3 +260,49 @@ extern "C" int cvx_format_batch(int32_t n, const cvx_result *results, const uint
 	return err.load();
 	ABI_GUARD_END
 }
+
+/* ---- the peak finder at the top of detectMisalignment (src/AlignmentBuffer.cpp:1316-1395) over a profile on the host ----
+ *
+ * The reference walks scan_len rows with the state (startInv, stopInv, distance).  Its outcome as a rule over the marked rows
+ * i0 < i1 < ... (9 <= nm <= 31, isInversion :1143-1148): a region starts at i0 and at every mark with i_k - i_(k-1) >= 22, ends
+ * at the mark in front of such a break, and the last one is emitted iff 21 or more rows follow its last mark.  The rows past
+ * the entries are zeros, so no mark lies there. */
+extern "C" int cvx_nm_regions_host(const int32_t *triples, int64_t n_entries, int64_t scan_len, cvx_nm_region *regions, int64_t cap,
+		int64_t *n_regions, cvx_nm_open *open) {
+	ABI_GUARD_BEGIN
+	if (n_entries < 0 || scan_len < 0 || cap < 0 || !n_regions || (n_entries > 0 && !triples) || (cap > 0 && !regions)) {
+		cvx::set_err("cvx_nm_regions_host: bad argument");
+		return CVX_ERR_ARG;
+	}
+	const int max_distance = 20;                         /* maxDistance, :1290 */
+	const int64_t rows = n_entries < scan_len ? n_entries : scan_len;
+	int64_t found = 0, last = -1;
+	cvx_nm_region cur = {-1, -1, -1, -1};
+	for (int64_t i = 0; i < rows; ++i) {
+		const int32_t *t = triples + 3 * i;
+		if (t[2] < 9 || t[2] > 31) continue;
+		if (last >= 0 && i - last > max_distance + 1) {  /* 21 or more unmarked rows: the run in front is complete */
+			if (found < cap) regions[found] = cur;
+			++found;
+			last = -1;
+		}
+		if (last < 0) { cur.ref_start = t[0]; cur.read_start = t[1]; }
+		cur.ref_stop = t[0]; cur.read_stop = t[1];
+		last = i;
+	}
+	cvx_nm_open end = {0, max_distance, {-1, -1, -1, -1}};
+	if (last >= 0) {
+		const int64_t behind = scan_len - 1 - last;
+		if (behind > max_distance) {
+			if (found < cap) regions[found] = cur;
+			++found;
+		} else {
+			end.open = 1; end.distance = (int32_t) (max_distance - behind); end.r = cur;
+		}
+	}
+	if (open) *open = end;
+	*n_regions = found;
+	if (regions && found > cap) { cvx::set_err("cvx_nm_regions_host: %lld regions, room for %lld", (long long) found, (long long) cap); return CVX_ERR_CAPACITY; }
+	return CVX_OK;
+	ABI_GUARD_END
+}

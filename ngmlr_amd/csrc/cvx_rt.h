@@ -17,6 +17,7 @@
 #include "cvx_align.h"
 #include "cvx_host_logic.h"
 #include "cvx_launch.h"
+#include "cvx_nm_regions.h"
 #include "cvx_rt_err.h"
 #include "cvx_types.h"
 
@@ -214,6 +215,12 @@ struct cvx_batch_s {
 	PinBuf h_nmoff;
 	PinBuf h_nm;                     /* the triples on the host (cvx_job_nm_profile_resident) */
 	hipEvent_t ev_nm0 = nullptr, ev_nm1 = nullptr;
+	DevBuf<unsigned long long> d_nmroff; /* the profile's low-identity regions (cvx_job_nm_regions): counts, offsets, total of the tile range */
+	DevBuf<NmOpen> d_nmopen;         /* ... the state every tile's scan ends in */
+	DevBuf<NmRegion> d_nmstage;      /* ... kNmStage regions per tile as the first pass found them */
+	DevBuf<NmRegion> d_nmreg;        /* ... and the regions, dense */
+	PinBuf h_nmroff, h_nmopen;
+	PinBuf h_nmreg;                  /* the regions on the host: what cvx_job_nm_regions hands out */
 	PinBuf h_win;                    /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
 	PinBuf h_refs;                   /* ... and the decoded windows back on the host (cvx_job_window_refs): the reference part of d_seq */
 	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
@@ -276,6 +283,7 @@ struct cvx_batch_s {
 		h_ext.release(); h_trec.release(); h_toff.release(); h_text.release();
 		d_ext.release(); d_trec.release(); d_tlen.release(); d_text.release();
 		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
+		d_nmroff.release(); d_nmopen.release(); d_nmstage.release(); d_nmreg.release(); h_nmroff.release(); h_nmopen.release(); h_nmreg.release();
 		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
 		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
 		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();

@@ -1,7 +1,8 @@
 /*
  * cvx_rt_text.cpp -- the device-side text stage of finished alignment jobs over the kernels of cvx_text.hip, on
  * the handle's `text` stream: the CIGAR / MD strings and records (cvx_job_text, cvx_job_text_all), the per-position NM profile
- * of a job (cvx_job_nm_*) and of results the caller holds (cvx_nm_profile_ops).
+ * of a job (cvx_job_nm_*) and of results the caller holds (cvx_nm_profile_ops), and that profile's low-identity regions found
+ * on the device (cvx_job_nm_regions, cvx_nm_regions_ops).
  */
 #include <cstring>
 #include <vector>
@@ -262,6 +263,131 @@ int cvx_nm_profile_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 	};
 	rc = body();
 	d_ops.release(); d_tri.release(); d_tout.release(); d_trun.release(); d_off.release();
+	return rc;
+	ABI_GUARD_END
+}
+
+/* ---- the profile's low-identity regions (nm_regions_kernel): the peak finder of detectMisalignment, src/AlignmentBuffer.cpp:1316-1395 */
+
+int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, uint64_t *region_off,
+		const cvx_nm_region **regions, cvx_nm_open *open, double *kernel_ms) {
+	ABI_GUARD_BEGIN
+	static_assert(sizeof(NmRegion) == sizeof(cvx_nm_region) && sizeof(NmOpen) == sizeof(cvx_nm_open), "NmRegion / NmOpen mirror cvx_nm_region / cvx_nm_open");
+	if (kernel_ms) *kernel_ms = 0.0;
+	if (regions) *regions = nullptr;
+	if (!h || !j || j->state < kFinished) { set_err("cvx_job_nm_regions: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (!j->text_done) { set_err("cvx_job_nm_regions: call cvx_job_text first"); return CVX_ERR_ARG; }
+	if (first < 0 || count < 0 || (int64_t) first + count > j->n || (count > 0 && (!region_off || !regions))) { set_err("cvx_job_nm_regions: bad tile range / NULL output"); return CVX_ERR_ARG; }
+	if (count == 0) return CVX_OK;
+	HIP_TRY(hipSetDevice(h->device));
+	hipStream_t st = h->s_text;
+	const size_t c1 = (size_t) count;
+	RC_TRY(j->d_nmroff.ensure(2 * c1 + 8));
+	RC_TRY(j->d_nmopen.ensure(c1));
+	RC_TRY(j->d_nmstage.ensure(c1 * (size_t) kNmStage));
+	RC_TRY(j->h_nmroff.ensure((c1 + 1) * sizeof(unsigned long long)));
+	if (open) RC_TRY(j->h_nmopen.ensure(c1 * sizeof(NmOpen)));
+	if (!j->ev_nm0) HIP_TRY(hipEventCreate(&j->ev_nm0));
+	if (!j->ev_nm1) HIP_TRY(hipEventCreate(&j->ev_nm1));
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
+	a.n_tiles = j->n;
+	/* pass 1: the regions per tile, their offsets (the total right behind them), the end states */
+	unsigned long long *d_len = j->d_nmroff.p, *d_off = j->d_nmroff.p + c1;
+	HIP_TRY(hipEventRecord(j->ev_nm0, st));
+	HIP_TRY(launch_nm_regions_count(a, first, count, d_len, d_off, d_off + c1, j->d_nmopen.p, j->d_nmstage.p, st));
+	HIP_TRY(hipEventRecord(j->ev_nm1, st));
+	unsigned long long *hoff = j->h_nmroff.as<unsigned long long>();
+	HIP_TRY(hipMemcpyAsync(hoff, d_off, (c1 + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	if (open) HIP_TRY(hipMemcpyAsync(j->h_nmopen.p, j->d_nmopen.p, c1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	float ms1 = 0.0f, ms2 = 0.0f;
+	HIP_TRY(hipEventElapsedTime(&ms1, j->ev_nm0, j->ev_nm1));
+	const unsigned long long total = hoff[c1];
+	/* pass 2: the regions, dense and in tile order */
+	RC_TRY(j->d_nmreg.ensure((size_t) total + 4));
+	RC_TRY(j->h_nmreg.ensure(((size_t) total + 4) * sizeof(NmRegion)));
+	if (total > 0) {
+		HIP_TRY(hipEventRecord(j->ev_nm0, st));
+		HIP_TRY(launch_nm_regions_write(a, first, count, d_len, d_off, j->d_nmstage.p, j->d_nmreg.p, st));
+		HIP_TRY(hipEventRecord(j->ev_nm1, st));
+		HIP_TRY(hipMemcpyAsync(j->h_nmreg.p, j->d_nmreg.p, (size_t) total * sizeof(NmRegion), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		HIP_TRY(hipEventElapsedTime(&ms2, j->ev_nm0, j->ev_nm1));
+	}
+	for (size_t i = 0; i <= c1; ++i) region_off[i] = hoff[i];
+	if (open) memcpy(open, j->h_nmopen.p, c1 * sizeof(NmOpen));
+	*regions = j->h_nmreg.as<cvx_nm_region>();
+	if (kernel_ms) *kernel_ms = (double) ms1 + (double) ms2;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
+		uint64_t *region_off, cvx_nm_region *regions, uint64_t cap_regions, cvx_nm_open *open) {
+	ABI_GUARD_BEGIN
+	if (!h || n < 0 || (n > 0 && (!results || !region_off)) || (ops_total > 0 && !ops_arena)) { set_err("cvx_nm_regions_ops: bad argument"); return CVX_ERR_ARG; }
+	if (n == 0) return CVX_OK;
+	HIP_TRY(hipSetDevice(h->device));
+	RC_TRY(ensure_streams(h));
+	const size_t n1 = (size_t) n;
+	std::vector<TileOut> tout(n1);
+	std::vector<TileRun> trun(n1);
+	for (size_t i = 0; i < n1; ++i) {
+		const cvx_result &r = results[i];
+		memset(&tout[i], 0, sizeof(TileOut));
+		memset(&trun[i], 0, sizeof(TileRun));
+		tout[i].status = r.status;
+		tout[i].qstart = r.qstart;
+		if (r.status != CVX_TILE_OK) continue;
+		if (r.n_ops < 0 || r.ops_begin + (uint64_t) r.n_ops > ops_total) { set_err("cvx_nm_regions_ops: ops of tile %zu outside the arena", i); return CVX_ERR_ARG; }
+		tout[i].n_ops = r.n_ops;
+		trun[i].ops_off = r.ops_begin;
+		for (int k = 0; k < r.n_ops; ++k) {
+			const int type = (int) (ops_arena[r.ops_begin + (uint64_t) k] & 15u);
+			if (type != CVX_OP_EQ && type != CVX_OP_X && type != CVX_OP_D && type != CVX_OP_I) { set_err("cvx_nm_regions_ops: op code %d in tile %zu", type, i); return CVX_ERR_ARG; }
+		}
+	}
+	DevBuf<int32_t> d_ops;
+	DevBuf<TileOut> d_tout;
+	DevBuf<TileRun> d_trun;
+	DevBuf<unsigned long long> d_off;
+	DevBuf<NmOpen> d_open;
+	DevBuf<NmRegion> d_stage, d_reg;
+	std::vector<unsigned long long> off(n1 + 1, 0ull);
+	auto body = [&]() -> int {
+		RC_TRY(d_ops.ensure((size_t) ops_total + 16));
+		RC_TRY(d_tout.ensure(n1));
+		RC_TRY(d_trun.ensure(n1));
+		RC_TRY(d_off.ensure(2 * n1 + 8));
+		RC_TRY(d_open.ensure(n1));
+		RC_TRY(d_stage.ensure(n1 * (size_t) kNmStage));
+		hipStream_t st = h->s_text;
+		if (ops_total) HIP_TRY(hipMemcpyAsync(d_ops.p, ops_arena, (size_t) ops_total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_tout.p, tout.data(), n1 * sizeof(TileOut), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(d_trun.p, trun.data(), n1 * sizeof(TileRun), hipMemcpyHostToDevice, st));
+		TextArgs a;
+		memset(&a, 0, sizeof(a));
+		a.tout = d_tout.p; a.trun = d_trun.p; a.ops = d_ops.p; a.n_tiles = n;
+		unsigned long long *d_len = d_off.p, *d_o = d_off.p + n1;
+		HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_o, d_o + n1, d_open.p, d_stage.p, st));
+		HIP_TRY(hipMemcpyAsync(off.data(), d_o, (n1 + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+		if (open) HIP_TRY(hipMemcpyAsync(open, d_open.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		for (size_t i = 0; i <= n1; ++i) region_off[i] = off[i];
+		const unsigned long long total = off[n1];
+		if (!regions) return CVX_OK;                      /* sizes only */
+		if (total > cap_regions) { set_err("cvx_nm_regions_ops: %llu regions, room for %llu", total, (unsigned long long) cap_regions); return CVX_ERR_CAPACITY; }
+		if (total == 0) return CVX_OK;
+		RC_TRY(d_reg.ensure((size_t) total + 4));
+		HIP_TRY(launch_nm_regions_write(a, 0, n, d_len, d_o, d_stage.p, d_reg.p, st));
+		HIP_TRY(hipMemcpyAsync(regions, d_reg.p, (size_t) total * sizeof(NmRegion), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		return CVX_OK;
+	};
+	const int rc = body();
+	d_ops.release(); d_tout.release(); d_trun.release(); d_off.release(); d_open.release(); d_stage.release(); d_reg.release();
 	return rc;
 	ABI_GUARD_END
 }

@@ -25,6 +25,7 @@
 
 #include "cvx_types.h"
 #include "cvx_launch.h"
+#include "cvx_nm_regions.h"
 
 namespace cvx {
 
@@ -398,6 +399,197 @@ text_scan_kernel(const unsigned long long *len, unsigned long long *off, unsigne
 	unsigned long long at = s_part[tid] - mine;
 	for (int t = t0; t < t1; ++t) { off[t] = at; at += len[t]; }
 	if (tid == T - 1) *total = s_part[T - 1];
+}
+
+/* ------------------------------------------------------------------ the profile's low-identity regions
+ *
+ * The peak finder at the top of detectMisalignment (src/AlignmentBuffer.cpp:1316-1395) walks alignmentLength rows of
+ * nmPerPosition -- the entries, then zeros -- and marks a row iff 9 <= nm <= 31 (isInversion, :1143-1148).  A region starts at
+ * the first mark and at every mark with 21 or more unmarked rows in front of it, ends at the last mark in front of such a
+ * break, and is emitted only once the 21st unmarked row behind it has been seen: a run that the end of the scan finds open is
+ * dropped.  As a rule over the entry ordinals that needs no state travelling along the alignment.
+ *
+ * Same walk as nm_tile, one op per lane, nothing stored per column.  The marks of ONE op are consecutive entries: along an
+ * EQ op bits only leave the 32-column register (Yi never rises), along an X op one enters per column and at most one leaves
+ * (Yi never falls), the entries of a D op share one Yi.  A lane therefore holds at most one run of marks (first and last
+ * column) and stops walking once Yi has left the band for good -- at most 32 columns past the skipped head.  The last mark in
+ * front of a lane comes from the nearest lower lane that has one (ballot) or from the previous 64-op step (uniform); a lane
+ * whose first mark is a head writes its region's start and the stop of the region before it, at the ordinal a wave scan over
+ * the heads gives it.
+ *
+ * Two launches with the offset scan between them, one walk for nearly every tile: the first counts and keeps a tile's first
+ * kNmStage regions in a slot of its own, the second copies them to the tile's offset and walks again only the tiles that
+ * found more.
+ */
+struct NmScanEnd {         /* what a tile's scan ends in (wave-uniform) */
+	int heads;             /* regions started */
+	bool has;              /* any mark at all */
+	int last_e, last_ref, last_read;      /* the last mark: entry ordinal, positions */
+	int head_ref, head_read;              /* the start of the last region */
+	int scan_len;          /* alignmentLength: every column of every op */
+};
+
+/* reg[0, cap): where the tile's regions go (the regions past cap are counted, not written) */
+TXT_DEV NmScanEnd nm_regions_tile(const int lane, const TileOut o, const int32_t *ops, const int cap, NmRegion *reg) {
+	const int n = o.n_ops;
+	int ref_base = 0, read_base = 0, col_base = 0, ent_base = 0;
+	NmScanEnd s;
+	s.heads = 0; s.has = false; s.last_e = 0; s.last_ref = -1; s.last_read = -1; s.head_ref = -1; s.head_read = -1;
+	for (int c0 = 0; c0 < n; c0 += 64) {
+		const int k = c0 + lane;
+		const bool valid = k < n;
+		const unsigned w = valid ? (unsigned) ops[k] : 0u;
+		const int len = (int) (w >> 4), type = (int) (w & 15u);
+		const bool isEQ = valid && type == 7, isX = valid && type == 8, isI = valid && type == 1, isD = valid && type == 2;
+		const bool refc = isEQ || isX || isD, readc = isEQ || isX || isI;
+		const int RC = wave_scan(refc ? len : 0, lane), RD = wave_scan(readc ? len : 0, lane), CS = wave_scan(valid ? len : 0, lane);
+		const int pr0 = ref_base + RC - (refc ? len : 0);
+		const int pq0 = o.qstart + read_base + RD - (readc ? len : 0);
+		const int cs = col_base + CS - (valid ? len : 0);
+		int cnt = 0, skip = 0;
+		if (isEQ || isX) {
+			const int mn = pr0 < pq0 ? pr0 : pq0;
+			skip = 17 - mn > 0 ? 17 - mn : 0;
+			cnt = len - skip > 0 ? len - skip : 0;
+		} else if (isD && pq0 > 16) {
+			skip = 17 - pr0 > 0 ? 17 - pr0 : 0;
+			cnt = len - skip > 0 ? len - skip : 0;
+		}
+		const int EN = wave_scan(cnt, lane);
+		const int e0 = ent_base + EN - cnt - skip;           /* entry ordinal of this op's column i = e0 + i */
+		int fi = -1, li = -1;                                /* first / last marked column of this op */
+		if (cnt > 0) {
+			OpCursor cur;
+			if (isD) {
+				int j = k - 1, g = 1, end = cs;
+				while (j >= 0) {
+					const unsigned wj = (unsigned) ops[j];
+					const int tj = (int) (wj & 15u);
+					if (tj != 1 && tj != 2) break;
+					end -= (int) (wj >> 4);
+					++g;
+					--j;
+				}
+				const int yi = (j >= 0 ? window_bits(ops, j, end, cur) : 0) + g;
+				if (yi >= kNmMarkLo && yi <= kNmMarkHi) { fi = skip; li = len - 1; }
+			} else {
+				int P = window_bits(ops, k - 1, cs, cur);
+				const int add = isX ? 1 : 0;
+				for (int i = 0; i < len; ++i) {
+					const int lc = cs + i - 32;
+					P += add;
+					if (lc >= 0) {
+						while (lc >= cur.start + cur.len) {
+							cur.start += cur.len;
+							cur.k += 1;
+							const unsigned wc = (unsigned) ops[cur.k];
+							cur.len = (int) (wc >> 4); cur.type = (int) (wc & 15u);
+						}
+						P -= (cur.type == 8 || ((cur.type == 1 || cur.type == 2) && lc == cur.start)) ? 1 : 0;
+					}
+					if (i >= skip && P >= kNmMarkLo && P <= kNmMarkHi) {
+						if (fi < 0) fi = i;
+						li = i;
+					}
+					if (isX ? P > kNmMarkHi : P < kNmMarkLo) break;      /* Yi has left the band for the rest of this op */
+				}
+			}
+		}
+		const bool has = fi >= 0;
+		const int f_e = e0 + fi, l_e = e0 + li;
+		const int f_ref = pr0 + fi - 16, l_ref = pr0 + li - 16;
+		const int f_read = pq0 - 16 + (isD ? 0 : fi), l_read = pq0 - 16 + (isD ? 0 : li);
+		/* the last mark in front of this lane */
+		const u64 hm = __builtin_amdgcn_ballot_w64(has);
+		const u64 below = hm & ((1ull << lane) - 1ull);
+		const int src = below ? 63 - __builtin_clzll(below) : 0;
+		int p_e = __shfl(l_e, src, 64), p_ref = __shfl(l_ref, src, 64), p_read = __shfl(l_read, src, 64);
+		bool p_has = below != 0ull;
+		if (!p_has) { p_has = s.has; p_e = s.last_e; p_ref = s.last_ref; p_read = s.last_read; }
+		const bool head = has && (!p_has || f_e - p_e > kNmMaxDistance + 1);
+		const int H = wave_scan(head ? 1 : 0, lane);
+		if (head) {
+			const int r = s.heads + H - 1;
+			if (r < cap) { reg[r].ref_start = f_ref; reg[r].read_start = f_read; }
+			if (r > 0 && r - 1 < cap) { reg[r - 1].ref_stop = p_ref; reg[r - 1].read_stop = p_read; }
+		}
+		const u64 hd = __builtin_amdgcn_ballot_w64(head);
+		if (hd) {
+			const int hl = 63 - __builtin_clzll(hd);
+			s.head_ref = __shfl(f_ref, hl, 64); s.head_read = __shfl(f_read, hl, 64);
+		}
+		if (hm) {
+			const int ll = 63 - __builtin_clzll(hm);
+			s.has = true;
+			s.last_e = __shfl(l_e, ll, 64); s.last_ref = __shfl(l_ref, ll, 64); s.last_read = __shfl(l_read, ll, 64);
+		}
+		s.heads += __builtin_amdgcn_readlane(H, 63);
+		ent_base += __builtin_amdgcn_readlane(EN, 63);
+		ref_base += __builtin_amdgcn_readlane(RC, 63);
+		read_base += __builtin_amdgcn_readlane(RD, 63);
+		col_base += __builtin_amdgcn_readlane(CS, 63);
+	}
+	s.scan_len = col_base;
+	return s;
+}
+
+/* FIRST: len[i] = closed regions of tile first + i, open[i] = the state its scan ends in, the first kNmStage regions in
+ * stage[i * kNmStage ...] (a run that stays open may sit behind them: a slot of the tile's own, never copied).  !FIRST: the
+ * regions at regions + off[i], from the stage, or by a second walk for a tile with more than kNmStage. */
+template <bool FIRST>
+__global__ void __launch_bounds__(64)
+nm_regions_kernel(const TextArgs a, const int first, unsigned long long *len, const unsigned long long *off, NmOpen *open,
+		NmRegion *stage, NmRegion *regions) {
+	const int b = (int) blockIdx.x, t = first + b;
+	const int lane = (int) threadIdx.x;
+	NmRegion *slot = stage + (size_t) b * kNmStage;
+	if (!FIRST) {
+		const int n_closed = (int) len[b];
+		NmRegion *dst = regions + off[b];
+		if (n_closed <= kNmStage) {
+			if (lane < n_closed) dst[lane] = slot[lane];
+			return;
+		}
+		const TileOut o = a.tout[t];
+		const NmScanEnd s = nm_regions_tile(lane, o, a.ops + a.trun[t].ops_off + o.ops_first, n_closed, dst);
+		if (lane == 0 && s.heads == n_closed) { dst[n_closed - 1].ref_stop = s.last_ref; dst[n_closed - 1].read_stop = s.last_read; }
+		return;
+	}
+	const TileOut o = a.tout[t];
+	NmOpen st;
+	st.open = 0; st.distance = kNmMaxDistance; st.r.ref_start = st.r.ref_stop = st.r.read_start = st.r.read_stop = -1;
+	int n_closed = 0;
+	if (o.status == 0) {
+		const NmScanEnd s = nm_regions_tile(lane, o, a.ops + a.trun[t].ops_off + o.ops_first, kNmStage, slot);
+		if (s.has) {
+			const int behind = s.scan_len - 1 - s.last_e;          /* unmarked rows behind the last mark, the zero tail included */
+			if (behind > kNmMaxDistance) {
+				if (lane == 0 && s.heads <= kNmStage) { slot[s.heads - 1].ref_stop = s.last_ref; slot[s.heads - 1].read_stop = s.last_read; }
+				n_closed = s.heads;
+			} else {
+				n_closed = s.heads - 1;
+				st.open = 1; st.distance = kNmMaxDistance - behind;
+				st.r.ref_start = s.head_ref; st.r.read_start = s.head_read; st.r.ref_stop = s.last_ref; st.r.read_stop = s.last_read;
+			}
+		}
+	}
+	if (lane == 0) { len[b] = (unsigned long long) n_closed; open[b] = st; }
+}
+
+hipError_t launch_nm_regions_count(const TextArgs &a, int first, int count, unsigned long long *len, unsigned long long *off,
+		unsigned long long *total, NmOpen *open, NmRegion *stage, hipStream_t st) {
+	if (count <= 0) return hipSuccess;
+	hipLaunchKernelGGL(nm_regions_kernel<true>, dim3(count), dim3(64), 0, st, a, first, len, off, open, stage, (NmRegion *) nullptr);
+	hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(256), 0, st, len, off, total, count);
+	return hipGetLastError();
+}
+
+hipError_t launch_nm_regions_write(const TextArgs &a, int first, int count, const unsigned long long *len, const unsigned long long *off,
+		const NmRegion *stage, NmRegion *regions, hipStream_t st) {
+	if (count <= 0) return hipSuccess;
+	hipLaunchKernelGGL(nm_regions_kernel<false>, dim3(count), dim3(64), 0, st, a, first, const_cast<unsigned long long *>(len), off,
+			(NmOpen *) nullptr, const_cast<NmRegion *>(stage), regions);
+	return hipGetLastError();
 }
 
 hipError_t launch_text_size(const TextArgs &a, hipStream_t st) {
