@@ -1,7 +1,9 @@
 /*
  * cvx_host_logic.h -- the device-independent half of the host runtime (cvx_rt_align.cpp):
  * how a batch of cvx_tile is laid out and packed for upload, and how the corridor plans that
- * come back from plan_kernel are turned into kernel classes, arena offsets and work lists.
+ * come back from plan_kernel are turned into kernel classes, arena offsets and work lists, and
+ * those into the compute stage's launch schedule (build_schedule: what is launched, in which order,
+ * on which stream, and how each class is walked).
  * Header-only and free of HIP so that the CPU suite can exercise it (tests/cpp/host_logic_test.cpp).
  */
 #ifndef CVX_HOST_LOGIC_H
@@ -53,8 +55,8 @@ static const int kNumChainClasses = 3;
  * whatever its width), and its very long tiles are chained even if a ring would hold them. */
 static const int kSmallBatchTiles = 2048;
 static const int kLongTileSteps = 32768;
-/* whole tiles of at least this many steps are filled by the exact-tracking instantiation right away (cvx_rt_align.cpp,
- * stage_compute), as long as their class holds at most kExactDirectMaxTiles of them */
+/* whole tiles of at least this many steps are filled by the exact-tracking instantiation right away (build_schedule),
+ * as long as their class holds at most kExactDirectMaxTiles of them */
 static const int kExactDirectSteps = 65536;
 static const int kExactDirectMaxTiles = 4096;
 /* streaming jobs smaller than this alternate between the runtime's two stream sets (cvx_rt_align.cpp, stage_compute) */
@@ -647,6 +649,247 @@ inline void host_plan_rows(int n, const TilePlan *plan, const TileIn *tin, RowsO
 				if (g < v.size()) hp.chain_tasks[slot].push_back(v[g]);
 	}
 	for (auto &v : hp.cls) lpt_sort(v, plan);
+}
+
+/* ------------------------------------------------------------------ the compute stage's launch schedule */
+
+/* What stage_compute (cvx_rt_align.cpp) queues for a planned batch, decided here so that the CPU suite can check it: the
+ * contents of the work lists, one record per fill launch in launch order, the layout of the chain upload and the lanes of
+ * every backtrack walk.  The stage itself only issues what the schedule says. */
+
+/* the knobs of the handle that shape the schedule (cvx_context, CVX_TUNE_*) */
+struct ScheduleTuning {
+	int exact_steps = kExactDirectSteps;
+	int bt_group = 0;
+	bool bt_per_class = true;
+	bool overlap_post = false;
+	int wide_prio = 1, gang_prio = 0, chain_prio = -1, chain_lds_kb = 48;
+};
+
+/* launch_fill's `mode` (= FillMode of cvx_kernels.hip) */
+enum { kModeTwoPhase = 0, kModeExact = 1, kModeChain = 2 };
+
+/* the streams a fill launch may ride on: the first side stream, `post`, `main`, the second side stream */
+enum StreamSlot { kOnSide0 = 0, kOnPost = 1, kOnMain = 2, kOnSide1 = 3, kStreamSlots = 4 };
+
+/* lanes of one backtrack walk: the first n_long tiles of the list at long_lanes per tile, the rest at bulk_lanes */
+struct WalkPlan { int n_long = 0, long_lanes = 32, bulk_lanes = 64; };
+
+/* the walk of list[0, count) (longest read first).  Few tiles in the batch: the walk is latency-bound and
+ * 64 probing lanes per tile take the long diagonal runs in a quarter of the probes; many tiles: it is issue-bound and
+ * several tiles share a wave -- eight for the bulk; the few reads much longer than the rest (a latency-bound tail, a
+ * serial chain of H / 7 probes each) get 32 lanes per tile, beside the bulk on a side stream when the walk is one walk for the
+ * whole batch, in front of it on the same stream otherwise (measured: PacBio 5.4 -> 4.9 ms with 8 lanes, ONT mix 8.2 -> 6.6 with 32).
+ * bt_group: cvx_context::bt_group; n_walk: tiles of all walks of the batch; mean_h: mean read rows per tile of the batch. */
+inline WalkPlan walk_plan(int count, int n_walk, int bt_group, uint64_t mean_h, const int32_t *list, const TileIn *tin) {
+	/* Lanes per tile by the number of tiles walked together (round 5): a walk is a serial chain of probes per tile, and
+	 * what hides a probe's latency is other waves -- so few tiles get many lanes each (a probe then covers 64 / 32 / 16
+	 * path columns of a diagonal run instead of 8) until the walk has about six waves per SIMD, and only beyond that
+	 * is it issue-bound and eight lanes per tile the cheapest.  Measured against round 4's rule (one wave per tile below
+	 * 4 096 tiles, eight lanes from there on): C5 mix, 4 096 tiles of 100 kb, walk 39.5 ms at 8 lanes = 512 waves on 1 024
+	 * SIMDs, 25.9 at 16, 21.6 at 32, 19.4 at 64; ONT mix at 49 152 tiles in one walk 7.6 ms at 8, 6.0 at 16; the PacBio
+	 * bench (49 152 tiles): the walk alone 7.7 ms at 8 and 8.4 at 16, the pipelined step 114.4-114.9 against 113.9-114.1 ms
+	 * (profiles/r05_ab_bt_group.txt). */
+	const int auto_group = count <= 6144 ? 64 : count <= 12288 ? 32 : count <= 49152 ? 16 : 8;
+	WalkPlan w;
+	/*   bt_group   > 0: that many lanes for all        -1: 64 below 4 096 tiles in the batch, else 8        0: by count */
+	w.bulk_lanes = bt_group > 0 ? bt_group : bt_group < 0 ? (n_walk < 4096 ? 64 : 8) : auto_group;
+	/* a bulk at 8 or 16 lanes (never a forced group): the much-longer-than-average reads at its head at 32 */
+	if (bt_group <= 0 && w.bulk_lanes <= 16)
+		while (w.n_long < count && (uint64_t) tin[(size_t) list[w.n_long]].H > 3 * mean_h) w.n_long++;
+	return w;
+}
+
+/* Dynamic LDS that caps the residency of a chained class: tasks are dispatched in order, long before their turn;
+ * resident tasks beyond the ones that can actually run only poll.  Unused dynamic LDS caps the residency at ~1.5x
+ * the blocks that are live at one time (`live` = need / rows-per-block per tile, + slack). */
+inline size_t chain_pad_lds(uint64_t live, int num_cus, int chain_lds_kb, bool rings_beside) {
+	const uint64_t resident = std::min<uint64_t>(8192, std::max<uint64_t>(768, live + live / 2 + 256));
+	const size_t per_cu = (size_t) ((resident + (uint64_t) num_cus - 1) / (uint64_t) num_cus);
+	size_t pad_lds = per_cu >= 32 ? 0 : (size_t) (160 * 1024) / per_cu - 4096;
+	pad_lds = std::min<size_t>(pad_lds, 60 * 1024) / 256 * 256;
+	/* The padding is LDS the ring classes of the same batch cannot use: a handful of chained retries among a thousand whole
+	 * tiles (ngmlr's own launches: 10-40 chained tiles, resident = 768 tasks = 3 per CU at 50 KB each) held 150 of a CU's
+	 * 160 KB for their 7 ms, and the M = 3 / M = 4 classes -- 4-5 KB per wave -- crawled until they were gone: a launch's
+	 * fill was the SUM of the chained class and the widest ring class (18.6 = 7.0 + 11.7 ms, profiles/r06_e2e_launch_trace.txt).
+	 * Beside ring classes the cap may hold chain_lds_kb per CU; more tasks than can run then sit in their back-off sleep. */
+	if (rings_beside && chain_lds_kb > 0 && per_cu > 0 && per_cu < 32) {
+		const size_t budget = (size_t) chain_lds_kb * 1024 / per_cu;
+		const size_t capped = budget > 4096 ? (budget - 4096) / 256 * 256 : 0;
+		pad_lds = std::min(pad_lds, capped);
+	}
+	return pad_lds;
+}
+
+/* one forward-fill launch: a chained class (row-block tasks + the per-tile reduction), a whole-tile class (the direct-exact
+ * prefix, the two-phase pass, the exact redo pass) or the catch-all kernel */
+struct FillLaunch {
+	int kind = 0;                    /* CVX_LAUNCH_* */
+	int m = 0, gang = 1, wrap = 0;   /* (the catch-all kernel: 0, 16, 1 -- what its cvx_launch_info has always said) */
+	int slot = 0;                    /* index into HostPlan::chain_tasks (chained) or HostPlan::cls (whole tiles) */
+	const std::vector<int32_t> *tiles = nullptr;   /* the launch's tiles (in the HostPlan) */
+	size_t list_off = 0;             /* whole tiles, catch-all: lists[list_off, + count), the first n_direct straight to the exact fill */
+	int n_direct = 0, count = 0;     /* (chained: count = row-block tasks) */
+	size_t pad_lds = 0;              /* chained: chain_pad_lds */
+	int prio = 0;                    /* FillArgs::chain_prio: the chain priority, the widest ring class's or the gangs' */
+	int stream = kOnMain;            /* StreamSlot */
+	size_t bt_off = 0;               /* the launch's backtrack segment: lists[bt_off, + bt_count) */
+	int bt_count = 0;
+	WalkPlan walk;                   /* of that segment (per_class only) */
+	cvx_launch_info info;
+};
+
+struct ComputeSchedule {
+	std::vector<FillLaunch> launches;      /* in launch order: chained classes, whole-tile classes from the widest ring down, the catch-all kernel */
+	size_t n_listed = 0;                   /* entries of `lists`: fill lists, then the backtrack segments from bt_begin on */
+	size_t bt_begin = 0;
+	int n_walk = 0;                        /* tiles of all backtrack segments */
+	bool per_class = false;                /* every launch walks its own segment behind its fill; else one walk (`walk`) behind all fills */
+	WalkPlan walk;
+	/* chained tiles: tasks of every chain class, block table and tile lists in one upload */
+	size_t chain_task_off[kNumChainClasses * 2] = {0}, chain_tile_off[kNumChainClasses * 2] = {0};
+	size_t chain_blk_off = 0, chain_bytes = 0;
+};
+
+/* hp: of host_plan_rows (the direct-exact tiles move to the front of their class and get kPadRedo in hp.tout);
+ * lists: room for 2 n entries; n_rows: read rows of all n tiles. */
+inline void build_schedule(HostPlan &hp, const TilePlan *plan, const TileIn *tin, int n, uint64_t n_rows, int num_cus,
+		const ScheduleTuning &t, int32_t *lists, ComputeSchedule &s) {
+	size_t n_listed = 0;
+	size_t cls_off[kNumClasses * 2];
+	int n_direct[kNumClasses * 2];
+	int ring_classes = 0;
+	/* Very long tiles go straight to the exact-tracking instantiation.  The two-phase pass saves three half-rate ops per
+	 * cell (~12 %) but a tile whose best cell is not in its last anti-diagonals -- a local alignment: an inverted segment,
+	 * a read that does not reach its end -- is redone from step 0, and for a 100 kb tile that second pass is another
+	 * ~100 ms on one wave behind everything else (C5 mix: 77 ms of a 200 ms fill).  Tiles of kExactDirectSteps steps and
+	 * more are flagged kPadRedo up front and listed first; the exact launch over that prefix does them once.  Only while
+	 * the class cannot fill the device several times over (then 12 % of throughput would cost more than the tail). */
+	for (size_t c = 0; c < hp.cls.size(); ++c) {
+		std::vector<int32_t> &v = hp.cls[c];      /* already in LPT order */
+		cls_off[c] = n_listed;
+		n_direct[c] = 0;
+		if (v.empty()) continue;
+		ring_classes++;
+		auto direct = [&](int32_t ti) { return hp.trun[(size_t) ti].nsteps >= t.exact_steps; };
+		const int nl = t.exact_steps > 0 ? (int) std::count_if(v.begin(), v.end(), direct) : 0;
+		if (nl > 0 && nl <= kExactDirectMaxTiles) {
+			std::stable_partition(v.begin(), v.end(), direct);
+			for (int q = 0; q < nl; ++q) hp.tout[(size_t) v[(size_t) q]].pad = kPadRedo;
+			n_direct[c] = nl;
+		}
+		memcpy(lists + n_listed, v.data(), v.size() * sizeof(int32_t));
+		n_listed += v.size();
+	}
+	const size_t generic_begin = n_listed;
+	if (!hp.generic.empty()) memcpy(lists + n_listed, hp.generic.data(), hp.generic.size() * sizeof(int32_t));
+	n_listed += hp.generic.size();
+
+	/* forward fill: one launch per populated kernel class (+ its exact redo pass), classes run
+	 * concurrently on separate streams (a sparsely populated class would otherwise serialise a
+	 * whole tile latency behind the big one); widest rings first, they have the longest tiles */
+	s.launches.clear();
+	s.launches.reserve((size_t) (kNumChainClasses + kNumClasses) * 2 + 1);
+	/* chained tiles first (their dependency chains are the longest thing in a batch): the row-block
+	 * tasks of a class, then the per-tile reduction of the block results */
+	for (size_t c = 0; c < hp.chain_tasks.size(); ++c) {
+		if (hp.chain_tasks[c].empty()) continue;
+		FillLaunch L;
+		L.kind = CVX_LAUNCH_CHAINED;
+		L.m = kChainClasses[c / 2]; L.wrap = (int) (c & 1); L.slot = (int) c;
+		L.tiles = &hp.chain_tiles[c];
+		L.count = (int) hp.chain_tasks[c].size();
+		L.prio = t.chain_prio >= 0 ? t.chain_prio : 1;
+		uint64_t live = 0;
+		for (int32_t ti : hp.chain_tiles[c]) live += (uint64_t) plan[(size_t) ti].need / (uint64_t) (64 * L.m + kChainChunk) + 2;
+		L.pad_lds = chain_pad_lds(live, num_cus, t.chain_lds_kb, ring_classes > 0);
+		s.launches.push_back(L);
+	}
+	bool widest = true;
+	for (int cc = (int) hp.cls.size() - 1; cc >= 0; --cc) {
+		const size_t c = (size_t) cc;
+		if (hp.cls[c].empty()) continue;
+		const KernelClass &kc = kClasses[c / 2];
+		FillLaunch L;
+		L.kind = kc.gang > 1 ? CVX_LAUNCH_GANG : CVX_LAUNCH_WHOLE;
+		L.m = kc.m; L.gang = kc.gang; L.wrap = (int) (c & 1); L.slot = cc;
+		L.tiles = &hp.cls[c];
+		L.list_off = cls_off[c]; L.n_direct = n_direct[c]; L.count = (int) hp.cls[c].size();
+		/* (the widest ring class of a batch of several one priority notch up; gangs have a knob of their own) */
+		L.prio = kc.gang > 1 ? t.gang_prio : (widest && ring_classes > 1) ? t.wide_prio : 0;
+		widest = false;
+		s.launches.push_back(L);
+	}
+	if (!hp.generic.empty()) {
+		FillLaunch L;
+		L.kind = CVX_LAUNCH_CATCH_ALL;
+		L.m = 0; L.gang = 16; L.wrap = 1;
+		L.tiles = &hp.generic;
+		L.list_off = generic_begin; L.count = (int) hp.generic.size();
+		s.launches.push_back(L);
+	}
+
+	/* fill launches go round-robin over the side streams, `post` and the main stream itself (which has
+	 * nothing else to do until they are all done): classes side by side */
+	/* (the `post` stream carries a fill class too unless the post-fill overlap experiment owns it) */
+	/* (order: first side stream, post, main -- the assignment of rounds 2-4 for up to three classes -- and the second side stream
+	 * only for a fourth class, i.e. with gangs.  Which class rides on which stream is not neutral: with the three whole-tile
+	 * classes of the C5 mix on side / side / post instead of side / post / main the same batch takes 181 or 236 ms depending on the
+	 * handle, on side / post / main 194 every time: profiles/r05_fill_stream_order.txt) */
+	int order[kStreamSlots], n_order = 0;
+	for (int sl = 0; sl < kStreamSlots; ++sl) if (sl != kOnPost || !t.overlap_post) order[n_order++] = sl;
+	/* behind the fill lists: every computed tile once, longest read first (counting sort on H / 32) --
+	 * the order in which the backtrack takes them, four to a wave: the walk of a tile is a serial
+	 * chain of ~H / 7 probes, so the long ones must start first and share their wave with their like.
+	 * One segment per fill launch, in launch order: a batch of several classes walks each class right behind its own fill,
+	 * on that fill's stream, while the other classes still fill; a batch of one class has one segment = the whole list. */
+	s.bt_begin = n_listed;
+	constexpr int kBuckets = 4096;
+	auto bucket = [&](int32_t ti) { const int k = tin[(size_t) ti].H >> 5; return kBuckets - 1 - (k < kBuckets ? k : kBuckets - 1); };
+	std::vector<int32_t> count((size_t) kBuckets + 1);
+	for (size_t i = 0; i < s.launches.size(); ++i) {
+		FillLaunch &L = s.launches[i];
+		L.stream = order[i % (size_t) n_order];
+		memset(&L.info, 0, sizeof(L.info));
+		L.info.slots_per_lane = L.m; L.info.wrap16 = L.wrap; L.info.n_tiles = (int) L.tiles->size(); L.info.kind = L.kind;
+		L.info.waves = L.kind == CVX_LAUNCH_CHAINED ? L.count : L.gang;      /* row-block tasks / waves per tile (a gang's size) */
+		std::fill(count.begin(), count.end(), 0);
+		for (int32_t ti : *L.tiles) {
+			const TilePlan &p = plan[(size_t) ti];
+			const TileIn &in = tin[(size_t) ti];
+			L.info.cells += p.cells; L.info.active_cells += p.active;
+			L.info.alg_bytes += p.cells + 6ull * (uint64_t) in.H + 2ull * (uint64_t) in.W;
+			L.info.read_bases += (uint64_t) in.H;
+			if (!hp.trun[(size_t) ti].skip) count[(size_t) bucket(ti) + 1]++;
+		}
+		for (int k = 0; k < kBuckets; ++k) count[(size_t) k + 1] += count[(size_t) k];
+		L.bt_off = n_listed;
+		L.bt_count = count[(size_t) kBuckets];
+		/* (stable: inside a bucket of equally long reads the class's own order, most cells first) */
+		for (int32_t ti : *L.tiles) if (!hp.trun[(size_t) ti].skip) lists[n_listed + (size_t) count[(size_t) bucket(ti)]++] = ti;
+		n_listed += (size_t) L.bt_count;
+	}
+	s.n_listed = n_listed;
+	s.n_walk = (int) (n_listed - s.bt_begin);
+
+	/* Several fill classes (ONT mix: chained retries, M = 4, M = 3; C5): each class is walked right behind its own fill on
+	 * that fill's stream.  The launch of such a batch lasts as long as its longest dependency chain, and while the last
+	 * chains finish on a few waves the device has issue slots to spare: the other classes' walks run there instead of
+	 * behind everything (CVX_TUNE_BT_PER_CLASS=0: one walk behind all fills, as a batch of one class has it anyway). */
+	/* Only where the walk is issue-bound (>= 4096 tiles; measured, r04c: ONT mix 60 000 tiles 57.2 -> 56.0 ms, 24 000 tiles
+	 * 35.3 -> 34.2, C5 mix 6 144 tiles 397 -> 369 ms); a small batch's one-wave-per-tile walks are latency-bound chains that
+	 * gain nothing from starting early and cost the fills still running (C5 mix 2 048 tiles: 183.6 -> 187.2 ms). */
+	s.per_class = t.bt_per_class && s.launches.size() > 1 && !t.overlap_post && s.n_walk >= 4096;
+	const uint64_t mean_h = n_rows / (uint64_t) std::max(n, 1);
+	if (s.per_class) for (FillLaunch &L : s.launches) L.walk = walk_plan(L.bt_count, s.n_walk, t.bt_group, mean_h, lists + L.bt_off, tin);
+	else s.walk = walk_plan(s.n_walk, s.n_walk, t.bt_group, mean_h, lists + s.bt_begin, tin);
+
+	s.chain_blk_off = s.chain_bytes = 0;
+	if (hp.n_chained) {
+		for (size_t c = 0; c < hp.chain_tasks.size(); ++c) { s.chain_task_off[c] = s.chain_bytes; s.chain_bytes += hp.chain_tasks[c].size() * sizeof(ChainTask); }
+		s.chain_blk_off = s.chain_bytes; s.chain_bytes += hp.chain_blk.size() * sizeof(ChainBlk);
+		for (size_t c = 0; c < hp.chain_tiles.size(); ++c) { s.chain_tile_off[c] = s.chain_bytes; s.chain_bytes += (hp.chain_tiles[c].size() * sizeof(int32_t) + 7) / 8 * 8; }
+	}
 }
 
 }  // namespace cvx

@@ -158,6 +158,9 @@ void score_state_free(cvx_score_state *ss);
  * 24 558-tile M = 3 launch instead of beside it. */
 static const int kAuxStreams = 2;      /* (round 5: a batch has up to four fill classes -- chained, gangs, M = 4, M = 3 -- and each wants a stream of its own) */
 
+/* the events of one fill launch: its start, two-phase pass done, exact pass done, the class's own backtrack done */
+enum LaunchEvent { kLevStart = 0, kLevTwoPhase = 1, kLevExact = 2, kLevWalked = 3, kLevPerLaunch = 4 };
+
 enum BatchState { kFailed = -1, kEmpty = 0, kUploaded = 1, kPlanned = 2, kComputed = 3, kFinished = 4 };
 
 struct cvx_batch_s {
@@ -235,9 +238,8 @@ struct cvx_batch_s {
 	hipEvent_t ev_bt0 = nullptr, ev_bt1 = nullptr;   /* fork / join of the long-read backtrack launch */
 	hipEvent_t ev_in = nullptr;      /* upload + plan records on the host */
 	hipEvent_t ev_res = nullptr;     /* result records on the host */
-	hipEvent_t ev_ops = nullptr;     /* dense ops on the host */
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* timing: plan begin/end, fills done, all done, fills may start */
-	std::vector<hipEvent_t> lev;     /* 4 events per fill class: start, two-phase pass done, exact pass done, the class's own backtrack done */
+	std::vector<hipEvent_t> lev;     /* kLevPerLaunch events per fill launch (LaunchEvent) */
 	std::vector<cvx_launch_info> launches;
 	cvx_timing timing;
 
@@ -264,7 +266,6 @@ struct cvx_batch_s {
 	int make_events() {
 		if (!ev_in) HIP_TRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
 		if (!ev_res) HIP_TRY(hipEventCreateWithFlags(&ev_res, hipEventDisableTiming));
-		if (!ev_ops) HIP_TRY(hipEventCreateWithFlags(&ev_ops, hipEventDisableTiming));
 		if (!ev_bt0) HIP_TRY(hipEventCreateWithFlags(&ev_bt0, hipEventDisableTiming));
 		if (!ev_bt1) HIP_TRY(hipEventCreateWithFlags(&ev_bt1, hipEventDisableTiming));
 		for (auto &e : ev) if (!e) HIP_TRY(hipEventCreate(&e));
@@ -289,7 +290,6 @@ struct cvx_batch_s {
 		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();
 		if (ev_in) { (void) hipEventDestroy(ev_in); ev_in = nullptr; }
 		if (ev_res) { (void) hipEventDestroy(ev_res); ev_res = nullptr; }
-		if (ev_ops) { (void) hipEventDestroy(ev_ops); ev_ops = nullptr; }
 		if (ev_bt0) { (void) hipEventDestroy(ev_bt0); ev_bt0 = nullptr; }
 		if (ev_bt1) { (void) hipEventDestroy(ev_bt1); ev_bt1 = nullptr; }
 		for (auto &e : ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
@@ -347,6 +347,7 @@ struct cvx_context {
 	int bt_group = 0;          /* lanes per tile in the backtrack: 0 = auto (by the number of tiles walked together: 64 / 32 / 16 / 8, and 32 for
 	                            * the much-longer-than-average reads of a bulk walked at 8 or 16), 8 / 16 / 32 = that many for all, 64 = the
 	                            * one-wave-per-tile walk, -1 = round 4's rule (64 below 4 096 tiles, else 8 + 32) (env CVX_TUNE_BT_GROUP) */
+	bool bt_per_class = true;  /* tuning knob (env CVX_TUNE_BT_PER_CLASS = 0 clears it): a batch of several fill classes walks each class behind its own fill (build_schedule) */
 	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
 	bool sse_variant = false; /* scoring outside the regime where the reference's SSE path equals the scalar recurrence:
 	                           * every tile goes to the catch-all kernel's SSE-variant instantiation */

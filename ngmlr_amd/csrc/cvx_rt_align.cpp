@@ -5,7 +5,8 @@
  *   upload   host threads pack sequences + corridor rows into the batch's own pinned staging,
  *            piece by piece, each piece's DMA running under the packing of the next  (stream `io`)
  *   plan     plan_kernel, plan records back to pinned memory                          (stream `io`)
- *   compute  host: kernel class / arena offsets / LPT lists from the plan records;
+ *   compute  host: kernel class / arena offsets / LPT lists from the plan records, then the launch schedule
+ *            (build_schedule, cvx_host_logic.h: list contents, one record per fill launch, stream slots, walk lanes);
  *            fill_ring_kernel per class (+ exact redo pass)                   (streams `main` + `aux`)
  *            backtrack_kernel, finalize_kernel (device-side prefix sums and result records),
  *            compact_ops_kernel, result records back to pinned memory               (stream `main`;
@@ -302,6 +303,71 @@ int stage_plan(cvx_context *h, cvx_batch_s *b, hipStream_t st) {
 	return CVX_OK;
 }
 
+/* ---- stage 3's helpers */
+/* the kernels' arguments of a batch; a fill launch adds its own list, chain fields and priority */
+void kernel_args(const cvx_context *h, const cvx_batch_s *b, const ChainBlk *chain_blk, FillArgs &a, BacktrackArgs &ba) {
+	a.seq = ba.seq = b->d_seq.p;
+	a.rows = ba.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
+	a.rsrc = ba.rsrc = b->d_rsrc.p;
+	a.tin = ba.tin = b->d_tin.p;
+	a.trun = ba.trun = b->d_trun.p;
+	a.tout = ba.tout = b->d_tout.p;
+	ba.dirs = a.dirs = b->d_dirs.p;
+	a.ops = ba.ops = b->d_regions.p;
+	a.list = nullptr; a.list_n = 0;
+	a.redo_count = b->d_counters.p;
+	a.late_min_groups = h->tune_late_min;
+	a.late_shift = h->tune_late_shift;
+	a.pen_table = h->tune_pen_table;
+	a.tasks = nullptr; a.chain_ticket = nullptr; a.bnd = nullptr; a.chain_out = nullptr; a.bnd_epoch = 0; a.chain_prio = 0;
+	a.sp = h->sp;
+	ba.chain_blk = chain_blk;
+	ba.n_tiles = b->n;
+}
+
+/* the walk of lists[at, at + count) on `ws` with the lanes `w` gives it (walk_plan, cvx_host_logic.h); the long head runs
+ * beside the bulk on `side` when there is one (the one walk of a whole batch), in front of it on `ws` otherwise */
+int issue_walk(cvx_batch_s *b, const BacktrackArgs &ba, const WalkPlan &w, size_t at, int count, hipStream_t ws, hipStream_t side) {
+	if (count <= 0) return CVX_OK;
+	const int32_t *list = b->d_lists.p + at;
+	const bool fork = w.n_long > 0 && side != nullptr;
+	if (fork) {
+		HIP_TRY(hipEventRecord(b->ev_bt0, ws));
+		HIP_TRY(hipStreamWaitEvent(side, b->ev_bt0, 0));
+	}
+	if (w.n_long > 0) HIP_TRY(launch_backtrack(ba, list, w.n_long, w.long_lanes, fork ? side : ws));
+	if (fork) HIP_TRY(hipEventRecord(b->ev_bt1, side));
+	HIP_TRY(launch_backtrack(ba, list + w.n_long, count - w.n_long, w.bulk_lanes, ws));
+	if (fork) HIP_TRY(hipStreamWaitEvent(ws, b->ev_bt1, 0));
+	return CVX_OK;
+}
+
+/* chained tiles: tasks of every chain class, block table and tile lists in one upload on `st` (layout: build_schedule) */
+int upload_chain(cvx_batch_s *b, const HostPlan &hp, const ComputeSchedule &sch, hipStream_t st) {
+	RC_TRY(b->h_chain.ensure(sch.chain_bytes));
+	uint8_t *hc = b->h_chain.as<uint8_t>();
+	for (size_t c = 0; c < hp.chain_tasks.size(); ++c)
+		if (!hp.chain_tasks[c].empty()) memcpy(hc + sch.chain_task_off[c], hp.chain_tasks[c].data(), hp.chain_tasks[c].size() * sizeof(ChainTask));
+	memcpy(hc + sch.chain_blk_off, hp.chain_blk.data(), hp.chain_blk.size() * sizeof(ChainBlk));
+	for (size_t c = 0; c < hp.chain_tiles.size(); ++c)
+		if (!hp.chain_tiles[c].empty()) memcpy(hc + sch.chain_tile_off[c], hp.chain_tiles[c].data(), hp.chain_tiles[c].size() * sizeof(int32_t));
+	RC_TRY(b->d_chain.ensure(sch.chain_bytes));
+	RC_TRY(b->d_chain_out.ensure(hp.chain_blk.size()));
+	{
+		/* boundary records validate themselves by the launch epoch in their upper bits: a buffer starts out zeroed
+		 * (epoch 0 = never written) and is zeroed again when the epochs wrap */
+		const size_t had = b->d_bnd.cap;
+		RC_TRY(b->d_bnd.ensure((size_t) hp.bnd_recs + 64));
+		if (b->d_bnd.cap != had || b->bnd_epoch >= kBndEpochMax) {
+			HIP_TRY(hipMemsetAsync(b->d_bnd.p, 0, b->d_bnd.cap * sizeof(BoundaryRec), st));
+			b->bnd_epoch = 0;
+		}
+		b->bnd_epoch += 1;
+	}
+	HIP_TRY(hipMemcpyAsync(b->d_chain.p, hc, sch.chain_bytes, hipMemcpyHostToDevice, st));
+	return CVX_OK;
+}
+
 /* ---- stage 3: host planning, then every kernel of the batch on `main` (+ aux); nothing waits */
 int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	const int n = b->n;
@@ -331,7 +397,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 		return CVX_OK;
 	}
 
-	/* host planning: kernel class, arena offsets, work lists (cvx_host_logic.h) */
+	/* host planning: kernel class, arena offsets, work lists, then the launch schedule (cvx_host_logic.h) */
 	HostPlan hp;
 	PlanTuning tune;
 	tune.min_slots = h->tune_min_slots; tune.max_slots = h->tune_max_slots; tune.force_wrap = h->tune_force_wrap; tune.chain_m = h->tune_chain_m;
@@ -345,8 +411,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 		expand_rows_host(rsrc[(size_t) i], b->tin()[(size_t) i].H, b->h_delta.as<uint8_t>(), b->h_rowsx.as<RowDesc>(), tmp.data());
 		return tmp.data();
 	}, true, tune, hp);
-	std::vector<std::vector<int32_t>> &cls = hp.cls;
-	std::vector<int32_t> &generic = hp.generic;
+	const std::vector<int32_t> &generic = hp.generic;
 	RC_TRY(b->d_dirs.ensure((size_t) hp.dir_dwords + 64));
 	RC_TRY(b->d_regions.ensure((size_t) hp.ops_ints + 64));
 	/* dense ops arena: an alignment of H read bases has far fewer than H run-length ops (about
@@ -359,66 +424,13 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	RC_TRY(b->h_trun.ensure((size_t) n * sizeof(TileRun)));
 	RC_TRY(b->h_tout.ensure((size_t) n * sizeof(TileOut)));
 	RC_TRY(b->h_lists.ensure((size_t) 2 * n * sizeof(int32_t) + 64));
+	ScheduleTuning stune;
+	stune.exact_steps = h->tune_exact_steps; stune.bt_group = h->bt_group; stune.bt_per_class = h->bt_per_class; stune.overlap_post = h->overlap_post;
+	stune.wide_prio = h->tune_wide_prio; stune.gang_prio = h->tune_gang_prio; stune.chain_prio = h->tune_chain_prio; stune.chain_lds_kb = h->tune_chain_lds_kb;
+	ComputeSchedule sch;
+	build_schedule(hp, b->plan(), b->tin(), n, b->n_rows, h->num_cus, stune, b->h_lists.as<int32_t>(), sch);
 	memcpy(b->h_trun.p, hp.trun.data(), (size_t) n * sizeof(TileRun));
-	memcpy(b->h_tout.p, hp.tout.data(), (size_t) n * sizeof(TileOut));
-	int32_t *lists = b->h_lists.as<int32_t>();
-	size_t n_listed = 0;
-	std::vector<int> seg_begin(cls.size(), 0);
-	/* Very long tiles go straight to the exact-tracking instantiation.  The two-phase pass saves three half-rate ops per
-	 * cell (~12 %) but a tile whose best cell is not in its last anti-diagonals -- a local alignment: an inverted segment,
-	 * a read that does not reach its end -- is redone from step 0, and for a 100 kb tile that second pass is another
-	 * ~100 ms on one wave behind everything else (C5 mix: 77 ms of a 200 ms fill).  Tiles of kExactDirectSteps steps and
-	 * more are flagged kPadRedo up front and listed first; the exact launch over that prefix does them once.  Only while
-	 * the class cannot fill the device several times over (then 12 % of throughput would cost more than the tail). */
-	std::vector<int> n_direct(cls.size(), 0);
-	for (size_t c = 0; c < cls.size(); ++c) {
-		seg_begin[c] = (int) n_listed;      /* already in LPT order */
-		if (h->tune_exact_steps > 0 && !cls[c].empty()) {
-			int nl = 0;
-			for (int32_t ti : cls[c]) if (hp.trun[(size_t) ti].nsteps >= h->tune_exact_steps) nl++;
-			if (nl > 0 && nl <= kExactDirectMaxTiles) {
-				std::stable_partition(cls[c].begin(), cls[c].end(), [&](int32_t ti) { return hp.trun[(size_t) ti].nsteps >= h->tune_exact_steps; });
-				TileOut *ho = b->h_tout.as<TileOut>();
-				for (int q = 0; q < nl; ++q) ho[(size_t) cls[c][(size_t) q]].pad = kPadRedo;
-				n_direct[c] = nl;
-			}
-		}
-		if (!cls[c].empty()) memcpy(lists + n_listed, cls[c].data(), cls[c].size() * sizeof(int32_t));
-		n_listed += cls[c].size();
-	}
-	const int generic_begin = (int) n_listed;
-	if (!generic.empty()) memcpy(lists + n_listed, generic.data(), generic.size() * sizeof(int32_t));
-	n_listed += generic.size();
-	/* behind the fill lists: every computed tile once, longest read first (counting sort on H / 32) --
-	 * the order in which the backtrack takes them, four to a wave: the walk of a tile is a serial
-	 * chain of ~H / 7 probes, so the long ones must start first and share their wave with their like.
-	 * One segment per fill launch, in launch order (chained classes, whole-tile classes from the widest ring down, the
-	 * catch-all kernel): a batch of several classes walks each class right behind its own fill, on that fill's stream,
-	 * while the other classes still fill; a batch of one class has one segment = the whole list. */
-	const size_t bt_begin = n_listed;
-	std::vector<const std::vector<int32_t> *> launch_tiles;
-	for (size_t c = 0; c < hp.chain_tasks.size(); ++c) if (!hp.chain_tasks[c].empty()) launch_tiles.push_back(&hp.chain_tiles[c]);
-	for (int cc = (int) cls.size() - 1; cc >= 0; --cc) if (!cls[(size_t) cc].empty()) launch_tiles.push_back(&cls[(size_t) cc]);
-	if (!generic.empty()) launch_tiles.push_back(&generic);
-	std::vector<std::pair<size_t, int>> bt_seg;      /* (offset in lists, tiles) per launch */
-	{
-		const TileIn *tin = b->tin();
-		constexpr int kBuckets = 4096;
-		auto bucket = [&](int32_t ti) { const int k = tin[(size_t) ti].H >> 5; return kBuckets - 1 - (k < kBuckets ? k : kBuckets - 1); };
-		std::vector<int32_t> count((size_t) kBuckets + 1);
-		for (const std::vector<int32_t> *v : launch_tiles) {
-			std::fill(count.begin(), count.end(), 0);
-			for (int32_t ti : *v) if (!hp.trun[(size_t) ti].skip) count[(size_t) bucket(ti) + 1]++;
-			for (int k = 0; k < kBuckets; ++k) count[(size_t) k + 1] += count[(size_t) k];
-			const size_t at = n_listed;
-			const int m = count[(size_t) kBuckets];
-			/* (stable: inside a bucket of equally long reads the class's own order, most cells first) */
-			for (int32_t ti : *v) if (!hp.trun[(size_t) ti].skip) lists[at + (size_t) count[(size_t) bucket(ti)]++] = ti;
-			n_listed += (size_t) m;
-			bt_seg.emplace_back(at, m);
-		}
-	}
-	const int n_walk = (int) (n_listed - bt_begin);
+	memcpy(b->h_tout.p, hp.tout.data(), (size_t) n * sizeof(TileOut));      /* (with the direct-exact tiles flagged kPadRedo) */
 	if (!generic.empty()) {
 		RC_TRY(b->h_goff.ensure((generic.size() + 1) * sizeof(uint64_t)));
 		uint64_t *goff = b->h_goff.as<uint64_t>();
@@ -429,251 +441,69 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 		RC_TRY(b->d_gscratch_off.ensure(generic.size() + 1));
 		HIP_TRY(hipMemcpyAsync(b->d_gscratch_off.p, goff, (generic.size() + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 	}
-	/* chained tiles: tasks of every chain class, block table and tile lists in one upload */
-	size_t chain_task_off[kNumChainClasses * 2] = {0}, chain_tile_off[kNumChainClasses * 2] = {0};
-	size_t chain_blk_off = 0, chain_bytes = 0;
-	if (hp.n_chained) {
-		for (size_t c = 0; c < hp.chain_tasks.size(); ++c) { chain_task_off[c] = chain_bytes; chain_bytes += hp.chain_tasks[c].size() * sizeof(ChainTask); }
-		chain_blk_off = chain_bytes; chain_bytes += hp.chain_blk.size() * sizeof(ChainBlk);
-		for (size_t c = 0; c < hp.chain_tiles.size(); ++c) { chain_tile_off[c] = chain_bytes; chain_bytes += (hp.chain_tiles[c].size() * sizeof(int32_t) + 7) / 8 * 8; }
-		RC_TRY(b->h_chain.ensure(chain_bytes));
-		uint8_t *hc = b->h_chain.as<uint8_t>();
-		for (size_t c = 0; c < hp.chain_tasks.size(); ++c)
-			if (!hp.chain_tasks[c].empty()) memcpy(hc + chain_task_off[c], hp.chain_tasks[c].data(), hp.chain_tasks[c].size() * sizeof(ChainTask));
-		memcpy(hc + chain_blk_off, hp.chain_blk.data(), hp.chain_blk.size() * sizeof(ChainBlk));
-		for (size_t c = 0; c < hp.chain_tiles.size(); ++c)
-			if (!hp.chain_tiles[c].empty()) memcpy(hc + chain_tile_off[c], hp.chain_tiles[c].data(), hp.chain_tiles[c].size() * sizeof(int32_t));
-		RC_TRY(b->d_chain.ensure(chain_bytes));
-		RC_TRY(b->d_chain_out.ensure(hp.chain_blk.size()));
-		{
-			/* boundary records validate themselves by the launch epoch in their upper bits: a buffer starts out zeroed
-			 * (epoch 0 = never written) and is zeroed again when the epochs wrap */
-			const size_t had = b->d_bnd.cap;
-			RC_TRY(b->d_bnd.ensure((size_t) hp.bnd_recs + 64));
-			if (b->d_bnd.cap != had || b->bnd_epoch >= kBndEpochMax) {
-				HIP_TRY(hipMemsetAsync(b->d_bnd.p, 0, b->d_bnd.cap * sizeof(BoundaryRec), st));
-				b->bnd_epoch = 0;
-			}
-			b->bnd_epoch += 1;
-		}
-		HIP_TRY(hipMemcpyAsync(b->d_chain.p, hc, chain_bytes, hipMemcpyHostToDevice, st));
-	}
+	if (hp.n_chained) RC_TRY(upload_chain(b, hp, sch, st));
 	HIP_TRY(hipMemcpyAsync(b->d_trun.p, b->h_trun.p, (size_t) n * sizeof(TileRun), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(b->d_tout.p, b->h_tout.p, (size_t) n * sizeof(TileOut), hipMemcpyHostToDevice, st));
-	if (n_listed) HIP_TRY(hipMemcpyAsync(b->d_lists.p, lists, n_listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
+	if (sch.n_listed) HIP_TRY(hipMemcpyAsync(b->d_lists.p, b->h_lists.p, sch.n_listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
 	/* (the batch's counters are zero: cleared when the arena was allocated and again by finalize_kernel,
 	 * their last reader -- a memset here would be a tiny kernel that has to find a free wave slot among
 	 * the previous batch's 24 576 backtrack waves before this batch's fills may start: measured 7 ms) */
 	HIP_TRY(hipEventRecord(b->ev[4], st));        /* inputs of the fills are in place */
 
-	/* forward fill: one launch per populated kernel class (+ its exact redo pass), classes run
-	 * concurrently on separate streams (a sparsely populated class would otherwise serialise a
-	 * whole tile latency behind the big one); widest rings first, they have the longest tiles */
-	auto fill_args = [&](const int32_t *list, int list_n) {
-		FillArgs a;
-		a.seq = b->d_seq.p;
-		a.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
-		a.rsrc = b->d_rsrc.p;
-		a.tin = b->d_tin.p;
-		a.trun = b->d_trun.p;
-		a.tout = b->d_tout.p;
-		a.dirs = b->d_dirs.p;
-		a.list = list;
-		a.list_n = list_n;
-		a.redo_count = b->d_counters.p;
-		a.late_min_groups = h->tune_late_min;
-		a.late_shift = h->tune_late_shift;
-		a.pen_table = h->tune_pen_table;
-		a.tasks = nullptr; a.chain_ticket = nullptr; a.bnd = nullptr; a.chain_out = nullptr; a.bnd_epoch = 0; a.chain_prio = 0;
-		a.ops = b->d_regions.p;
-		a.sp = h->sp;
-		return a;
-	};
-	auto launch_stats = [&](const std::vector<int32_t> &v, int m, int nw, int wrap, int kind) {
-		cvx_launch_info li;
-		memset(&li, 0, sizeof(li));
-		li.slots_per_lane = m; li.waves = nw; li.wrap16 = wrap; li.n_tiles = (int) v.size(); li.kind = kind;
-		for (int32_t ti : v) {
-			const TilePlan &p = b->plan()[(size_t) ti];
-			const TileIn &in = b->tin()[(size_t) ti];
-			li.cells += p.cells; li.active_cells += p.active;
-			li.alg_bytes += p.cells + 6ull * (uint64_t) in.H + 2ull * (uint64_t) in.W;
-			li.read_bases += (uint64_t) in.H;
-		}
-		b->launches.push_back(li);
-	};
-	/* backtrack, device-side result records + prefix sums, ops compaction */
+	/* the fill launches, as scheduled: each on its stream behind the input copies, its own walk behind it (per_class) */
+	FillArgs fa;
 	BacktrackArgs ba;
-	ba.chain_blk = hp.n_chained ? reinterpret_cast<const ChainBlk *>(b->d_chain.p + chain_blk_off) : nullptr;
-	ba.seq = b->d_seq.p;
-	ba.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
-	ba.rsrc = b->d_rsrc.p;
-	ba.tin = b->d_tin.p;
-	ba.trun = b->d_trun.p;
-	ba.tout = b->d_tout.p;
-	ba.dirs = b->d_dirs.p;
-	ba.ops = b->d_regions.p;
-	ba.n_tiles = n;
-	/* the walk of lists[at, at + count) (longest read first) on `ws`.  Few tiles in the batch: the walk is latency-bound and
-	 * 64 probing lanes per tile take the long diagonal runs in a quarter of the probes; many tiles: it is issue-bound and
-	 * several tiles share a wave -- eight for the bulk; the few reads much longer than the rest (a latency-bound tail, a
-	 * serial chain of H / 7 probes each) get 32 lanes per tile, beside the bulk on `side` when `fork` (one walk for the whole
-	 * batch), in front of it on the same stream otherwise (measured: PacBio 5.4 -> 4.9 ms with 8 lanes, ONT mix 8.2 -> 6.6 with 32) */
-	auto walk_list = [&](size_t at, int count, hipStream_t ws, hipStream_t side, bool fork) -> int {
-		if (count <= 0) return CVX_OK;
-		/* Lanes per tile by the number of tiles walked together (round 5): a walk is a serial chain of probes per tile, and
-		 * what hides a probe's latency is other waves -- so few tiles get many lanes each (a probe then covers 64 / 32 / 16
-		 * path columns of a diagonal run instead of 8) until the walk has about six waves per SIMD, and only beyond that
-		 * is it issue-bound and eight lanes per tile the cheapest.  Measured against round 4's rule (one wave per tile below
-		 * 4 096 tiles, eight lanes from there on): C5 mix, 4 096 tiles of 100 kb, walk 39.5 ms at 8 lanes = 512 waves on 1 024
-		 * SIMDs, 25.9 at 16, 21.6 at 32, 19.4 at 64; ONT mix at 49 152 tiles in one walk 7.6 ms at 8, 6.0 at 16; the PacBio
-		 * bench (49 152 tiles): the walk alone 7.7 ms at 8 and 8.4 at 16, the pipelined step 114.4-114.9 against 113.9-114.1 ms
-		 * (profiles/r05_ab_bt_group.txt). */
-		const int auto_group = count <= 6144 ? 64 : count <= 12288 ? 32 : count <= 49152 ? 16 : 8;
-		if (h->bt_group < 0 ? n_walk < 4096 : (h->bt_group == 0 && auto_group == 64)) {
-			HIP_TRY(launch_backtrack(ba, b->d_lists.p + at, count, 64, ws));
-		} else if (h->bt_group > 0) {
-			HIP_TRY(launch_backtrack(ba, b->d_lists.p + at, count, h->bt_group, ws));
-		} else if (h->bt_group == 0 && auto_group >= 32) {
-			HIP_TRY(launch_backtrack(ba, b->d_lists.p + at, count, auto_group, ws));
-		} else {
-			const int bulk = h->bt_group < 0 ? 8 : auto_group;      /* 8 or 16; the much-longer-than-average reads at 32 */
-			const TileIn *tin = b->tin();
-			const uint64_t mean_h = b->n_rows / (uint64_t) std::max(n, 1);
-			int n_long = 0;
-			while (n_long < count && (uint64_t) tin[(size_t) lists[at + (size_t) n_long]].H > 3 * mean_h) n_long++;
-			if (n_long > 0 && fork) {
-				HIP_TRY(hipEventRecord(b->ev_bt0, ws));
-				HIP_TRY(hipStreamWaitEvent(side, b->ev_bt0, 0));
-				HIP_TRY(launch_backtrack(ba, b->d_lists.p + at, n_long, 32, side));
-				HIP_TRY(hipEventRecord(b->ev_bt1, side));
-			} else if (n_long > 0) {
-				HIP_TRY(launch_backtrack(ba, b->d_lists.p + at, n_long, 32, ws));
-			}
-			HIP_TRY(launch_backtrack(ba, b->d_lists.p + at + n_long, count - n_long, bulk, ws));
-			if (n_long > 0 && fork) HIP_TRY(hipStreamWaitEvent(ws, b->ev_bt1, 0));
-		}
-		return CVX_OK;
-	};
-	/* Several fill classes (ONT mix: chained retries, M = 4, M = 3; C5): each class is walked right behind its own fill on
-	 * that fill's stream.  The launch of such a batch lasts as long as its longest dependency chain, and while the last
-	 * chains finish on a few waves the device has issue slots to spare: the other classes' walks run there instead of
-	 * behind everything (CVX_TUNE_BT_PER_CLASS=0: one walk behind all fills, as a batch of one class has it anyway). */
-	static const bool bt_per_class_env = !(getenv("CVX_TUNE_BT_PER_CLASS") && atoi(getenv("CVX_TUNE_BT_PER_CLASS")) == 0);
-	/* Only where the walk is issue-bound (>= 4096 tiles; measured, r04c: ONT mix 60 000 tiles 57.2 -> 56.0 ms, 24 000 tiles
-	 * 35.3 -> 34.2, C5 mix 6 144 tiles 397 -> 369 ms); a small batch's one-wave-per-tile walks are latency-bound chains that
-	 * gain nothing from starting early and cost the fills still running (C5 mix 2 048 tiles: 183.6 -> 187.2 ms). */
-	const bool per_class = bt_per_class_env && launch_tiles.size() > 1 && !h->overlap_post && n_walk >= 4096;
-	int launches = 0;
-	/* fill launches go round-robin over the two aux streams and the main stream itself (which has
-	 * nothing else to do until they are all done): three classes side by side */
-	/* (the `post` stream carries a fill class too unless the post-fill overlap experiment owns it) */
-	hipStream_t fill_streams[kAuxStreams + 2];
-	int n_fill_streams = 0;
-	/* (order: first side stream, post, main -- the assignment of rounds 2-4 for up to three classes -- and the second side stream
-	 * only for a fourth class, i.e. with gangs.  Which class rides on which stream is not neutral: with the three whole-tile
-	 * classes of the C5 mix on side / side / post instead of side / post / main the same batch takes 181 or 236 ms depending on the
-	 * handle, on side / post / main 194 every time: gpurun_out r05u, profiles/r05_fill_stream_order.txt) */
-	fill_streams[n_fill_streams++] = S_aux[0];
-	if (!h->overlap_post) fill_streams[n_fill_streams++] = S_post;
-	fill_streams[n_fill_streams++] = st;
-	for (int i = 1; i < kAuxStreams; ++i) fill_streams[n_fill_streams++] = S_aux[i];
-	auto begin_launch = [&](hipStream_t ls) -> int {
-		while (b->lev.size() < (size_t) (launches + 1) * 4) {
-			hipEvent_t e;
-			HIP_TRY(hipEventCreate(&e));
-			b->lev.push_back(e);
-		}
+	kernel_args(h, b, hp.n_chained ? reinterpret_cast<const ChainBlk *>(b->d_chain.p + sch.chain_blk_off) : nullptr, fa, ba);
+	static_assert(kAuxStreams == 2, "StreamSlot names two side streams");
+	hipStream_t fill_streams[kStreamSlots];
+	fill_streams[kOnSide0] = S_aux[0]; fill_streams[kOnPost] = S_post; fill_streams[kOnMain] = st; fill_streams[kOnSide1] = S_aux[1];
+	const int launches = (int) sch.launches.size();
+	while (b->lev.size() < (size_t) launches * kLevPerLaunch) {
+		hipEvent_t e;
+		HIP_TRY(hipEventCreate(&e));
+		b->lev.push_back(e);
+	}
+	for (int i = 0; i < launches; ++i) {
+		const FillLaunch &L = sch.launches[(size_t) i];
+		const hipStream_t ls = fill_streams[L.stream];
+		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		const bool wrap = L.wrap != 0;
+		b->launches.push_back(L.info);
 		HIP_TRY(hipStreamWaitEvent(ls, b->ev[4], 0));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4], ls));
-		return CVX_OK;
-	};
-	/* closes launch number `launches` on its stream: the class's own walk (per_class), then the event everything after waits for */
-	auto end_launch = [&](hipStream_t ls) -> int {
-		if (per_class) RC_TRY(walk_list(bt_seg[(size_t) launches].first, bt_seg[(size_t) launches].second, ls, ls, false));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 3], ls));
-		launches++;
-		return CVX_OK;
-	};
-	/* chained tiles first (their dependency chains are the longest thing in a batch): the row-block
-	 * tasks of a class, then the per-tile reduction of the block results */
-	for (size_t c = 0; c < hp.chain_tasks.size(); ++c) {
-		if (hp.chain_tasks[c].empty()) continue;
-		const int m = kChainClasses[c / 2];
-		launch_stats(hp.chain_tiles[c], m, (int) hp.chain_tasks[c].size(), (int) (c & 1), CVX_LAUNCH_CHAINED);     /* `waves` = row-block tasks */
-		hipStream_t ls = fill_streams[launches % n_fill_streams];
-		RC_TRY(begin_launch(ls));
-		FillArgs a = fill_args(nullptr, (int) hp.chain_tasks[c].size());
-		a.tasks = reinterpret_cast<const ChainTask *>(b->d_chain.p + chain_task_off[c]);
-		a.chain_ticket = b->d_counters.p + 8 + (int) c;
-		a.bnd = b->d_bnd.p;
-		a.bnd_epoch = b->bnd_epoch;
-		a.chain_prio = (h->tune_chain_prio >= 0) ? h->tune_chain_prio : 1;
-		a.chain_out = b->d_chain_out.p;
-		/* tasks are dispatched in order, long before their turn; resident tasks beyond the ones that can
-		 * actually run only poll.  Unused dynamic LDS caps the residency at ~1.5x the blocks that are
-		 * live at one time (need / rows-per-block per tile, + slack). */
-		uint64_t live = 0;
-		for (int32_t ti : hp.chain_tiles[c]) live += (uint64_t) b->plan()[(size_t) ti].need / (uint64_t) (64 * m + kChainChunk) + 2;
-		const uint64_t resident = std::min<uint64_t>(8192, std::max<uint64_t>(768, live + live / 2 + 256));
-		const size_t per_cu = (size_t) ((resident + (uint64_t) h->num_cus - 1) / (uint64_t) h->num_cus);
-		size_t pad_lds = per_cu >= 32 ? 0 : (size_t) (160 * 1024) / per_cu - 4096;
-		pad_lds = std::min<size_t>(pad_lds, 60 * 1024) / 256 * 256;
-		/* The padding is LDS the ring classes of the same batch cannot use: a handful of chained retries among a thousand whole
-		 * tiles (ngmlr's own launches: 10-40 chained tiles, resident = 768 tasks = 3 per CU at 50 KB each) held 150 of a CU's
-		 * 160 KB for their 7 ms, and the M = 3 / M = 4 classes -- 4-5 KB per wave -- crawled until they were gone: a launch's
-		 * fill was the SUM of the chained class and the widest ring class (18.6 = 7.0 + 11.7 ms, profiles/r06_e2e_launch_trace.txt).
-		 * Beside ring classes the cap may hold tune_chain_lds_kb per CU; more tasks than can run then sit in their back-off sleep. */
-		bool rings_beside = false;
-		for (size_t rc_ = 0; rc_ < cls.size(); ++rc_) rings_beside = rings_beside || !cls[rc_].empty();
-		if (rings_beside && h->tune_chain_lds_kb > 0 && per_cu > 0 && per_cu < 32) {
-			const size_t budget = (size_t) h->tune_chain_lds_kb * 1024 / per_cu;
-			const size_t capped = budget > 4096 ? (budget - 4096) / 256 * 256 : 0;
-			pad_lds = std::min(pad_lds, capped);
+		HIP_TRY(hipEventRecord(le[kLevStart], ls));
+		FillArgs a = fa;
+		a.chain_prio = L.prio;
+		if (L.kind == CVX_LAUNCH_CHAINED) {
+			a.list_n = L.count;
+			a.tasks = reinterpret_cast<const ChainTask *>(b->d_chain.p + sch.chain_task_off[L.slot]);
+			a.chain_ticket = b->d_counters.p + 8 + L.slot;
+			a.bnd = b->d_bnd.p;
+			a.bnd_epoch = b->bnd_epoch;
+			a.chain_out = b->d_chain_out.p;
+			HIP_TRY(launch_fill(L.m, 1, wrap, kModeChain, a, L.pad_lds, ls));
+			HIP_TRY(launch_chain_reduce(reinterpret_cast<const int32_t *>(b->d_chain.p + sch.chain_tile_off[L.slot]), L.info.n_tiles,
+					b->d_trun.p, b->d_chain_out.p, b->d_tout.p, ls));
+			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+		} else if (L.kind == CVX_LAUNCH_CATCH_ALL) {
+			a.list = b->d_lists.p + L.list_off;
+			a.list_n = L.count;
+			HIP_TRY(launch_fill_generic(a, h->sse_variant, b->d_gscratch.p, b->d_gscratch_off.p, ls));
+			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+		} else {
+			/* the very long tiles of the class, exact from the first step (flagged kPadRedo), before everything else */
+			a.list = b->d_lists.p + L.list_off;
+			a.list_n = L.n_direct;
+			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
+			a.list += L.n_direct;
+			a.list_n = L.count - L.n_direct;
+			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, a, 0, ls));
+			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+			/* exact-tracking pass over the tiles the two-phase pass flagged (usually none) */
+			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
 		}
-		HIP_TRY(launch_fill(m, 1, (c & 1) != 0, 2, a, pad_lds, ls));
-		HIP_TRY(launch_chain_reduce(reinterpret_cast<const int32_t *>(b->d_chain.p + chain_tile_off[c]), (int) hp.chain_tiles[c].size(),
-				b->d_trun.p, b->d_chain_out.p, b->d_tout.p, ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 1], ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 2], ls));
-		RC_TRY(end_launch(ls));
-	}
-	int ring_classes = 0;
-	for (size_t c = 0; c < cls.size(); ++c) ring_classes += cls[c].empty() ? 0 : 1;
-	bool widest = true;
-	for (int cc = (int) cls.size() - 1; cc >= 0; --cc) {
-		const size_t c = (size_t) cc;
-		if (cls[c].empty()) continue;
-		const KernelClass &kc = kClasses[c / 2];
-		const int wide_prio = (h->tune_wide_prio && widest && ring_classes > 1) ? h->tune_wide_prio : 0;
-		widest = false;
-		launch_stats(cls[c], kc.m, kc.gang, (int) (c & 1), kc.gang > 1 ? CVX_LAUNCH_GANG : CVX_LAUNCH_WHOLE);      /* `waves` = waves per tile (a gang's size) */
-		hipStream_t ls = fill_streams[launches % n_fill_streams];
-		RC_TRY(begin_launch(ls));
-		if (n_direct[c] > 0) {
-			/* the very long tiles of the class, exact from the first step (flagged above), before everything else */
-			FillArgs ad = fill_args(b->d_lists.p + seg_begin[c], n_direct[c]);
-			ad.chain_prio = kc.gang > 1 ? h->tune_gang_prio : wide_prio;
-			HIP_TRY(launch_fill(kc.m, kc.gang, (c & 1) != 0, 1, ad, 0, ls));
-		}
-		FillArgs a = fill_args(b->d_lists.p + seg_begin[c] + n_direct[c], (int) cls[c].size() - n_direct[c]);
-		a.chain_prio = kc.gang > 1 ? h->tune_gang_prio : wide_prio;
-		if (a.list_n > 0) HIP_TRY(launch_fill(kc.m, kc.gang, (c & 1) != 0, 0, a, 0, ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 1], ls));
-		/* exact-tracking pass over the tiles the two-phase pass flagged (usually none) */
-		if (a.list_n > 0) HIP_TRY(launch_fill(kc.m, kc.gang, (c & 1) != 0, 1, a, 0, ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 2], ls));
-		RC_TRY(end_launch(ls));
-	}
-	if (!generic.empty()) {
-		launch_stats(generic, 0, 16, 1, CVX_LAUNCH_CATCH_ALL);
-		hipStream_t ls = fill_streams[launches % n_fill_streams];
-		RC_TRY(begin_launch(ls));
-		const FillArgs a = fill_args(b->d_lists.p + generic_begin, (int) generic.size());
-		HIP_TRY(launch_fill_generic(a, h->sse_variant, b->d_gscratch.p, b->d_gscratch_off.p, ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 1], ls));
-		HIP_TRY(hipEventRecord(b->lev[(size_t) launches * 4 + 2], ls));
-		RC_TRY(end_launch(ls));
+		HIP_TRY(hipEventRecord(le[kLevExact], ls));
+		if (sch.per_class) RC_TRY(issue_walk(b, ba, L.walk, L.bt_off, L.bt_count, ls, nullptr));
+		HIP_TRY(hipEventRecord(le[kLevWalked], ls));      /* what everything after the fills waits for */
 	}
 	/* Everything after the fills CAN run on its own stream, so that `main` goes straight on to the next
 	 * batch's fills while this batch's backtrack (one wave per tile) and small kernels run beside them. */
@@ -684,12 +514,11 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	 * turns it on. */
 	st = h->overlap_post ? S_post : S_main;
 	HIP_TRY(hipStreamWaitEvent(st, b->ev[4], 0));  /* also orders `post` behind the input copies when no fill was launched */
-	for (int i = 0; i < launches; ++i) HIP_TRY(hipStreamWaitEvent(st, b->lev[(size_t) i * 4 + 3], 0));
+	for (int i = 0; i < launches; ++i) HIP_TRY(hipStreamWaitEvent(st, b->lev[(size_t) i * kLevPerLaunch + kLevWalked], 0));
 	HIP_TRY(hipEventRecord(b->ev[2], st));
 
-	if (!per_class) {
-		RC_TRY(walk_list(bt_begin, n_walk, st, S_aux[0], true));
-	}
+	/* backtrack (unless every class was walked behind its own fill), device-side result records + prefix sums, ops compaction */
+	if (!sch.per_class) RC_TRY(issue_walk(b, ba, sch.walk, sch.bt_begin, sch.n_walk, st, S_aux[0]));
 	ResultRec *d_rec = reinterpret_cast<ResultRec *>(b->d_res.p);
 	BatchSummary *d_sum = reinterpret_cast<BatchSummary *>(b->d_res.p + (size_t) n * sizeof(ResultRec));
 	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
@@ -717,12 +546,12 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	const BatchSummary *s = b->summary();
 	b->ops_total = s->ops_total;
 	const int launches = b->timing.n_fill_launches;
-	for (int i = 0; i < launches; ++i) b->launches[(size_t) i].ms = ev_ms(b->lev[(size_t) i * 4], b->lev[(size_t) i * 4 + 1]);
+	for (int i = 0; i < launches; ++i) b->launches[(size_t) i].ms = ev_ms(b->lev[(size_t) i * kLevPerLaunch + kLevStart], b->lev[(size_t) i * kLevPerLaunch + kLevTwoPhase]);
 	b->timing.plan_ms = ev_ms(b->ev[0], b->ev[1]);
 	/* fill = until the last fill class has finished its exact pass; backtrack = what is left of the compute stage (when every
 	 * class is walked behind its own fill, the walks of the early classes lie inside `fill`: the two still add up) */
 	float fill_end = 0.0f;
-	for (int i = 0; i < launches; ++i) fill_end = std::max(fill_end, ev_ms(b->ev[4], b->lev[(size_t) i * 4 + 2]));
+	for (int i = 0; i < launches; ++i) fill_end = std::max(fill_end, ev_ms(b->ev[4], b->lev[(size_t) i * kLevPerLaunch + kLevExact]));
 	if (launches == 0) fill_end = ev_ms(b->ev[4], b->ev[2]);
 	b->timing.fill_ms = fill_end;
 	b->timing.backtrack_ms = std::max(0.0f, ev_ms(b->ev[4], b->ev[3]) - fill_end);
@@ -752,20 +581,13 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 		 * job submitted last, and returning only when those are done paces the caller -- it submits its next batch one
 		 * step later, so that exactly one corridor analysis runs beside each fill (beside a fill it takes most of the
 		 * fill's duration; two of them queued under one fill finish late and the next fill starts late: measured 150
-		 * instead of 124 ms per step with an event right behind the copy).  CVX_TUNE_OPS_EVENT=1 selects the event. */
+		 * instead of 124 ms per step with an event right behind the copy). */
 		HIP_TRY(hipMemcpyAsync(b->h_ops.p, b->d_dense.p, (size_t) b->ops_total * sizeof(uint32_t), hipMemcpyDeviceToHost, h->s_io));
 		/* Round 4 tried to drop the pacing for closed-form batches (their corridor analysis reads nothing: 2.3 ms alone): over
 		 * 3 steps of 24 576 tiles the event-only form measured the same, over the driver's 20 steps of 49 152 tiles it costs
 		 * 146.5 instead of 118.7 ms per step (gpurun_out/r04g/pacing.txt) -- the analysis is starved beside a fill whatever it
-		 * reads (70-100 ms), and two of them queued under one fill still delay the fill after next.  The stream wait stays;
-		 * CVX_TUNE_OPS_EVENT=1 selects the event. */
-		static const bool ops_event = getenv("CVX_TUNE_OPS_EVENT") && atoi(getenv("CVX_TUNE_OPS_EVENT")) != 0;
-		if (ops_event) {
-			HIP_TRY(hipEventRecord(b->ev_ops, h->s_io));
-			HIP_TRY(hipEventSynchronize(b->ev_ops));
-		} else {
-			HIP_TRY(hipStreamSynchronize(h->s_io));
-		}
+		 * reads (70-100 ms), and two of them queued under one fill still delay the fill after next.  The stream wait stays. */
+		HIP_TRY(hipStreamSynchronize(h->s_io));
 	}
 	b->have_ops = true;
 	return CVX_OK;

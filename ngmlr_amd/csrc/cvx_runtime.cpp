@@ -283,6 +283,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	c->max_matrix_mb = max_matrix_mb ? max_matrix_mb : 10000;
 	c->sse_variant = !fast_regime;
 	if (const char *e = getenv("CVX_TUNE_BT_GROUP")) c->bt_group = atoi(e);
+	if (const char *e = getenv("CVX_TUNE_BT_PER_CLASS")) c->bt_per_class = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_OVERLAP_POST")) c->overlap_post = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_SSE_VARIANT")) c->sse_variant = c->sse_variant || atoi(e) != 0;   /* test knob */
 	c->pack_threads = PackPool::get().size();      /* the process's shared pack threads (CVX_PACK_THREADS) */

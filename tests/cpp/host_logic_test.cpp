@@ -1,6 +1,7 @@
 // CPU test of the device-independent host logic (ngmlr_amd/csrc/cvx_host_logic.h): upload layout and
 // packing (ragged, empty and strided tiles, multi-threaded == single-threaded), kernel-class choice,
-// arena offsets and the LPT work lists.  Built with plain g++ by tests/test_host_logic_cpu.py.
+// arena offsets and the LPT work lists, and the compute stage's launch schedule (list contents, launch order, stream slots,
+// residency cap of chained classes, lanes of the backtrack walks).  Built with plain g++ by tests/test_host_logic_cpu.py.
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -328,6 +329,285 @@ int main() {
 		{ PlanTuning tn; tn.chain_m = 2; host_plan(1, &p, &in, rows.data(), tn, hl); }
 		CHECK(hl.n_chained == 1 && hl.trun[0].mnw == 2 && hl.trun[0].ring == 128);   // forced block height
 		CHECK(chain_class_for(175, true) == 0 && chain_class_for(4000, false) == 0); // 64-row blocks for every batch
+	}
+	// ---------------------------------------------------------------- the compute stage's launch schedule
+	{
+		struct Batch {
+			std::vector<TilePlan> plan; std::vector<TileIn> tin; uint64_t n_rows = 0;
+			void add(std::mt19937 &rng, int need, int H, int steps, uint32_t flags = 0) {
+				TilePlan p; memset(&p, 0, sizeof(p));
+				p.r0 = 0; p.rend = steps; p.need = need; p.flags = flags;
+				p.active = 1000 + rng() % 5000; p.cells = p.active + rng() % 100;     // (few values: LPT ties)
+				TileIn in; memset(&in, 0, sizeof(in));
+				in.H = H; in.W = H + 50;
+				plan.push_back(p); tin.push_back(in); n_rows += (uint64_t) H;
+			}
+			int n() const { return (int) plan.size(); }
+		};
+		struct Built { HostPlan hp; std::vector<int32_t> lists; ComputeSchedule s; };
+		auto build = [](const Batch &B, const RowDesc *rows, const PlanTuning &pt, const ScheduleTuning &st, Built &o) {
+			host_plan(B.n(), B.plan.data(), B.tin.data(), rows, pt, o.hp);
+			o.lists.assign((size_t) 2 * B.n() + 16, -1);
+			build_schedule(o.hp, B.plan.data(), B.tin.data(), B.n(), B.n_rows, 256, st, o.lists.data(), o.s);
+		};
+		// what the walk of `count` tiles gets under bt_group = 0, written out: 64 lanes up to 6 144 tiles, 32 up to 12 288, 16 up to 49 152, 8 beyond
+		auto lanes_by_count = [](int count) { return count <= 6144 ? 64 : count <= 12288 ? 32 : count <= 49152 ? 16 : 8; };
+		// the invariants of every schedule
+		auto check = [&](const Batch &B, const Built &o, const ScheduleTuning &st) {
+			const HostPlan &hp = o.hp;
+			const ComputeSchedule &s = o.s;
+			const int n = B.n();
+			std::vector<int> filled(n, 0), walked(n, 0);
+			static const int free_post[] = {kOnSide0, kOnPost, kOnMain, kOnSide1}, own_post[] = {kOnSide0, kOnMain, kOnSide1};
+			size_t fill_at = 0, bt_at = s.bt_begin;
+			int n_ring = 0, stage = 0, last_slot = -1;
+			for (const FillLaunch &L : s.launches) if (L.kind == CVX_LAUNCH_WHOLE || L.kind == CVX_LAUNCH_GANG) n_ring++;
+			bool first_ring = true;
+			for (size_t i = 0; i < s.launches.size(); ++i) {
+				const FillLaunch &L = s.launches[i];
+				// order: chained classes (ascending), whole-tile classes from the widest ring down, the catch-all kernel
+				const int stg = L.kind == CVX_LAUNCH_CHAINED ? 0 : L.kind == CVX_LAUNCH_CATCH_ALL ? 2 : 1;
+				CHECK(stg >= stage);
+				if (stg == stage && stg == 0) CHECK(L.slot > last_slot);
+				if (stg == stage && stg == 1) CHECK(L.slot < last_slot);
+				if (stg == stage && stg == 2) CHECK(!"one catch-all launch");
+				stage = stg; last_slot = L.slot;
+				CHECK(L.stream == (st.overlap_post ? own_post[i % 3] : free_post[i % 4]));
+				CHECK(L.tiles != nullptr && !L.tiles->empty());
+				uint64_t cells = 0;
+				for (int32_t t : *L.tiles) cells += B.plan[t].cells;
+				CHECK(L.info.kind == L.kind && L.info.n_tiles == (int) L.tiles->size() && L.info.cells == cells && L.info.slots_per_lane == L.m && L.info.wrap16 == L.wrap);
+				if (stg == 0) {
+					CHECK(L.tiles == &hp.chain_tiles[L.slot] && L.count == (int) hp.chain_tasks[L.slot].size() && L.info.waves == L.count);
+					CHECK(L.m == kChainClasses[L.slot / 2] && L.wrap == (L.slot & 1) && L.prio == (st.chain_prio >= 0 ? st.chain_prio : 1));
+					for (int32_t t : *L.tiles) filled[t]++;
+				} else {
+					// the fill lists lie back to back in front of the backtrack segments: classes from the narrowest ring up, then the catch-all list
+					CHECK(L.count == (int) L.tiles->size());
+					for (int q = 0; q < L.count; ++q) { const int32_t t = o.lists[L.list_off + q]; CHECK(t == (*L.tiles)[q]); filled[t]++; }
+					fill_at += (size_t) L.count;
+					if (stg == 1) {
+						const KernelClass &kc = kClasses[L.slot / 2];
+						CHECK(L.tiles == &hp.cls[L.slot] && L.m == kc.m && L.gang == kc.gang && L.wrap == (L.slot & 1) && L.info.waves == kc.gang);
+						CHECK(L.kind == (kc.gang > 1 ? CVX_LAUNCH_GANG : CVX_LAUNCH_WHOLE));
+						// wide_prio: the widest ring class only, and only beside another ring class; gangs have their own knob
+						CHECK(L.prio == (kc.gang > 1 ? st.gang_prio : (first_ring && n_ring > 1) ? st.wide_prio : 0));
+						first_ring = false;
+						// the direct-exact prefix: flagged, in LPT order, and everything behind it shorter
+						int reach = 0;
+						for (int32_t t : *L.tiles) if (st.exact_steps > 0 && hp.trun[t].nsteps >= st.exact_steps) reach++;
+						CHECK(L.n_direct == ((reach >= 1 && reach <= kExactDirectMaxTiles) ? reach : 0));
+						for (int q = 0; q < L.count; ++q) {
+							const int32_t t = (*L.tiles)[q];
+							CHECK((hp.tout[t].pad == kPadRedo) == (q < L.n_direct));
+							if (L.n_direct) CHECK((hp.trun[t].nsteps >= st.exact_steps) == (q < L.n_direct));
+							if (q > 0 && q != L.n_direct) {
+								const uint64_t x = B.plan[(*L.tiles)[q - 1]].active, y = B.plan[t].active;
+								if (!(x > y || (x == y && (*L.tiles)[q - 1] < t))) { CHECK(!"LPT order on either side of the prefix"); break; }
+							}
+						}
+					} else {
+						CHECK(L.tiles == &hp.generic && L.m == 0 && L.info.waves == 16 && L.wrap == 1 && L.prio == 0 && L.n_direct == 0);
+					}
+				}
+				// one backtrack segment per launch, in launch order, back to back; H >> 5 never increases, ties keep the class's order
+				CHECK(L.bt_off == bt_at && L.bt_count == (int) L.tiles->size());
+				std::vector<int> pos(n, -1);
+				for (size_t q = 0; q < L.tiles->size(); ++q) pos[(*L.tiles)[q]] = (int) q;
+				for (int q = 0; q < L.bt_count; ++q) {
+					const int32_t t = o.lists[L.bt_off + q];
+					if (t < 0 || t >= n || pos[t] < 0) { CHECK(!"segment holds the launch's tiles"); break; }
+					walked[t]++;
+					if (q > 0) {
+						const int32_t u = o.lists[L.bt_off + q - 1];
+						const int ku = B.tin[u].H >> 5, kt = B.tin[t].H >> 5;
+						if (!(ku > kt || (ku == kt && pos[u] < pos[t]))) { CHECK(!"backtrack order"); break; }
+					}
+				}
+				bt_at += (size_t) L.bt_count;
+				if (s.per_class) CHECK(L.walk.bulk_lanes == (st.bt_group > 0 ? st.bt_group : st.bt_group < 0 ? 8 : lanes_by_count(L.bt_count)));
+			}
+			CHECK(fill_at == s.bt_begin && bt_at == s.n_listed && s.n_walk == (int) (s.n_listed - s.bt_begin) && s.n_listed <= (size_t) 2 * n);
+			for (int i = 0; i < n; ++i) {
+				const int want = hp.trun[i].skip ? 0 : 1;
+				if (filled[i] != want || walked[i] != want) { CHECK(!"every computed tile once in the fill lists and once in the backtrack segments"); break; }
+				if (hp.tout[i].pad == kPadRedo && hp.trun[i].nsteps < st.exact_steps) CHECK(!"only direct-exact tiles are flagged");
+			}
+			CHECK(s.per_class == (s.launches.size() > 1 && s.n_walk >= 4096 && !st.overlap_post && st.bt_per_class));
+			if (!s.per_class) CHECK(s.walk.bulk_lanes == (st.bt_group > 0 ? st.bt_group : st.bt_group < 0 ? (s.n_walk < 4096 ? 64 : 8) : lanes_by_count(s.n_walk)));
+			// the chain upload: tasks of every class, the block table, the tile lists (8-byte aligned), nothing else
+			if (hp.n_chained) {
+				size_t at = 0;
+				for (size_t c = 0; c < hp.chain_tasks.size(); ++c) { CHECK(s.chain_task_off[c] == at); at += hp.chain_tasks[c].size() * sizeof(ChainTask); }
+				CHECK(s.chain_blk_off == at); at += hp.chain_blk.size() * sizeof(ChainBlk);
+				for (size_t c = 0; c < hp.chain_tiles.size(); ++c) { CHECK(s.chain_tile_off[c] == at && at % 8 == 0); at += (hp.chain_tiles[c].size() * 4 + 7) / 8 * 8; }
+				CHECK(s.chain_bytes == at);
+			} else CHECK(s.chain_bytes == 0);
+		};
+		// rows of a slope-1 band no ring holds (~1050 live rows): shared by every chained tile of the batches below
+		const int cH = 3001, cw = 2100;
+		std::vector<RowDesc> crow((size_t) cH);
+		for (int y = 0; y < cH; ++y) { crow[(size_t) y].off = y - cw / 2; crow[(size_t) y].len = cw; }
+		// a mixed batch of `count` tiles: four ring classes, int16-run tiles, irregular tiles, skipped tiles, `chained` wide tiles
+		auto mixed = [&](int count, int chained, Batch &B) {
+			static const int needs[] = {40, 100, 150, 150, 150, 250};
+			for (int i = 0; i < count; ++i) {
+				uint32_t fl = 0;
+				if (i % 97 == 5) fl |= kPlanEmpty;
+				if (i % 89 == 7) fl |= kPlanTooLarge;
+				if (i % 53 == 9) fl |= kPlanIrregular;
+				if (i % 31 == 3) fl |= kPlanWrap16;
+				// (a few reads much longer than the rest; not in a small batch, which would chain them)
+				const int H = (count >= kSmallBatchTiles && i % 211 == 0) ? 60000 + (int) (rng() % 30000) : 200 + (int) (rng() % 12000);
+				if (i < chained) B.add(rng, 1054, cH, 2 * cH);
+				else B.add(rng, needs[i % 6], H, 2 * H + 100, fl);
+			}
+		};
+		for (const int count : {600, 4200, 6300, 12400, 49300}) {
+			for (int variant = 0; variant < 4; ++variant) {
+				Batch B;
+				mixed(count, 5, B);
+				ScheduleTuning st;
+				if (variant == 1) st.overlap_post = true;
+				if (variant == 2) { st.bt_group = -1; st.wide_prio = 2; st.chain_prio = 0; }
+				if (variant == 3) { st.bt_per_class = false; st.bt_group = 8; st.exact_steps = 0; }
+				Built o;
+				build(B, crow.data(), PlanTuning(), st, o);
+				check(B, o, st);
+				// chained, M = 4, 3, 2, 1 in both run forms where populated, the catch-all last
+				CHECK(o.hp.n_chained == 5 && !o.hp.generic.empty() && o.s.launches.size() >= 6);
+				CHECK(o.s.launches.front().kind == CVX_LAUNCH_CHAINED && o.s.launches.back().kind == CVX_LAUNCH_CATCH_ALL);
+				CHECK(o.s.per_class == (count >= 4200 && variant != 1 && variant != 3));
+				// live = 5 tiles x (1054 / (64 + kChainChunk) + 2) = 75 blocks: 768 resident tasks, 3 per CU; beside ring classes 48 KB per CU
+				CHECK(o.s.launches.front().pad_lds == 12288);
+			}
+		}
+		// the direct-exact prefix: 1 to kExactDirectMaxTiles tiles of a class reach exact_steps
+		for (const int reach : {0, 1, kExactDirectMaxTiles, kExactDirectMaxTiles + 1}) {
+			Batch B;
+			for (int i = 0; i < kExactDirectMaxTiles + 600; ++i) {
+				const bool lng = (i * 7 % (kExactDirectMaxTiles + 600)) < reach;      // scattered through the class
+				B.add(rng, 150, 3000, lng ? kExactDirectSteps + (int) (rng() % 3) : kExactDirectSteps - 1 - (int) (rng() % 100));
+			}
+			for (const int steps : {kExactDirectSteps, 0}) {
+				ScheduleTuning st;
+				st.exact_steps = steps;
+				Built o;
+				build(B, nullptr, PlanTuning(), st, o);
+				check(B, o, st);
+				CHECK(o.s.launches.size() == 1 && o.s.launches[0].count == B.n());
+				CHECK(o.s.launches[0].n_direct == ((steps > 0 && reach >= 1 && reach <= kExactDirectMaxTiles) ? reach : 0));
+				int flagged = 0;
+				for (const TileOut &t : o.hp.tout) flagged += t.pad == kPadRedo;
+				CHECK(flagged == o.s.launches[0].n_direct);
+			}
+		}
+		// launch order, stream slots and priorities of batches of 1, 3 and 4 ring classes (M = 3; 3, 2, 1; 4, 3, 2, 1)
+		for (const int classes : {1, 3, 4}) {
+			for (const bool overlap : {false, true}) {
+				static const int needs[] = {150, 100, 40, 250};
+				Batch B;
+				for (int i = 0; i < 400; ++i) B.add(rng, needs[i % classes], 1000 + (int) (rng() % 100), 2500);
+				ScheduleTuning st;
+				st.overlap_post = overlap;
+				st.wide_prio = 2;
+				Built o;
+				build(B, nullptr, PlanTuning(), st, o);
+				check(B, o, st);
+				const std::vector<FillLaunch> &ls = o.s.launches;
+				CHECK((int) ls.size() == classes);
+				static const int m3[] = {3, 2, 1}, m4[] = {4, 3, 2, 1};
+				static const int slots[] = {kOnSide0, kOnPost, kOnMain, kOnSide1}, slots_overlap[] = {kOnSide0, kOnMain, kOnSide1, kOnSide0};
+				for (int i = 0; i < (int) ls.size() && i < classes; ++i) {
+					CHECK(ls[i].m == (classes == 1 ? 3 : classes == 3 ? m3[i] : m4[i]) && ls[i].kind == CVX_LAUNCH_WHOLE);
+					CHECK(ls[i].stream == (overlap ? slots_overlap[i] : slots[i]));
+					CHECK(ls[i].prio == ((i == 0 && classes > 1) ? 2 : 0));
+				}
+				CHECK(!o.s.per_class);
+			}
+		}
+		// a gang class is the widest ring: it takes gang_prio, and wide_prio goes to nobody
+		{
+			Batch B;
+			for (int i = 0; i < 300; ++i) B.add(rng, (i % 3 == 0) ? 300 : (i % 3 == 1) ? 150 : 40, 1000, 2500);
+			ScheduleTuning st;
+			st.gang_prio = 1;
+			Built o;
+			build(B, nullptr, PlanTuning(), st, o);
+			check(B, o, st);
+			CHECK(o.s.launches.size() == 3 && o.s.launches[0].kind == CVX_LAUNCH_GANG && o.s.launches[0].gang == 2 && o.s.launches[0].prio == 1);
+			CHECK(o.s.launches[1].prio == 0 && o.s.launches[2].prio == 0);
+		}
+		// per_class exactly when: more than one launch, n_walk >= 4096, no overlap_post, the knob not 0
+		for (const int count : {4095, 4096, 4097}) {
+			for (const int classes : {1, 2}) {
+				Batch B;
+				for (int i = 0; i < count; ++i) B.add(rng, (classes == 2 && (i & 1)) ? 100 : 150, 1000, 2500);
+				for (int variant = 0; variant < 3; ++variant) {
+					ScheduleTuning st;
+					st.overlap_post = variant == 1;
+					st.bt_per_class = variant != 2;
+					Built o;
+					build(B, nullptr, PlanTuning(), st, o);
+					check(B, o, st);
+					CHECK(o.s.n_walk == count && o.s.per_class == (classes == 2 && count >= 4096 && variant == 0));
+				}
+			}
+		}
+		// chain_pad_lds on 256 CUs.  Expected values worked out from the rule as stage_compute had it inline:
+		//   resident = min(8192, max(768, live * 3 / 2 + 256)), per_cu = ceil(resident / CUs), pad = (160 KB / per_cu - 4 KB, at most 60 KB) in
+		//   256-byte units, 0 from 32 tasks per CU on; beside ring classes at most (chain_lds_kb KB / per_cu - 4 KB)
+		CHECK(chain_pad_lds(10, 256, 0, true) == 50432 && chain_pad_lds(10, 256, 48, false) == 50432 && chain_pad_lds(10, 256, 48, true) == 12288);        // 3 per CU
+		CHECK(chain_pad_lds(400, 256, 0, true) == 36864 && chain_pad_lds(400, 256, 48, false) == 36864 && chain_pad_lds(400, 256, 48, true) == 8192);       // 4 per CU
+		CHECK(chain_pad_lds(1000, 256, 0, true) == 19200 && chain_pad_lds(1000, 256, 48, false) == 19200 && chain_pad_lds(1000, 256, 48, true) == 2816);    // 7 per CU
+		CHECK(chain_pad_lds(4000, 256, 0, true) == 2304 && chain_pad_lds(4000, 256, 48, false) == 2304 && chain_pad_lds(4000, 256, 48, true) == 0);         // 25 per CU: 48 KB / 25 < 4 KB
+		CHECK(chain_pad_lds(6000, 256, 0, true) == 0 && chain_pad_lds(6000, 256, 48, true) == 0);                                                           // 32 per CU: no padding
+		CHECK(chain_pad_lds(10, 1024, 0, true) == 61440 && chain_pad_lds(10, 1024, 48, true) == 45056);                                                     // 1 per CU: the 60 KB limit
+		// ... and as the schedule applies it: chained tiles alone (no ring class beside them), and with the cap switched off
+		{
+			Batch B;
+			mixed(5, 5, B);
+			Built o;
+			build(B, crow.data(), PlanTuning(), ScheduleTuning(), o);
+			check(B, o, ScheduleTuning());
+			CHECK(o.s.launches.size() == 1 && o.s.launches[0].pad_lds == 50432 && o.s.launches[0].prio == 1);
+			Batch B2;
+			mixed(300, 5, B2);
+			ScheduleTuning st;
+			st.chain_lds_kb = 0;
+			build(B2, crow.data(), PlanTuning(), st, o);
+			check(B2, o, st);
+			CHECK(o.s.launches[0].kind == CVX_LAUNCH_CHAINED && o.s.launches[0].pad_lds == 50432);
+		}
+		// the walk plan at each threshold and one either side
+		{
+			const int big = 49154;
+			std::vector<TileIn> tin((size_t) big);
+			std::vector<int32_t> list((size_t) big);
+			for (int i = 0; i < big; ++i) { memset(&tin[(size_t) i], 0, sizeof(TileIn)); tin[(size_t) i].H = 1000; list[(size_t) i] = big - 1 - i; }
+			const uint64_t mean = 1000;
+			// the head: three reads of more than 3 x the mean, then one of exactly 3 x
+			tin[(size_t) list[0]].H = 9000; tin[(size_t) list[1]].H = 3002; tin[(size_t) list[2]].H = 3001; tin[(size_t) list[3]].H = 3000;
+			struct Want { int count, lanes, n_long; };
+			static const Want by_count[] = { {1, 64, 0}, {6143, 64, 0}, {6144, 64, 0}, {6145, 32, 0}, {12287, 32, 0}, {12288, 32, 0}, {12289, 16, 3},
+					{49151, 16, 3}, {49152, 16, 3}, {49153, 8, 3}, {49154, 8, 3} };
+			for (const Want &w : by_count) {
+				const WalkPlan a = walk_plan(w.count, w.count, 0, mean, list.data(), tin.data());
+				CHECK(a.bulk_lanes == w.lanes && a.n_long == w.n_long && a.long_lanes == 32);
+				// forced groups: that many lanes for every tile, no 32-lane head
+				const WalkPlan f8 = walk_plan(w.count, w.count, 8, mean, list.data(), tin.data()), f64 = walk_plan(w.count, w.count, 64, mean, list.data(), tin.data());
+				CHECK(f8.bulk_lanes == 8 && f8.n_long == 0 && f64.bulk_lanes == 64 && f64.n_long == 0);
+				// -1: by the tiles of the whole batch, 64 lanes below 4 096 and 8 (+ the head) from there on, whatever this walk's own count
+				const WalkPlan small = walk_plan(w.count, 4095, -1, mean, list.data(), tin.data()), large = walk_plan(w.count, 4096, -1, mean, list.data(), tin.data());
+				CHECK(small.bulk_lanes == 64 && small.n_long == 0 && large.bulk_lanes == 8 && large.n_long == std::min(3, w.count));
+			}
+			CHECK(walk_plan(20000, 4097, -1, mean, list.data(), tin.data()).bulk_lanes == 8);
+			// the lanes follow the walk's own count, not the batch's (a class walked behind its own fill)
+			CHECK(walk_plan(5000, 60000, 0, mean, list.data(), tin.data()).bulk_lanes == 64 && walk_plan(5000, 60000, 0, mean, list.data(), tin.data()).n_long == 0);
+			// a head that is the whole list; a mean that makes nobody long
+			CHECK(walk_plan(2, 50000, -1, mean, list.data(), tin.data()).n_long == 2);
+			CHECK(walk_plan(20000, 20000, 0, 3000, list.data(), tin.data()).n_long == 0 && walk_plan(20000, 20000, 0, 2999, list.data(), tin.data()).n_long == 1);
+		}
 	}
 	printf(fails ? "host_logic_test: %d FAILED\n" : "host_logic_test: ok\n", fails);
 	return fails ? 1 : 0;

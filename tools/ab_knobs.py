@@ -86,8 +86,8 @@ def main():
                     st or "default", w, len(tiles), best.plan_ms, best.fill_ms, best.backtrack_ms, best.total_ms, bases / best.total_ms * 3.6e-3,
                     best.n_tiles_redone, int((rec["status"] == 0).sum()), diff), flush=True)
                 for li in b.launches():
-                    print("        M=%d tasks/waves=%d wrap=%d: %6d tiles %8.2f ms %7.0f G cells/s" % (
-                        li["slots_per_lane"], li["waves"], li["wrap16"], li["n_tiles"], li["ms"], li["cells"] / max(li["ms"], 1e-6) * 1e-6), flush=True)
+                    print("        M=%d tasks/waves=%d wrap=%d kind=%d: %6d tiles %12d cells %8.2f ms %7.0f G cells/s" % (
+                        li["slots_per_lane"], li["waves"], li["wrap16"], li["kind"], li["n_tiles"], li["cells"], li["ms"], li["cells"] / max(li["ms"], 1e-6) * 1e-6), flush=True)
                 print("        digest of all records: %s" % hashlib.blake2b(b"".join(per), digest_size=8).hexdigest(), flush=True)
             finally:
                 b.free()
