@@ -30,6 +30,7 @@
  * cvx_tile.corridor_kind      the corridor builders' closed forms, rows generated on the device
  *                             src/AlignmentBuffer.cpp:68-197 (a8: the builders stay in ngmlr, their output need not travel)
  * cvx_format_alignment        convertCigar + N-clip flags    src/ConvexAlignFast.cpp:112-333,493-528
+ * CVX_CREATE_SCALAR_TWIN      Convex::ConvexAlign (--nosse)  src/ConvexAlign.cpp:418-610 (a9), src/AlignmentBuffer.h:345-353
  * cvx_job_text                the same for a whole finished job, on the device (next-row f3)
  * cvx_job_nm_profile          addPosition / nmPerPosition    src/ConvexAlignFast.cpp:76-98,186-269, on the device
  * cvx_job_nm_regions / cvx_nm_regions_ops / cvx_nm_regions_host  the peak finder over that profile at the top of
@@ -238,7 +239,21 @@ int cvx_create(int device_id, const cvx_params *params, uint64_t max_matrix_mb, 
  * cvx_genome_decode) from a thread that blocks in them -- its stream gets the device's highest priority, so that a 0.3 ms scoring
  * kernel does not queue behind a 10 ms fill of an aligning handle in the same process.  MEASURED AND OFF: inside ngmlr the run got
  * slower with it (profiles/r06_e2e_service_prio.txt); the flag is recorded in the handle, the priority applies only with CVX_SERVICE_PRIO=1. */
-enum { CVX_CREATE_SERVICE = 1 };
+enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2 };
+/* CVX_CREATE_SCALAR_TWIN (additive, ABI 9): the handle reproduces Convex::ConvexAlign, the scalar aligner ngmlr's --nosse selects
+ * (src/ConvexAlign.cpp:418-610, bound at src/AlignmentBuffer.h:345-353), instead of Convex::ConvexAlignFast:
+ *   - the scalar recurrence for ANY scoring (a default handle reproduces the SSE path, which differs from it outside
+ *     gap_open + gap_extend_min < mismatch); on tiles without an 'x' in the reference window and scoring inside that regime the
+ *     two give the same results;
+ *   - a mismatch against an 'x' of the reference window (the padding of a window that reaches past its contig,
+ *     src/SequenceProvider.cpp:610-613) costs mismatch * 100.0f, one binary32 multiply (src/ConvexAlign.cpp:513).  The compare of
+ *     read and reference characters is the raw byte compare: 'x' against 'x' is a match, 'X' is an ordinary character;
+ *   - no matrix-size cap: AlignmentMatrix::prepare allocates whatever is asked, so max_matrix_mb is ignored and no tile is
+ *     CVX_TILE_TOO_LARGE because of it (the library's own limits and their statuses remain);
+ *   - the text stage of the handle's jobs (cvx_job_text, cvx_job_text_all) has no N-clip block and reports cigar_op_count and
+ *     sv_type as CVX_NOT_WRITTEN: the twin never stores Align::cigarOpCount / Align::svType, a caller keeps what it had there.
+ * The twin's binaryCigar has a fixed 200 000 entries and its MD buffer never grows (src/ConvexAlign.cpp:36,51): past those the
+ * reference's behaviour is undefined; the library returns its normal result there. */
 /* ABI 7: which of the process-wide settings above this process really got (a host that initialised HIP before
  * the library was loaded gets neither, and its mixed launches run their fill classes one after the other).
  *   hw_queues_env             GPU_MAX_HW_QUEUES as the process's environment has it now (0: unset)
@@ -503,6 +518,19 @@ typedef struct {
 	int32_t cigar_len, md_len;/* full lengths (text is truncated to the given capacity) */
 } cvx_alignment_text;
 
+/* cvx_format_alignment_ex / cvx_format_batch_ex (additive, ABI 9): the same with flags.  CVX_FORMAT_SCALAR_TWIN: the text stage
+ * of Convex::ConvexAlign -- CIGAR, MD, NM, identity, positions and nmPerPosition as above, no N-clip block (bit 0x1 is never
+ * set), cigar_op_count = sv_type = CVX_NOT_WRITTEN (-1; neither is a value the fast form can produce).
+ * A caller that goes on to the SAM helpers (cvx_sam_record.sv_type / cigar_op_count) must put its own values there first --
+ * what it held in Align::svType / Align::cigarOpCount before the alignment, as ngmlr does under --nosse: handed on as they
+ * are, -1 suppresses the SV:i tag and leaves the BAM long-CIGAR fix without its op count. */
+enum { CVX_FORMAT_SCALAR_TWIN = 1 };
+enum { CVX_NOT_WRITTEN = -1 };
+int cvx_format_alignment_ex(const cvx_result *r, const uint32_t *ops_arena,
+		const char *ref, int32_t ref_len, int32_t qry_len,
+		int32_t ext_qstart, int32_t ext_qend,
+		char *cigar, int32_t cigar_cap, char *md, int32_t md_cap,
+		int32_t *nm_triples, int32_t nm_cap, uint32_t flags, cvx_alignment_text *out);
 int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_arena,
 		const char *ref, int32_t ref_len, int32_t qry_len,
 		int32_t ext_qstart, int32_t ext_qend,
@@ -524,6 +552,9 @@ typedef struct {
 int cvx_format_batch(int32_t n, const cvx_result *results, const uint32_t *ops_arena,
 		const cvx_tile *tiles, const cvx_text_buffers *bufs, cvx_alignment_text *out,
 		int32_t n_threads);
+int cvx_format_batch_ex(int32_t n, const cvx_result *results, const uint32_t *ops_arena,
+		const cvx_tile *tiles, const cvx_text_buffers *bufs, cvx_alignment_text *out,
+		int32_t n_threads, uint32_t flags);
 
 /* The same on the device: CIGAR, MD and the scalar fields of every tile of a finished
  * job, from the ops and sequences still resident in HBM -- one launch instead of a host core per ~70 Mbp/s.

@@ -23,14 +23,20 @@ DEFAULT_SCORING = dict(match=2.0, mismatch=-5.0, gap_open=-5.0, gap_extend=-5.0,
 
 
 class ConvexAlignHip:
-    def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, **scoring):
+    def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, scalar_twin: bool = False, **scoring):
+        """scalar_twin: the handle reproduces Convex::ConvexAlign (ngmlr --nosse) instead of Convex::ConvexAlignFast
+        (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h); the host text helpers of its batches follow."""
         self.lib = capi.load(lib_path)
+        self.scalar_twin = bool(scalar_twin)
         sc = dict(DEFAULT_SCORING)
         sc.update(scoring)
         self.params = capi.CvxParams(sc["match"], sc["mismatch"], sc["gap_open"], sc["gap_extend"],
                                      sc["gap_extend_min"], sc["gap_decay"])
         self.h = C.c_void_p()
-        capi.check(self.lib.cvx_create(device, C.byref(self.params), max_matrix_mb, C.byref(self.h)))
+        if self.scalar_twin:
+            capi.check(self.lib.cvx_create_ex(device, C.byref(self.params), max_matrix_mb, capi.CREATE_SCALAR_TWIN, C.byref(self.h)))
+        else:
+            capi.check(self.lib.cvx_create(device, C.byref(self.params), max_matrix_mb, C.byref(self.h)))
 
     def stage_kernel_ms(self, stage: int) -> float:
         """cvx_stage_kernel_ms: device time (HIP events) of the kernels of the handle's last call of a next-row stage
@@ -338,7 +344,7 @@ class Job:
             self.results = self.ops = None
 
 
-def format_tileset(lib, tileset, idx, results, ops, n_threads: int = 0):
+def format_tileset(lib, tileset, idx, results, ops, n_threads: int = 0, scalar_twin: bool = False):
     """Host text stage (cvx_format_batch, all host threads) for tiles `idx` of a TileSet whose
     result records / ops arena are `results` / `ops` (numpy, RESULT_DTYPE).  Returns a list of
     dicts with the text-level Align fields (ret, score bits, CIGAR, MD, ...), no NM profile."""
@@ -360,8 +366,9 @@ def format_tileset(lib, tileset, idx, results, ops, n_threads: int = 0):
         bufs[k].md_cap = int(caps[k])
         bufs[k].nm_cap = 0
     out = (capi.CvxAlignmentText * max(n, 1))()
-    capi.check(lib.cvx_format_batch(n, res.ctypes.data_as(C.POINTER(capi.CvxResult)), ops.ctypes.data,
-                                    tab.ctypes.data_as(C.POINTER(capi.CvxTile)), bufs, out, n_threads))
+    capi.check(lib.cvx_format_batch_ex(n, res.ctypes.data_as(C.POINTER(capi.CvxResult)), ops.ctypes.data,
+                                       tab.ctypes.data_as(C.POINTER(capi.CvxTile)), bufs, out, n_threads,
+                                       capi.FORMAT_SCALAR_TWIN if scalar_twin else 0))
     texts = []
     for k in range(n):
         t = out[k]
@@ -621,7 +628,7 @@ class DeviceBatch:
     def alignments(self, want_nm: bool = True) -> List[dict]:
         if self.results is None:
             self.download()
-        return [format_alignment(self.al.lib, self.results[i], self.ops, t, want_nm)
+        return [format_alignment(self.al.lib, self.results[i], self.ops, t, want_nm, scalar_twin=self.al.scalar_twin)
                 for i, t in enumerate(self.tiles)]
 
     def format_batch(self, n_threads: int = 0, want_nm: bool = True):
@@ -650,7 +657,8 @@ class DeviceBatch:
             bufs[i].ext_qend = t.ext_qend
         out = (capi.CvxAlignmentText * max(n, 1))()
         t0 = time.perf_counter()
-        capi.check(self.al.lib.cvx_format_batch(n, self.results, self.ops.ctypes.data, arr, bufs, out, n_threads))
+        capi.check(self.al.lib.cvx_format_batch_ex(n, self.results, self.ops.ctypes.data, arr, bufs, out, n_threads,
+                                                   capi.FORMAT_SCALAR_TWIN if self.al.scalar_twin else 0))
         dt = time.perf_counter() - t0
         return dt, out, store
 
@@ -660,8 +668,9 @@ class DeviceBatch:
             self.b = None
 
 
-def format_alignment(lib, res: capi.CvxResult, ops: np.ndarray, tile, want_nm: bool = True) -> dict:
-    """Host text stage (cvx_format_alignment) -> dict with the Align fields."""
+def format_alignment(lib, res: capi.CvxResult, ops: np.ndarray, tile, want_nm: bool = True, scalar_twin: bool = False) -> dict:
+    """Host text stage (cvx_format_alignment_ex) -> dict with the Align fields.  scalar_twin: the text stage of
+    Convex::ConvexAlign (no N-clip block; cigar_op_count and sv_type come back as capi.NOT_WRITTEN)."""
     H, W = len(tile.qry), len(tile.ref)
     cap = 4 * H + 64
     txt = capi.CvxAlignmentText()
@@ -670,9 +679,10 @@ def format_alignment(lib, res: capi.CvxResult, ops: np.ndarray, tile, want_nm: b
         md = C.create_string_buffer(cap)
         nm_cap = 2 * (H + 1) + W + 16
         nm = np.zeros((nm_cap, 3), dtype=np.int32)
-        capi.check(lib.cvx_format_alignment(C.byref(res), ops.ctypes.data, tile.ref, W, H,
-                                            tile.ext_qstart, tile.ext_qend, cig, cap, md, cap,
-                                            nm.ctypes.data if want_nm else None, nm_cap, C.byref(txt)))
+        capi.check(lib.cvx_format_alignment_ex(C.byref(res), ops.ctypes.data, tile.ref, W, H,
+                                               tile.ext_qstart, tile.ext_qend, cig, cap, md, cap,
+                                               nm.ctypes.data if want_nm else None, nm_cap,
+                                               capi.FORMAT_SCALAR_TWIN if scalar_twin else 0, C.byref(txt)))
         if txt.cigar_len < cap and txt.md_len < cap:
             break
         cap = max(txt.cigar_len, txt.md_len) + 64

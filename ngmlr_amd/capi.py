@@ -13,6 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(HERE, "libcvxalign.so")   # CVX_LIB: A/B builds while tuning
 
 CVX_OK = 0
+CREATE_SERVICE, CREATE_SCALAR_TWIN = 1, 2      # cvx_create_ex flags
+FORMAT_SCALAR_TWIN = 1                         # cvx_format_alignment_ex / cvx_format_batch_ex flags
+NOT_WRITTEN = -1                               # cigar_op_count / sv_type of the scalar twin's text stage
 STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH = 0, 1, 2      # cvx_stage_kernel_ms
 ERR_NAMES = {0: "CVX_OK", -1: "CVX_ERR_NO_DEVICE", -2: "CVX_ERR_PARAMS", -3: "CVX_ERR_ARG",
              -4: "CVX_ERR_OOM", -5: "CVX_ERR_HIP", -6: "CVX_ERR_CAPACITY"}
@@ -31,7 +34,7 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_job_nm_regions", "cvx_nm_regions_ops", "cvx_nm_regions_host",
            "cvx_sam_record_text", "cvx_sam_unmapped_text", "cvx_sam_batch", "cvx_stage_kernel_ms", "cvx_search_last_attempts", "cvx_index_build", "cvx_index_build_device",
            "cvx_corridor_fit", "cvx_corridor_fit_batch", "cvx_create_ex", "cvx_runtime_regime", "cvx_search_batch_arena",
-           "cvx_score_submit", "cvx_score_poll", "cvx_score_wait")
+           "cvx_score_submit", "cvx_score_poll", "cvx_score_wait", "cvx_format_alignment_ex", "cvx_format_batch_ex")
 
 
 class CvxParams(C.Structure):
@@ -230,6 +233,12 @@ def load(path: str = None) -> C.CDLL:
                                          C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32,
                                          C.c_char_p, C.c_int32, C.c_void_p, C.c_int32,
                                          C.POINTER(CvxAlignmentText)]
+    lib.cvx_format_alignment_ex.argtypes = [C.POINTER(CvxResult), C.c_void_p, C.c_char_p, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32,
+                                            C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32,
+                                            C.POINTER(CvxAlignmentText)]
+    lib.cvx_format_batch_ex.argtypes = [C.c_int32, C.POINTER(CvxResult), C.c_void_p, C.POINTER(CvxTile),
+                                        C.POINTER(CvxTextBuffers), C.POINTER(CvxAlignmentText), C.c_int32, C.c_uint32]
     _libs[path] = lib
     return lib
 

@@ -331,7 +331,7 @@ int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int co
 	req.tile.externalQStart = externalQStart; req.tile.externalQEnd = externalQEnd; req.tile.ret = -1; req.tile.failed = false;
 	req.launch = 0; req.result = 0; req.done = false; req.failed = false;
 	req.fiber = FiberApi::Current();
-	ConvexAlignHip::Prepare(req.tile);       /* in the caller's thread; throws like the reference for a malformed call */
+	ConvexAlignHip::Prepare(req.tile, backend->ScalarTwin());       /* in the caller's thread; throws like the reference for a malformed call */
 
 	std::unique_lock<std::mutex> lk(mtx);
 	if (queue.empty()) oldest = std::chrono::steady_clock::now();
@@ -424,7 +424,7 @@ void SharedAligner::ThreadBegin() { if (BatchingAligner * d = currentDispatcher(
 void SharedAligner::ThreadEnd() { if (BatchingAligner * d = currentDispatcher()) d->WorkerDone(); }
 
 SharedAligner::SharedAligner(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
-		float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId) : shared(0), device(0), perRead(false) {
+		float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId, bool const scalarTwin) : shared(0), device(0), perRead(false) {
 	std::lock_guard<std::mutex> g(g_sharedMtx);
 	perRead = g_poolAccounting;
 	/* CVX_DEVICES=k: only the first k devices.  CVX_ALIAS_DEVICES=k: deal the workers over k LOGICAL devices (own backend, own
@@ -441,7 +441,7 @@ SharedAligner::SharedAligner(int const stdOutMode, float const match, float cons
 		int maxBatch = 4096, timeoutUs = 2000;
 		if (const char * e = getenv("CVX_BATCH_MAX")) maxBatch = atoi(e);
 		if (const char * e = getenv("CVX_BATCH_TIMEOUT_US")) timeoutUs = atoi(e);
-		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device);   /* throws without a usable device */
+		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device, 0, scalarTwin);   /* throws without a usable device */
 		g_shared[device] = new BatchingAligner(g_backend[device], 0, maxBatch, timeoutUs);   /* workers join one by one */
 		/* with alignment contexts off the CS threads (align_pool.h) a launch waits for 256 tiles, 30 ms at most: hundreds of
 		 * contexts hide that wait, and the device sees a few large launches instead of many small ones (CVX_BATCH_TARGET /

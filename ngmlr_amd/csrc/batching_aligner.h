@@ -175,7 +175,8 @@ private:
 class SharedAligner: public IAlignment {
 public:
 	SharedAligner(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
-			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = -1 /* -1: workers are dealt over all devices */);
+			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = -1 /* -1: workers are dealt over all devices */,
+			bool const scalarTwin = false /* the device's shared backend in scalar-twin mode (ConvexAlignHip; one mode per process, as --nosse is) */);
 	virtual ~SharedAligner();
 
 	virtual int GetScoreBatchSize() const { return 0; }

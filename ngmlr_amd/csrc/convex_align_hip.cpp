@@ -84,7 +84,7 @@ void ConvexAlignHip::CorridorStats(long & prepared, long & closedForm) {
 
 ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float const mismatch,
 		float const gapOpen, float const gapExtend, float const gapExtendMin, float const gapDecay,
-		int const deviceId, unsigned long const maxMatrixSizeMB) : handle(0), genome(0) {
+		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin) : handle(0), twin(scalarTwin), genome(0) {
 	(void) stdOutMode;
 	cvx_params p;
 	p.match = match; p.mismatch = mismatch; p.gap_open = gapOpen;
@@ -94,7 +94,7 @@ ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float co
 	if (maxMatrixMB == 0) maxMatrixMB = (unsigned long) Config.getMaxMatrixSizeMB();
 #endif
 	if (maxMatrixMB == 0) maxMatrixMB = 10000;      /* IConfig's default (src/IConfig.h:47) */
-	if (cvx_create(deviceId, &p, (uint64_t) maxMatrixMB, &handle) != CVX_OK) {
+	if (cvx_create_ex(deviceId, &p, (uint64_t) maxMatrixMB, twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u, &handle) != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
 		throw "ConvexAlignHip: no usable MI355X / unsupported scoring";
 	}
@@ -140,9 +140,9 @@ int ConvexAlignHip::SingleAlign(int const mode, CorridorLine * corridor, int con
 	return t.ret;
 }
 
-void ConvexAlignHip::Prepare(Tile & t) {
+void ConvexAlignHip::Prepare(Tile & t, bool const scalarTwin) {
 	Align & a = *t.result;
-	a.svType = 0;               /* the reference reads it as a debug id, then clears it */
+	if (!scalarTwin) a.svType = 0;      /* ConvexAlignFast reads it as a debug id, then clears it; the scalar twin only reads it */
 	a.Score = -1.0f;
 	t.ret = -1;
 	t.failed = false;
@@ -308,7 +308,7 @@ void ConvexAlignHip::Release(cvx_job job) {
 
 void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 	if (n <= 0) return;
-	for (int i = 0; i < n; ++i) Prepare(tiles[i]);
+	for (int i = 0; i < n; ++i) Prepare(tiles[i], twin);
 	cvx_job job = Submit(tiles, n);
 	cvx_result const * res = 0;
 	uint32_t const * ops = 0;
@@ -349,9 +349,9 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 	if (noAlignment(t, r)) return;
 	cvx_alignment_text txt;
 	for (;;) {
-		int rc = cvx_format_alignment(&r, ops, t.refSeq, refLen, qryLen, t.externalQStart,
+		int rc = cvx_format_alignment_ex(&r, ops, t.refSeq, refLen, qryLen, t.externalQStart,
 				t.externalQEnd, a.pBuffer1, a.maxBufferLength, a.pBuffer2, a.maxMdBufferLength,
-				(int32_t *) a.nmPerPosition, a.nmPerPostionLength, &txt);
+				(int32_t *) a.nmPerPosition, a.nmPerPostionLength, twin ? (uint32_t) CVX_FORMAT_SCALAR_TWIN : 0u, &txt);
 		if (rc != CVX_OK) throw 1;
 		bool again = false;
 		if (txt.md_len >= a.maxMdBufferLength) {       /* checkMdBufferLength: grow with new[] */
@@ -391,10 +391,12 @@ void ConvexAlignHip::fillAlign(Tile & t, cvx_alignment_text const & txt) const {
 	a.Identity = txt.identity;
 	a.NM = txt.nm;
 	a.alignmentLength = txt.alignment_length;
-	a.cigarOpCount = txt.cigar_op_count;
 	a.PositionOffset = txt.position_offset;
 	a.Score = txt.score;
-	a.svType = txt.sv_type;
+	if (!twin) {                /* the scalar twin writes neither (both come back as CVX_NOT_WRITTEN): the caller's values stay */
+		a.cigarOpCount = txt.cigar_op_count;
+		a.svType = txt.sv_type;
+	}
 	t.ret = txt.ret;
 }
 

@@ -31,7 +31,14 @@ class ConvexAlignHip: public IAlignment {
 public:
 	ConvexAlignHip(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = 0,
-			unsigned long const maxMatrixSizeMB = 0 /* Config.getMaxMatrixSizeMB(); 0 = the reference's default 10000 */);
+			unsigned long const maxMatrixSizeMB = 0 /* Config.getMaxMatrixSizeMB(); 0 = the reference's default 10000 */,
+			bool const scalarTwin = false);
+	/* scalarTwin: the drop-in takes the place of Convex::ConvexAlign, the scalar aligner ngmlr's --nosse binds at
+	 * src/AlignmentBuffer.h:345-353, instead of ConvexAlignFast's (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h).  In that mode
+	 * SingleAlign / AlignTiles leave Align::svType and Align::cigarOpCount exactly as the caller passed them -- no clear at entry,
+	 * no assignment at exit: the twin only reads svType (src/ConvexAlign.cpp:423), and ngmlr prints what it stored there
+	 * (the read's id, src/AlignmentBuffer.cpp:362) as SV:i. */
+	bool ScalarTwin() const { return twin; }
 	virtual ~ConvexAlignHip();
 
 	virtual int GetScoreBatchSize() const;
@@ -84,7 +91,7 @@ public:
 	 *   Poll     non-blocking "is it done"; Wait  blocks until the job is done: result records and run-length ops, valid until Release
 	 *   Finish   convertCigar + flags of ONE tile into its Align (throws 1 for that tile's hard errors)
 	 *   Release  gives the job's buffers back */
-	static void Prepare(Tile & t);
+	static void Prepare(Tile & t, bool scalarTwin = false);      /* scalarTwin: of the aligner the tile goes to (ScalarTwin()) */
 	cvx_job Submit(Tile const * tiles, int n);
 	bool Poll(cvx_job job);       /* true: Wait would not block (also keeps queued launches moving) */
 	void Wait(cvx_job job, cvx_result const ** results, uint32_t const ** ops);
@@ -119,6 +126,7 @@ private:
 	void fillAlign(Tile & t, cvx_alignment_text const & txt) const;
 	bool noAlignment(Tile & t, cvx_result const & r) const;
 	cvx_handle handle;
+	bool twin;
 	unsigned long maxMatrixMB;
 	std::vector<cvx_tile> packed;
 	cvx_genome genome;                     /* DeviceWindows' genome on this aligner's device (uploaded by the first launch that carries a window) */

@@ -92,12 +92,28 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 		char *cigar, int32_t cigar_cap, char *md, int32_t md_cap,
 		int32_t *nm_triples, int32_t nm_cap, cvx_alignment_text *out) {
 	ABI_GUARD_BEGIN
+	return cvx_format_alignment_ex(r, ops_arena, ref, ref_len, qry_len, ext_qstart, ext_qend, cigar, cigar_cap, md, md_cap, nm_triples, nm_cap, 0u, out);
+	ABI_GUARD_END
+}
+
+/* flags & CVX_FORMAT_SCALAR_TWIN: the text stage of the scalar twin (Convex::ConvexAlign::SingleAlign, src/ConvexAlign.cpp:418-467):
+ * the same convertCigar, no N-clip block behind it and no store to Align::cigarOpCount / Align::svType -- both fields come back
+ * as CVX_NOT_WRITTEN */
+extern "C" int cvx_format_alignment_ex(const cvx_result *r, const uint32_t *ops_arena,
+		const char *ref, int32_t ref_len, int32_t qry_len,
+		int32_t ext_qstart, int32_t ext_qend,
+		char *cigar, int32_t cigar_cap, char *md, int32_t md_cap,
+		int32_t *nm_triples, int32_t nm_cap, uint32_t flags, cvx_alignment_text *out) {
+	ABI_GUARD_BEGIN
+	if (flags & ~(uint32_t) CVX_FORMAT_SCALAR_TWIN) { cvx::set_err("cvx_format_alignment_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	const bool twin = (flags & CVX_FORMAT_SCALAR_TWIN) != 0;
 	(void) qry_len;
 	if (!r || !out || cigar_cap < 0 || md_cap < 0 || (cigar_cap > 0 && !cigar) || (md_cap > 0 && !md))
 		return CVX_ERR_ARG;
 	memset(out, 0, sizeof(*out));
 	out->ret = -1;
 	out->score = -1.0f;
+	if (twin) out->cigar_op_count = out->sv_type = CVX_NOT_WRITTEN;      /* (also for a tile without an alignment) */
 	if (cigar_cap > 0) cigar[0] = '\0';
 	if (md_cap > 0) md[0] = '\0';
 	if (r->status != CVX_TILE_OK) return CVX_OK;
@@ -195,7 +211,7 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 	out->nm = columns - matches;
 	out->identity = matches * 1.0f / columns;
 	out->alignment_length = columns;
-	out->cigar_op_count = n_cigar_ops;
+	out->cigar_op_count = twin ? (int32_t) CVX_NOT_WRITTEN : n_cigar_ops;
 	out->last_ref = pos_ref;
 	out->last_read = pos_read;
 	out->nm_count = nm.n;
@@ -204,6 +220,7 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 
 	/* N-clip flags: both tests set bit 0x1 and look for 'X' (never produced by the
 	 * decoder, which emits 'N'/'x') -- reproduced as is, src/ConvexAlignFast.cpp:493-528 */
+	if (twin) { out->sv_type = CVX_NOT_WRITTEN; return CVX_OK; }      /* the twin has no N-clip block */
 	int sv = 0;
 	{
 		int n_count = 0, probes = 0;
@@ -231,7 +248,14 @@ extern "C" int cvx_format_alignment(const cvx_result *r, const uint32_t *ops_are
 extern "C" int cvx_format_batch(int32_t n, const cvx_result *results, const uint32_t *ops_arena,
 		const cvx_tile *tiles, const cvx_text_buffers *bufs, cvx_alignment_text *out,
 		int32_t n_threads) {
+	ABI_GUARD_BEGIN return cvx_format_batch_ex(n, results, ops_arena, tiles, bufs, out, n_threads, 0u); ABI_GUARD_END
+}
+
+extern "C" int cvx_format_batch_ex(int32_t n, const cvx_result *results, const uint32_t *ops_arena,
+		const cvx_tile *tiles, const cvx_text_buffers *bufs, cvx_alignment_text *out,
+		int32_t n_threads, uint32_t flags) {
 	ABI_GUARD_BEGIN
+	if (flags & ~(uint32_t) CVX_FORMAT_SCALAR_TWIN) { cvx::set_err("cvx_format_batch_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
 	if (n < 0 || (n > 0 && (!results || !tiles || !bufs || !out))) return CVX_ERR_ARG;
 	if (n == 0) return CVX_OK;
 	int nt = n_threads > 0 ? n_threads : (int) std::thread::hardware_concurrency();
@@ -245,9 +269,9 @@ extern "C" int cvx_format_batch(int32_t n, const cvx_result *results, const uint
 			const int e = b + 16 < n ? b + 16 : n;
 			for (int i = b; i < e; ++i) {
 				const cvx_text_buffers &tb = bufs[i];
-				const int rc = cvx_format_alignment(&results[i], ops_arena, tiles[i].ref, tiles[i].ref_len,
+				const int rc = cvx_format_alignment_ex(&results[i], ops_arena, tiles[i].ref, tiles[i].ref_len,
 						tiles[i].qry_len, tb.ext_qstart, tb.ext_qend, tb.cigar, tb.cigar_cap, tb.md, tb.md_cap,
-						tb.nm_triples, tb.nm_cap, &out[i]);
+						tb.nm_triples, tb.nm_cap, flags, &out[i]);
 				if (rc != CVX_OK) { int ok = CVX_OK; err.compare_exchange_strong(ok, rc); }
 			}
 		}

@@ -59,7 +59,8 @@ struct Pub {               /* what a slot shows its lower neighbour, double buff
 
 }  // namespace
 
-template <bool SSE>
+/* TWIN (with SSE = false): the scalar aligner's mismatch against an 'x' of the window (ScoreParams::misx, src/ConvexAlign.cpp:513) */
+template <bool SSE, bool TWIN = false>
 __global__ void __launch_bounds__(1024)
 fill_generic_kernel(const FillArgs a, uint8_t *scratch, const uint64_t *scratch_off) {
 	const int qi = blockIdx.x;
@@ -74,6 +75,8 @@ fill_generic_kernel(const FillArgs a, uint8_t *scratch, const uint64_t *scratch_
 	const int Ng = tr.ring;
 	uint32_t *dirs = a.dirs + tr.dir_off;
 	const float mat = a.sp.mat, mis = a.sp.mis, go = a.sp.go;
+	const float misx = a.sp.misx;
+	static_assert(!(SSE && TWIN), "the twin runs the scalar rules for any scoring");
 	const float gext = a.sp.ge, gem = a.sp.gem, decay = a.sp.decay;
 	const int tid = threadIdx.x, T = blockDim.x;
 
@@ -128,7 +131,7 @@ fill_generic_kernel(const FillArgs a, uint8_t *scratch, const uint64_t *scratch_
 			if (act && !SSE) {
 				const int x = r - st.y;
 				const bool eq = ((int) ref[x] == st.qch);
-				const float diag_cell = st.dg + (eq ? mat : mis);
+				const float diag_cell = st.dg + (eq ? mat : (TWIN && ref[x] == 'x') ? misx : mis);
 				const float up_cell = up.V;
 				const float left_cell = st.Hc;
 				const float mx = fmaxf(fmaxf(fmaxf(left_cell, diag_cell), up_cell), 0.0f);
@@ -292,7 +295,10 @@ size_t generic_scratch_bytes(int ring) {
 
 hipError_t launch_fill_generic(const FillArgs &a, bool sse_variant, uint8_t *scratch, const uint64_t *scratch_off, hipStream_t st) {
 	if (a.list_n <= 0) return hipSuccess;
-	if (sse_variant) hipLaunchKernelGGL(fill_generic_kernel<true>, dim3(a.list_n), dim3(1024), 0, st, a, scratch, scratch_off);
+	if (a.twin) {
+		if (sse_variant) return hipErrorInvalidValue;
+		hipLaunchKernelGGL((fill_generic_kernel<false, true>), dim3(a.list_n), dim3(1024), 0, st, a, scratch, scratch_off);
+	} else if (sse_variant) hipLaunchKernelGGL(fill_generic_kernel<true>, dim3(a.list_n), dim3(1024), 0, st, a, scratch, scratch_off);
 	else hipLaunchKernelGGL(fill_generic_kernel<false>, dim3(a.list_n), dim3(1024), 0, st, a, scratch, scratch_off);
 	return hipGetLastError();
 }

@@ -527,6 +527,41 @@ inline void lpt_sort(std::vector<int32_t> &v, const TilePlan *plan) {
 	});
 }
 
+/* Which forward fill a handle's scoring gets (cvx_create_ex).  The ring kernels implement the scalar recurrence and use its sign
+ * structure: match > 0 > every penalty, extension never dearer than its floor (ring_signs).  A default handle must reproduce the
+ * reference's SSE path, which equals that recurrence only while opening a gap directly off the other gap type can never win --
+ * gap_open + gap_ext_min < mismatch (the 0.25 keeps float rounding out of the argument); any other scoring
+ * goes to the catch-all kernel's SSE-variant instantiation.  A scalar-twin handle (CVX_CREATE_SCALAR_TWIN) reproduces
+ * Convex::ConvexAlign, which runs the scalar recurrence for ANY scoring: it never takes the SSE variant; where the sign structure
+ * holds it uses the rings' twin instantiations, otherwise the catch-all kernel with scalar rules.  Twin handles build no gang
+ * classes (the twin form of the gang kernels is not instantiated): their corridors of 257-576 live rows are chained. */
+struct FillSemantics {
+	bool ring_signs;       /* the sign structure the ring kernels rely on holds */
+	bool sse_variant;      /* every tile to fill_generic_kernel<SSE = true> */
+	bool force_generic;    /* every tile to the catch-all kernel (either instantiation) */
+	bool no_gangs;         /* the handle builds no gang classes, whatever CVX_TUNE_GANGS says */
+	bool matrix_cap;       /* max_matrix_mb applies (the twin's AlignmentMatrix::prepare allocates whatever is asked) */
+};
+inline FillSemantics fill_semantics(const float match, const float mismatch, const float gap_open, const float gap_extend,
+		const float gap_extend_min, const float gap_decay, const bool scalar_twin) {
+	FillSemantics f;
+	f.ring_signs = match > 0.0f && mismatch < 0.0f && gap_open < 0.0f && gap_extend < 0.0f && gap_extend_min < 0.0f &&
+			gap_decay >= 0.0f && gap_extend <= gap_extend_min;
+	const bool fast_regime = f.ring_signs && (gap_open + gap_extend_min) < mismatch - 0.25f;
+	f.sse_variant = !scalar_twin && !fast_regime;
+	f.force_generic = scalar_twin ? !f.ring_signs : !fast_regime;
+	f.no_gangs = scalar_twin;
+	f.matrix_cap = !scalar_twin;
+	return f;
+}
+/* the twin's mismatch against an 'x' of the reference window: ONE binary32 multiply (src/ConvexAlign.cpp:513; the files that
+ * include this are compiled with -ffp-contract=off and for a target that evaluates float expressions in binary32) */
+inline float twin_mismatch_x(const float mismatch) {
+	volatile float m = mismatch;
+	volatile float r = m * 100.0f;
+	return r;
+}
+
 /* Kernel class, arena offsets and (sorted) work lists of every tile from its corridor plan.
  * tune: the CVX_TUNE_* knobs of the runtime. */
 /* tuning / test knobs of the runtime (CVX_TUNE_* environment variables; all 0 = off) */

@@ -349,6 +349,8 @@ struct cvx_context {
 	                            * one-wave-per-tile walk, -1 = round 4's rule (64 below 4 096 tiles, else 8 + 32) (env CVX_TUNE_BT_GROUP) */
 	bool bt_per_class = true;  /* tuning knob (env CVX_TUNE_BT_PER_CLASS = 0 clears it): a batch of several fill classes walks each class behind its own fill (build_schedule) */
 	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
+	bool scalar_twin = false; /* cvx_create_ex(CVX_CREATE_SCALAR_TWIN): the semantics of Convex::ConvexAlign (cvx_host_logic.h, fill_semantics) */
+	bool force_generic = false; /* every tile to the catch-all kernel: sse_variant, or a twin handle whose scoring lacks the rings' sign structure */
 	bool sse_variant = false; /* scoring outside the regime where the reference's SSE path equals the scalar recurrence:
 	                           * every tile goes to the catch-all kernel's SSE-variant instantiation */
 	/* freed batches keep their device arenas and pinned staging and wait here for the next upload

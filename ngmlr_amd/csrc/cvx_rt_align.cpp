@@ -321,6 +321,7 @@ void kernel_args(const cvx_context *h, const cvx_batch_s *b, const ChainBlk *cha
 	a.pen_table = h->tune_pen_table;
 	a.tasks = nullptr; a.chain_ticket = nullptr; a.bnd = nullptr; a.chain_out = nullptr; a.bnd_epoch = 0; a.chain_prio = 0;
 	a.sp = h->sp;
+	a.twin = h->scalar_twin ? 1 : 0;
 	ba.chain_blk = chain_blk;
 	ba.n_tiles = b->n;
 }
@@ -401,7 +402,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	HostPlan hp;
 	PlanTuning tune;
 	tune.min_slots = h->tune_min_slots; tune.max_slots = h->tune_max_slots; tune.force_wrap = h->tune_force_wrap; tune.chain_m = h->tune_chain_m;
-	tune.force_generic = h->sse_variant ? 1 : 0;
+	tune.force_generic = h->force_generic ? 1 : 0;
 	tune.long_steps = h->tune_long_steps; tune.small_batch = h->tune_small_batch; tune.long_need = h->tune_long_need;
 	tune.no_gangs = h->tune_gangs ? 0 : 1;
 	/* (a tile that gets chained needs its rows on the host: rebuilt from the step stream the batch still owns) */

@@ -40,6 +40,13 @@ int text_setup(cvx_batch_s *j, const int32_t *ext_qstart, const int32_t *ext_qen
 
 }  // namespace
 
+/* a scalar-twin handle's jobs: Convex::ConvexAlign writes neither Align::cigarOpCount nor Align::svType and has no N-clip block
+ * (cvx_format_alignment_ex, CVX_FORMAT_SCALAR_TWIN); text_kernel computes them for every tile, the records leave without them */
+static void twin_text_fields(const cvx_context *h, cvx_alignment_text *out, const int n) {
+	if (!h->scalar_twin) return;
+	for (int i = 0; i < n; ++i) { out[i].cigar_op_count = CVX_NOT_WRITTEN; out[i].sv_type = CVX_NOT_WRITTEN; }
+}
+
 extern "C" {
 
 int cvx_job_text(cvx_handle h, cvx_job j, const int32_t *ext_qstart, const int32_t *ext_qend,
@@ -71,6 +78,7 @@ int cvx_job_text(cvx_handle h, cvx_job j, const int32_t *ext_qstart, const int32
 	HIP_TRY(hipMemcpyAsync(j->h_text.p, j->d_text.p, (size_t) ((total + 255) / 256 * 256 <= j->d_text.cap ? (total + 255) / 256 * 256 : total), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	memcpy(out, j->h_trec.p, n1 * sizeof(TextRec));
+	twin_text_fields(h, out, n);
 	for (int i = 0; i < n; ++i) text_off[i] = hoff[i];
 	*text = j->h_text.as<char>();
 	if (text_bytes) *text_bytes = total;
@@ -120,6 +128,7 @@ int cvx_job_text_all(cvx_handle h, cvx_job j, const int32_t *ext_qstart, const i
 	if (entries > 0) HIP_TRY(hipMemcpyAsync(j->h_nm.p, j->d_nm.p, 3 * (size_t) entries * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	memcpy(out, j->h_trec.p, n1 * sizeof(TextRec));
+	twin_text_fields(h, out, n);
 	for (int i = 0; i < n; ++i) text_off[i] = hoff[i];
 	for (int i = 0; i <= n; ++i) nm_entry_off[i] = hnm[i];
 	*text = j->h_text.as<char>();

@@ -229,10 +229,11 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 				p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay);
 		return CVX_ERR_PARAMS;
 	}
-	const bool fast_regime = p->match > 0.0f && p->mismatch < 0.0f && p->gap_open < 0.0f &&
-			p->gap_extend < 0.0f && p->gap_extend_min < 0.0f && p->gap_decay >= 0.0f &&
-			p->gap_extend <= p->gap_extend_min &&
-			(p->gap_open + p->gap_extend_min) < p->mismatch - 0.25f;
+	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	/* (a scalar-twin handle runs the scalar recurrence for any scoring: rings where their sign structure holds, else the
+	 * catch-all kernel with scalar rules, never the SSE variant -- fill_semantics, cvx_host_logic.h) */
+	const bool scalar_twin = (flags & CVX_CREATE_SCALAR_TWIN) != 0;
+	const FillSemantics sem = fill_semantics(p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay, scalar_twin);
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
 		set_err("cvx_create: no HIP device available (the HIP path has no CPU fallback)");
@@ -280,12 +281,17 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	c->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
 	c->sp.mat = p->match; c->sp.mis = p->mismatch; c->sp.go = p->gap_open;
 	c->sp.ge = p->gap_extend; c->sp.gem = p->gap_extend_min; c->sp.decay = p->gap_decay;
-	c->max_matrix_mb = max_matrix_mb ? max_matrix_mb : 10000;
-	c->sse_variant = !fast_regime;
+	c->sp.misx = twin_mismatch_x(p->mismatch);
+	c->scalar_twin = scalar_twin;
+	/* the twin has no matrix-size cap (its AlignmentMatrix::prepare allocates whatever is asked): no tile of a twin handle is
+	 * CVX_TILE_TOO_LARGE because of max_matrix_mb */
+	c->max_matrix_mb = !sem.matrix_cap ? ~0ull : (max_matrix_mb ? max_matrix_mb : 10000);
+	c->sse_variant = sem.sse_variant;
 	if (const char *e = getenv("CVX_TUNE_BT_GROUP")) c->bt_group = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_BT_PER_CLASS")) c->bt_per_class = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_OVERLAP_POST")) c->overlap_post = atoi(e) != 0;
-	if (const char *e = getenv("CVX_TUNE_SSE_VARIANT")) c->sse_variant = c->sse_variant || atoi(e) != 0;   /* test knob */
+	if (const char *e = getenv("CVX_TUNE_SSE_VARIANT")) c->sse_variant = c->sse_variant || (atoi(e) != 0 && !scalar_twin);   /* test knob */
+	c->force_generic = sem.force_generic || c->sse_variant;
 	c->pack_threads = PackPool::get().size();      /* the process's shared pack threads (CVX_PACK_THREADS) */
 	if (const char *e = getenv("CVX_TUNE_MIN_M")) c->tune_min_slots = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_FORCE_WRAP16")) c->tune_force_wrap = atoi(e);
@@ -312,7 +318,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	if (const char *e = getenv("CVX_TUNE_LONG_STEPS")) c->tune_long_steps = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_SMALL_BATCH")) c->tune_small_batch = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_LONG_NEED")) c->tune_long_need = atoi(e);
-	if (const char *e = getenv("CVX_TUNE_GANGS")) c->tune_gangs = atoi(e) != 0;
+	if (const char *e = getenv("CVX_TUNE_GANGS")) c->tune_gangs = atoi(e) != 0 && !sem.no_gangs;
 	if (const char *e = getenv("CVX_TUNE_GANG_PRIO")) c->tune_gang_prio = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_LATE_MIN")) c->tune_late_min = std::max(1, atoi(e));
 	if (const char *e = getenv("CVX_TUNE_LATE_SHIFT")) c->tune_late_shift = std::min(16, std::max(0, atoi(e)));

@@ -62,6 +62,8 @@ static const int kChainChunk = 16;     /* chained row blocks: steps per boundary
 
 struct ScoreParams {
 	float mat, mis, go, ge, gem, decay;
+	float misx;            /* scalar-twin handles: mismatch against an 'x' of the reference window = mis * 100.0f, one binary32 multiply
+	                        * on the host (src/ConvexAlign.cpp:513); read by the TWIN instantiations only */
 };
 
 /* How a tile's corridor rows travel to the device (expand_rows_kernel rebuilds the int2 rows arena):
@@ -293,6 +295,7 @@ struct FillArgs {
 	int32_t pen_table;       /* != 0: the two-phase float-score launches read the convex penalty from an LDS table (TAB instantiation) */
 	int32_t *ops;          /* per-tile op regions */
 	ScoreParams sp;
+	int32_t twin;          /* != 0: launch the scalar twin's instantiations (a property of the handle; the kernels never read it) */
 };
 
 struct BacktrackArgs {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of several builds of libcvxalign.so in ONE process on the same resident batch (GPU).
 
-    python tools/ab_fill.py TILES [workload] name1 name2 ...   (name: default | a build under ngmlr_amd/variants/)
+    python tools/ab_fill.py TILES [workload] name1 name2 ...   (name: default | a build under ngmlr_amd/variants/;
+                                                               name:twin = a scalar-twin handle of that build)
 
 Tiles are generated once; every build uploads them, runs warm-up + 3 timed runs and prints the
 dominant fill launch, the stage times and how many tiles needed the exact-tracking redo pass.
@@ -39,7 +40,8 @@ def main():
     ref = None
     for name in args:
         try:
-            al = ConvexAlignHip(lib_path=lib_path(name))
+            build, _, mode = name.partition(":")
+            al = ConvexAlignHip(lib_path=lib_path(build), scalar_twin=(mode == "twin"))
             batch = al.upload(tiles)
             batch.run()
             tms = [batch.run() for _ in range(3)]
@@ -48,7 +50,7 @@ def main():
             key = (np.array([(np.float32(r.score).view(np.uint32), r.status, r.best_ref_index, r.best_read_index,
                               r.ref_position, r.qstart, r.qend, r.n_ops) for r in res[:n]], dtype=np.int64), ops.copy())
             dom = max(launches, key=lambda l: l["alg_bytes"])
-            msg = "%-10s dom M%d/NW%d %8.3f ms (%5.0f Gcell/s)  plan %.2f fill %.2f bt %.2f total %.2f ms  -> %6.0f Gbp/h dev" % (
+            msg = "%-12s dom M%d/NW%d %8.3f ms (%5.0f Gcell/s)  plan %.2f fill %.2f bt %.2f total %.2f ms  -> %6.0f Gbp/h dev" % (
                 name, dom["slots_per_lane"], dom["waves"], dom["ms"], dom["cells"] / dom["ms"] / 1e6,
                 np.mean([t.plan_ms for t in tms]), np.mean([t.fill_ms for t in tms]),
                 np.mean([t.backtrack_ms for t in tms]), np.mean([t.total_ms for t in tms]),

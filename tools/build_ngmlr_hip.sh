@@ -2,7 +2,8 @@
 # tools/build_ngmlr_hip.sh -- the drop-in, end to end: builds the reference's own ngmlr
 # (its CMake, its sources, in a fresh /tmp copy) with exactly the change INTEGRATION.md
 # describes -- Convex::ConvexAlignHip constructed instead of Convex::ConvexAlignFast at
-# src/AlignmentBuffer.h:355 -- linked against this repository's libcvxalign.so.  The
+# src/AlignmentBuffer.h:355, and in scalar-twin mode instead of Convex::ConvexAlign in the --nosse
+# branch at :346 -- linked against this repository's libcvxalign.so.  The
 # binary lands in oracle/_ref/ngmlr_hip (git-ignored build artefact, travels to the GPU
 # box like the .so files); tests/test_gpu_e2e.py runs it on the reference's test data and
 # compares the SAM with the unmodified reference's output (tests/golden/test_*.sam).
@@ -189,6 +190,13 @@ if CLASS != 'cpu':
     pat = re.compile(r'aligner = new Convex::ConvexAlignFast\(', re.S)
     assert len(pat.findall(s)) == 1
     s = pat.sub('aligner = new %s(' % CLASS, s)
+    # the --nosse branch (src/AlignmentBuffer.h:345-353): the same class, constructed in scalar-twin mode -- Convex::ConvexAlign's
+    # semantics on the device (CVX_CREATE_SCALAR_TWIN), Align::svType / cigarOpCount left as the caller passed them
+    if CLASS in ('Convex::ConvexAlignHip', 'Convex::SharedAligner'):
+        twin_args = {'Convex::ConvexAlignHip': '0, 0, true', 'Convex::SharedAligner': '-1, true'}[CLASS]
+        nosse = re.compile(r'aligner = new Convex::ConvexAlign\((.*?)Config\.getScoreGapDecay\(\)\);', re.S)
+        assert len(nosse.findall(s)) == 1
+        s = nosse.sub(lambda m: 'aligner = new %s(%sConfig.getScoreGapDecay(), %s);' % (CLASS, m.group(1), twin_args), s)
     open(p, 'w').write(s)
 p = T + '/src/CMakeLists.txt'
 c = open(p).read()

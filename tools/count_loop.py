@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Instruction mix of the step loop of fill_ring_kernel<M,1,false> in a hipcc -S dump.
-usage: count_loop.py file.s [M]   (classes per tools/ubench_ops.hip: A = full-rate VALU, B = half-rate)"""
+usage: count_loop.py file.s [M] [--tab] [--twin] [-v]   (classes per tools/ubench_ops.hip: A = full-rate VALU, B = half-rate)"""
 import re, sys
 args = [a for a in sys.argv[1:] if not a.startswith("-")]
 M = int(args[1]) if len(args) > 1 else 3
 txt = open(args[0]).read()
-name = "_ZN3cvx16fill_ring_kernelILi%dELb0ELi0EEEvNS_8FillArgsE" % M      # <M, WRAP = false, MODE = kFillTwoPhase>
+# <M, WRAP = false, MODE = kFillTwoPhase, TAB, G = 1>; --tab: the form with the LDS penalty table (the PacBio launch); --twin: the scalar twin's kernel
+name = "_ZN3cvx%sILi%dELb0ELi0ELb%dELi1EEEvNS_8FillArgsE" % ("21fill_ring_twin_kernel" if "--twin" in sys.argv else "16fill_ring_kernel", M, "--tab" in sys.argv)
 body = txt[txt.index(name + ":"):]
 body = body[:body.index("s_endpgm")].split("\n")
 # the step loop = the longest stretch between a label and a backward branch to it
