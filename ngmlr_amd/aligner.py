@@ -415,8 +415,13 @@ class Genome:
         return [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(pos))]
 
     def submit(self, tiles: Sequence, ref_positions) -> "Job":
-        """cvx_submit_windows: the tiles' references are windows of this genome (tile.ref is not uploaded)."""
-        arr, keep = self.al._pack(tiles)
+        """cvx_submit_windows: the tiles' references are windows of this genome (tile.ref is not uploaded).
+        `tiles`: as for ConvexAlignHip.submit, a synth.TileSet or a sequence of Tile objects."""
+        if hasattr(tiles, "table"):
+            tab = tiles.table()
+            arr, keep = tab.ctypes.data_as(C.POINTER(capi.CvxTile)), (tiles, tab)
+        else:
+            arr, keep = self.al._pack(tiles)
         pos = np.ascontiguousarray(ref_positions, dtype=np.uint64)
         j = C.c_void_p()
         capi.check(self.al.lib.cvx_submit_windows(self.al.h, self.g, len(tiles), arr, pos.ctypes.data, C.byref(j)))

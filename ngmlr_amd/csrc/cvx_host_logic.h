@@ -1,6 +1,7 @@
 /*
  * cvx_host_logic.h -- the device-independent half of the host runtime (cvx_rt_align.cpp):
- * how a batch of cvx_tile is laid out and packed for upload, and how the corridor plans that
+ * how a batch of cvx_tile is laid out and packed for upload and which bytes travel to the device when
+ * (build_upload_schedule: blocks that travel as they are, pieces, one record per transfer), and how the corridor plans that
  * come back from plan_kernel are turned into kernel classes, arena offsets and work lists, and
  * those into the compute stage's launch schedule (build_schedule: what is launched, in which order,
  * on which stream, and how each class is walked).
@@ -10,6 +11,7 @@
 #define CVX_HOST_LOGIC_H
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <condition_variable>
 #include <cstdlib>
@@ -61,6 +63,10 @@ static const int kExactDirectSteps = 65536;
 static const int kExactDirectMaxTiles = 4096;
 /* streaming jobs smaller than this alternate between the runtime's two stream sets (cvx_rt_align.cpp, stage_compute) */
 static const int kSmallJobTiles = 2048;
+/* an upload whose host packing moves fewer bytes than this is not worth a thread (build_upload_schedule): one thread, one
+ * piece; above it the batch is packed and copied in kUploadPieces pieces, each piece's copies under the packing of the next */
+static const uint64_t kPackThreadBytes = 8ull << 20;
+static const int kUploadPieces = 8;
 inline int chain_class_for(int need, bool small_batch) {
 	/* measured (C5 mix, 96 tiles): 64-row blocks 100 ms, 128-row 117 ms, 256-row 174 ms -- a tile's
 	 * time is its block count times the lag between neighbouring blocks, and a step of a 64-row block
@@ -407,6 +413,173 @@ inline void expand_rows_host(const RowSrc &rs, int H, const uint8_t *hdelta, con
 		out[y].off = o;
 		out[y].len = rs.width;
 	}
+}
+
+/* The misfits' rows (none in any corridor the reference builds) behind the packing: the lists of all packing ranges, back
+ * to back, are the explicit-rows buffer.  misfit_rows: its entries; place_misfits fills hx (room for that many) and points
+ * every kRowsExplicit tile's src_off -- the tile's step-stream offset until here -- at its rows in it. */
+inline uint64_t misfit_rows(const std::vector<RowOverflow> &overflow) {
+	uint64_t n_x = 0;
+	for (const RowOverflow &o : overflow) n_x += o.rows.size();
+	return n_x;
+}
+inline void place_misfits(const std::vector<RowOverflow> &overflow, const std::vector<TileIn> &tin, std::vector<RowSrc> &rsrc, RowDesc *hx) {
+	uint64_t at = 0;
+	for (const RowOverflow &o : overflow) {
+		uint64_t r = 0;
+		for (int32_t ti : o.tiles) {
+			rsrc[(size_t) ti].src_off = at + r;
+			r += (uint64_t) tin[(size_t) ti].H;
+		}
+		if (!o.rows.empty()) memcpy(hx + at, o.rows.data(), o.rows.size() * sizeof(RowDesc));
+		at += o.rows.size();
+	}
+}
+
+/* ------------------------------------------------------------------ upload schedule */
+
+/* What stage_upload (cvx_rt_align.cpp) moves to the device for a laid-out batch, decided here so that the CPU suite can
+ * check it: which blocks travel as they are, how the batch is cut into pieces, and one record per transfer in issue order.
+ * The stage itself packs a piece, then issues that piece's records. */
+
+enum UploadDst { kToSeq = 0, kToDelta = 1 };            /* the sequence arena, the step-stream arena */
+/* the job's sequence / step staging, the page-locked block of zeros, the caller's block of reads / of references;
+ * kClearOnDevice: no source, the destination is cleared by the device itself */
+enum UploadSrc { kFromSeqStaging = 0, kFromDeltaStaging = 1, kFromZeros = 2, kFromQryBlock = 3, kFromRefBlock = 4, kClearOnDevice = 5 };
+
+struct UploadCopy {
+	int dst = kToSeq, src = kFromSeqStaging;
+	uint64_t dst_off = 0, src_off = 0, len = 0;
+};
+
+struct UploadPiece {
+	int t0 = 0, t1 = 0;              /* tiles packed for this piece */
+	size_t rec0 = 0, rec1 = 0;       /* copies[rec0, rec1): issued once they are packed */
+};
+
+struct UploadSchedule {
+	bool zc_qry = false, zc_ref = false;   /* the block of reads / of references travels straight from the caller's page-locked arena */
+	bool pack_seq = true;                  /* anything left for the host to copy into the sequence staging? */
+	uint64_t zero_copy_bytes = 0;
+	uint64_t pack_work = 0;                /* bytes the host still moves */
+	int threads = 1;                       /* pack threads per piece */
+	uint64_t zero_bytes = 0;               /* size the block of zeros must have (0: not needed) */
+	std::vector<UploadCopy> copies;        /* [0, n_leading): before any packing; then the pieces' ranges; [n_staged, size()): behind the whole upload */
+	size_t n_leading = 0, n_staged = 0;
+	std::vector<UploadPiece> pieces;
+};
+
+/* L, tin: of upload_layout, L.rsrc not yet packed (the step-stream cut-offs read src_off); qry_pinned / ref_pinned: the
+ * caller's block of reads / references (qry_bytes + 4 / ref_bytes + 4 bytes from the first tile's pointer) lies inside one
+ * page-locked block; threads_on_offer: pack threads the handle may use. */
+inline void build_upload_schedule(const UploadLayout &L, const std::vector<TileIn> &tin, int n, bool qry_pinned, bool ref_pinned,
+		int threads_on_offer, UploadSchedule &s, uint64_t thread_bytes = kPackThreadBytes) {
+	const bool windows = L.windows;
+	/* a block of sequences that already lies back to back in page-locked memory is not packed: the
+	 * device pulls it out of the caller's arena (the job's staging then holds only what the host wrote) */
+	s.zc_qry = n > 0 && L.qry_contig && L.qry_bytes > 0 && qry_pinned;
+	s.zc_ref = n > 0 && !windows && L.ref_contig && L.ref_bytes > 0 && ref_pinned;
+	s.zero_copy_bytes = (s.zc_qry ? L.qry_bytes : 0) + (s.zc_ref ? L.ref_bytes : 0);
+	s.pack_seq = !(s.zc_qry && (s.zc_ref || windows));
+	s.copies.clear(); s.pieces.clear();
+	auto add = [&](int dst, int src, uint64_t dst_off, uint64_t src_off, uint64_t len) { s.copies.push_back(UploadCopy{dst, src, dst_off, src_off, len}); };
+	/* the three pads: uploaded with the packed blocks (upload_zero_pads wrote them into the staging), or copied from zeros
+	 * around the blocks that travel as they are (queued in front of those copies: a copy rounded up to whole dwords may
+	 * spill a few bytes into the pad that follows) */
+	s.zero_bytes = 0;
+	if (s.zc_qry || s.zc_ref) {
+		/* Pads around blocks that travel as they are: copied from a page-locked block of zeros, whole 256-byte
+		 * units (SDMA engines; a memset would be a kernel that has to find wave slots beside the fill), queued
+		 * BEFORE the blocks, which then overwrite the few bytes of overlap.  A block's own copy is rounded up to
+		 * whole dwords: up to three bytes of whatever follows it in the caller's arena land in the pad behind it --
+		 * pads only have to be readable (every cell outside a tile is forced to the empty element), not zero. */
+		const uint64_t zmax = L.pad + 1024;
+		s.zero_bytes = zmax;
+		auto zero_range = [&](uint64_t lo, uint64_t hi) {      /* [lo, hi) widened to 256-byte units, inside the arena */
+			lo = lo / 256 * 256;
+			hi = std::min<uint64_t>((hi + 255) / 256 * 256, (L.seq_total + 255) / 256 * 256);
+			for (uint64_t at = lo; at < hi; at += zmax / 256 * 256)
+				add(kToSeq, kFromZeros, at, 0, std::min<uint64_t>(hi - at, zmax / 256 * 256));
+		};
+		if (s.zc_qry) {
+			zero_range(0, L.qry_base);
+			zero_range(L.qry_base + L.qry_bytes, L.ref_base);
+			add(kToSeq, kFromQryBlock, L.qry_base, 0, (L.qry_bytes + 3) / 4 * 4);
+		}
+		if (s.zc_ref) {
+			zero_range(L.ref_base + L.ref_bytes, L.seq_total);
+			add(kToSeq, kFromRefBlock, L.ref_base, 0, (L.ref_bytes + 3) / 4 * 4);
+		}
+	}
+	s.n_leading = s.copies.size();
+	/* what the host still moves per tile decides whether packing is worth threads and pieces */
+	s.pack_work = L.delta_total * 9ull;
+	if (!s.zc_qry) s.pack_work += L.qry_bytes;
+	if (!s.zc_ref && !windows) s.pack_work += L.ref_bytes;
+	s.threads = std::max(1, threads_on_offer);
+	if (s.pack_work < thread_bytes) s.threads = 1;      /* not worth a thread below ~8 MB */
+	const int pieces = s.threads > 1 ? kUploadPieces : 1;
+	const std::vector<uint64_t> &wprefix = L.wprefix;
+	int t0 = 0;
+	/* bytes of the two blocks of the sequence staging / of the step staging already on their way (block A = [pad][reads][pad], block B = [references][pad]) */
+	uint64_t a_done = 0, b_done = L.ref_base, delta_done = 0;
+	const uint64_t a_end_all = L.ref_base, b_end_all = (L.seq_total + 255) / 256 * 256;
+	for (int pc = 1; pc <= pieces; ++pc) {
+		int t1 = n;
+		if (pc < pieces) {
+			const uint64_t target = wprefix[(size_t) n] / (uint64_t) pieces * (uint64_t) pc;
+			t1 = (int) (std::upper_bound(wprefix.begin(), wprefix.end(), target) - wprefix.begin());
+			t1 = std::min(std::max(t1, t0), n);
+		}
+		const size_t rec0 = s.copies.size();
+		/* Copy boundaries are multiples of 256 bytes: a host-to-device copy whose address or size is
+		 * not dword-aligned is not handed to the SDMA engines but to a blit kernel that pulls the bytes
+		 * over PCIe with compute units the fill needs.  The bytes below the rounded-down end are all
+		 * packed (tiles are laid out in order inside either block); the remainder travels with the next
+		 * piece, the last piece runs to the aligned end. */
+		if (!s.zc_qry) {
+			const uint64_t a_end = (t1 == n) ? a_end_all : (uint64_t) tin[(size_t) t1].qry_off / 256 * 256;
+			if (a_end > a_done) add(kToSeq, kFromSeqStaging, a_done, a_done, a_end - a_done);
+			a_done = std::max(a_done, a_end);
+		}
+		if (!s.zc_ref && !windows) {
+			const uint64_t b_end = (t1 == n) ? b_end_all : (uint64_t) tin[(size_t) t1].ref_off / 256 * 256;
+			if (b_end > b_done) add(kToSeq, kFromSeqStaging, b_done, b_done, b_end - b_done);
+			b_done = std::max(b_done, b_end);
+		}
+		if (L.delta_total) {
+			uint64_t del_end = L.delta_total;
+			if (t1 < n) {        /* first tile at or after t1 whose rows travel as steps (src_off = step-stream offset until the misfits are renumbered, place_misfits) */
+				int q = t1;
+				while (q < n && L.rsrc[(size_t) q].fmt != kRowsDelta8 && L.rsrc[(size_t) q].fmt != kRowsExplicit) q++;
+				if (q < n) del_end = L.rsrc[(size_t) q].src_off;
+			}
+			del_end = (t1 == n) ? (del_end + 255) / 256 * 256 : del_end / 256 * 256;
+			if (del_end > delta_done) add(kToDelta, kFromDeltaStaging, delta_done, delta_done, del_end - delta_done);
+			delta_done = std::max(delta_done, del_end);
+		}
+		s.pieces.push_back(UploadPiece{t0, t1, rec0, s.copies.size()});
+		t0 = t1;
+	}
+	s.n_staged = s.copies.size();
+	/* windows: the references are decoded on the device straight into the arena, and the pad behind them is cleared there */
+	if (windows && n) add(kToSeq, kClearOnDevice, L.ref_base + L.ref_bytes, 0, L.seq_total - L.ref_base - L.ref_bytes);
+}
+
+/* Packs one piece of the schedule into the staging arenas on the schedule's pack threads (upload_pack per range);
+ * every packing range of the piece collects the rows of its misfits in its own list, appended to `overflow`. */
+inline void upload_pack_piece(const UploadSchedule &s, const UploadPiece &p, const cvx_tile *tiles, const std::vector<TileIn> &tin,
+		UploadLayout &L, uint8_t *hseq, uint8_t *hdelta, std::vector<RowOverflow> &overflow) {
+	if (p.t1 <= p.t0 || s.pack_work == 0) return;
+	std::vector<uint64_t> wp((size_t) (p.t1 - p.t0) + 1);
+	for (int i = p.t0; i <= p.t1; ++i) wp[(size_t) (i - p.t0)] = L.wprefix[(size_t) i] - L.wprefix[(size_t) p.t0];
+	const int base = p.t0;
+	const size_t first = overflow.size();
+	overflow.resize(first + (size_t) s.threads + 1);
+	std::atomic<int> slot(0);
+	parallel_ranges(p.t1 - p.t0, wp, s.threads, [&](int bg, int en) {
+		upload_pack(base + bg, base + en, tiles, tin, hseq, hdelta, L.rsrc, overflow[first + (size_t) slot.fetch_add(1)], !s.zc_qry, !s.zc_ref && !L.windows);
+	});
 }
 
 /* ------------------------------------------------------------------ host planning */

@@ -3,7 +3,8 @@
  * A batch of tiles moves through four stages:
  *
  *   upload   host threads pack sequences + corridor rows into the batch's own pinned staging,
- *            piece by piece, each piece's DMA running under the packing of the next  (stream `io`)
+ *            piece by piece, each piece's DMA running under the packing of the next  (stream `io`;
+ *            what travels when and from where: build_upload_schedule, cvx_host_logic.h)
  *   plan     plan_kernel, plan records back to pinned memory                          (stream `io`)
  *   compute  host: kernel class / arena offsets / LPT lists from the plan records, then the launch schedule
  *            (build_schedule, cvx_host_logic.h: list contents, one record per fill launch, stream slots, walk lanes);
@@ -135,128 +136,49 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	RC_TRY(b->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
 	if (n) memcpy(b->h_tin.p, tin.data(), (size_t) n * sizeof(TileIn));
 
-	/* a block of sequences that already lies back to back in page-locked memory is not packed: the
-	 * device pulls it out of the caller's arena (the job's staging then holds only what the host wrote) */
-	const bool zc_qry = n > 0 && L.qry_contig && L.qry_bytes > 0 && in_pinned_block(tiles[0].qry, L.qry_bytes + 4);
-	const bool zc_ref = n > 0 && !windows && L.ref_contig && L.ref_bytes > 0 && in_pinned_block(tiles[0].ref, L.ref_bytes + 4);
-	b->zero_copy_bytes = (zc_qry ? L.qry_bytes : 0) + (zc_ref ? L.ref_bytes : 0);
-	const bool pack_seq = !(zc_qry && (zc_ref || windows));      /* anything left for the host to copy? */
-	if (pack_seq) RC_TRY(b->h_seq.ensure((size_t) L.seq_total + 256));
+	/* which bytes travel when, and from where: build_upload_schedule (cvx_host_logic.h); here only its questions to the
+	 * runtime (does a block of the caller's lie in page-locked memory?) and the issuing */
+	const bool qry_pinned = L.qry_contig && in_pinned_block(tiles[0].qry, L.qry_bytes + 4);      /* (contiguous: n > 0) */
+	const bool ref_pinned = L.ref_contig && in_pinned_block(tiles[0].ref, L.ref_bytes + 4);
+	UploadSchedule sch;
+	build_upload_schedule(L, tin, n, qry_pinned, ref_pinned, std::min(h->pack_threads, PackPool::get().size()), sch);
+	b->zero_copy_bytes = sch.zero_copy_bytes;
+	if (sch.pack_seq) RC_TRY(b->h_seq.ensure((size_t) L.seq_total + 256));
 	uint8_t *hseq = b->h_seq.as<uint8_t>();
 	uint8_t *hdelta = b->h_delta.as<uint8_t>();
-	std::vector<RowOverflow> overflow;
-	hipStream_t st = h->s_io;
-	/* the three pads: uploaded with the packed blocks, or cleared on the device around the blocks that travel as they are
-	 * (queued behind those copies: a copy rounded up to whole dwords may spill a few bytes into the pad that follows) */
-	if (pack_seq) upload_zero_pads(L, hseq);
-	if (zc_qry || zc_ref) {
-		/* Pads around blocks that travel as they are: copied from a page-locked block of zeros, whole 256-byte
-		 * units (SDMA engines; a memset would be a kernel that has to find wave slots beside the fill), queued
-		 * BEFORE the blocks, which then overwrite the few bytes of overlap.  A block's own copy is rounded up to
-		 * whole dwords: up to three bytes of whatever follows it in the caller's arena land in the pad behind it --
-		 * pads only have to be readable (every cell outside a tile is forced to the empty element), not zero. */
-		const uint64_t zmax = L.pad + 1024;
-		RC_TRY(b->h_zero.ensure((size_t) zmax));
+	if (sch.pack_seq) upload_zero_pads(L, hseq);
+	if (sch.zero_bytes) {
+		RC_TRY(b->h_zero.ensure((size_t) sch.zero_bytes));
 		if (b->zero_cap != b->h_zero.cap) { memset(b->h_zero.p, 0, b->h_zero.cap); b->zero_cap = b->h_zero.cap; }
-		auto zero_range = [&](uint64_t lo, uint64_t hi) -> int {      /* [lo, hi) widened to 256-byte units, inside the arena */
-			lo = lo / 256 * 256;
-			hi = std::min<uint64_t>((hi + 255) / 256 * 256, (L.seq_total + 255) / 256 * 256);
-			for (uint64_t at = lo; at < hi; at += zmax / 256 * 256) {
-				const uint64_t len = std::min<uint64_t>(hi - at, zmax / 256 * 256);
-				HIP_TRY(hipMemcpyAsync(b->d_seq.p + at, b->h_zero.p, (size_t) len, hipMemcpyHostToDevice, st));
-			}
-			return CVX_OK;
-		};
-		if (zc_qry) {
-			RC_TRY(zero_range(0, L.qry_base));
-			RC_TRY(zero_range(L.qry_base + L.qry_bytes, L.ref_base));
-			HIP_TRY(hipMemcpyAsync(b->d_seq.p + L.qry_base, tiles[0].qry, (size_t) ((L.qry_bytes + 3) / 4 * 4), hipMemcpyHostToDevice, st));
-		}
-		if (zc_ref) {
-			RC_TRY(zero_range(L.ref_base + L.ref_bytes, L.seq_total));
-			HIP_TRY(hipMemcpyAsync(b->d_seq.p + L.ref_base, tiles[0].ref, (size_t) ((L.ref_bytes + 3) / 4 * 4), hipMemcpyHostToDevice, st));
-		}
 	}
-	/* what the host still moves per tile decides whether packing is worth threads and pieces */
-	uint64_t pack_work = L.delta_total * 9ull;
-	if (!zc_qry) pack_work += L.qry_bytes;
-	if (!zc_ref && !windows) pack_work += L.ref_bytes;
-	const std::vector<uint64_t> &wprefix = L.wprefix;
-	int threads = std::max(1, std::min(h->pack_threads, PackPool::get().size()));
-	if (pack_work < (8u << 20)) threads = 1;      /* not worth a thread below ~8 MB */
-	const int pieces = threads > 1 ? 8 : 1;
-	int t0 = 0;
-	/* bytes of the two blocks of hseq / of hdelta already on their way (block A = [pad][reads][pad], block B = [references][pad]) */
-	uint64_t a_done = 0, b_done = L.ref_base, delta_done = 0;
-	const uint64_t a_end_all = L.ref_base, b_end_all = (L.seq_total + 255) / 256 * 256;
-	for (int pc = 1; pc <= pieces; ++pc) {
-		int t1 = n;
-		if (pc < pieces) {
-			const uint64_t target = wprefix[(size_t) n] / (uint64_t) pieces * (uint64_t) pc;
-			t1 = (int) (std::upper_bound(wprefix.begin(), wprefix.end(), target) - wprefix.begin());
-			t1 = std::min(std::max(t1, t0), n);
+	hipStream_t st = h->s_io;
+	const void *const from[] = { hseq, hdelta, b->h_zero.p, n ? tiles[0].qry : nullptr, n ? tiles[0].ref : nullptr };      /* UploadSrc */
+	auto issue = [&](size_t r0, size_t r1) -> int {
+		for (size_t r = r0; r < r1; ++r) {
+			const UploadCopy &c = sch.copies[r];
+			uint8_t *dst = (c.dst == kToSeq ? b->d_seq.p : b->d_delta.p) + c.dst_off;
+			if (c.src == kClearOnDevice) HIP_TRY(hipMemsetAsync(dst, 0, (size_t) c.len, st));
+			else HIP_TRY(hipMemcpyAsync(dst, static_cast<const uint8_t *>(from[c.src]) + c.src_off, (size_t) c.len, hipMemcpyHostToDevice, st));
 		}
-		if (t1 > t0 && pack_work > 0) {
-			std::vector<uint64_t> wp((size_t) (t1 - t0) + 1);
-			for (int i = t0; i <= t1; ++i) wp[(size_t) (i - t0)] = wprefix[(size_t) i] - wprefix[(size_t) t0];
-			const int base = t0;
-			/* every packing range of the piece collects the rows of its misfits in its own list */
-			const size_t first = overflow.size();
-			overflow.resize(first + (size_t) threads + 1);
-			std::atomic<int> slot(0);
-			parallel_ranges(t1 - t0, wp, threads, [&](int bg, int en) {
-				upload_pack(base + bg, base + en, tiles, tin, hseq, hdelta, L.rsrc, overflow[first + (size_t) slot.fetch_add(1)], !zc_qry, !zc_ref && !windows);
-			});
-		}
-		/* Copy boundaries are multiples of 256 bytes: a host-to-device copy whose address or size is
-		 * not dword-aligned is not handed to the SDMA engines but to a blit kernel that pulls the bytes
-		 * over PCIe with compute units the fill needs.  The bytes below the rounded-down end are all
-		 * packed (tiles are laid out in order inside either block); the remainder travels with the next
-		 * piece, the last piece runs to the aligned end. */
-		if (!zc_qry) {
-			const uint64_t a_end = (t1 == n) ? a_end_all : (uint64_t) tin[(size_t) t1].qry_off / 256 * 256;
-			if (a_end > a_done) HIP_TRY(hipMemcpyAsync(b->d_seq.p + a_done, hseq + a_done, (size_t) (a_end - a_done), hipMemcpyHostToDevice, st));
-			a_done = std::max(a_done, a_end);
-		}
-		if (!zc_ref && !windows) {
-			const uint64_t b_end = (t1 == n) ? b_end_all : (uint64_t) tin[(size_t) t1].ref_off / 256 * 256;
-			if (b_end > b_done) HIP_TRY(hipMemcpyAsync(b->d_seq.p + b_done, hseq + b_done, (size_t) (b_end - b_done), hipMemcpyHostToDevice, st));
-			b_done = std::max(b_done, b_end);
-		}
-		if (L.delta_total) {
-			uint64_t del_end = L.delta_total;
-			if (t1 < n) {        /* first tile at or after t1 whose rows travel as steps (src_off = step-stream offset until the misfits are renumbered below) */
-				int q = t1;
-				while (q < n && L.rsrc[(size_t) q].fmt != kRowsDelta8 && L.rsrc[(size_t) q].fmt != kRowsExplicit) q++;
-				if (q < n) del_end = L.rsrc[(size_t) q].src_off;
-			}
-			del_end = (t1 == n) ? (del_end + 255) / 256 * 256 : del_end / 256 * 256;
-			if (del_end > delta_done)
-				HIP_TRY(hipMemcpyAsync(b->d_delta.p + delta_done, hdelta + delta_done, (size_t) (del_end - delta_done), hipMemcpyHostToDevice, st));
-			delta_done = std::max(delta_done, del_end);
-		}
-		t0 = t1;
+		return CVX_OK;
+	};
+	RC_TRY(issue(0, sch.n_leading));
+	/* piece p's copies are queued before piece p + 1 is packed: they run under that packing */
+	std::vector<RowOverflow> overflow;
+	for (const UploadPiece &pc : sch.pieces) {
+		upload_pack_piece(sch, pc, tiles, tin, L, hseq, hdelta, overflow);
+		RC_TRY(issue(pc.rec0, pc.rec1));
 	}
 	if (n) HIP_TRY(hipMemcpyAsync(b->d_tin.p, b->h_tin.p, (size_t) n * sizeof(TileIn), hipMemcpyHostToDevice, st));
 	if (n) {
 		/* the misfits' rows (none in any corridor the reference builds), then the rows arena on the device */
-		uint64_t n_x = 0;
-		for (const RowOverflow &o : overflow) n_x += o.rows.size();
+		const uint64_t n_x = misfit_rows(overflow);
 		b->n_rowsx = n_x;
 		if (n_x) {
 			RC_TRY(b->h_rowsx.ensure((size_t) n_x * sizeof(RowDesc)));
 			RC_TRY(b->d_rowsx.ensure((size_t) n_x));
 			RowDesc *hx = b->h_rowsx.as<RowDesc>();
-			uint64_t at = 0;
-			for (const RowOverflow &o : overflow) {
-				uint64_t r = 0;
-				for (int32_t ti : o.tiles) {
-					L.rsrc[(size_t) ti].src_off = at + r;
-					r += (uint64_t) tin[(size_t) ti].H;
-				}
-				if (!o.rows.empty()) memcpy(hx + at, o.rows.data(), o.rows.size() * sizeof(RowDesc));
-				at += o.rows.size();
-			}
+			place_misfits(overflow, tin, L.rsrc, hx);
 			HIP_TRY(hipMemcpyAsync(b->d_rowsx.p, hx, (size_t) n_x * sizeof(RowDesc), hipMemcpyHostToDevice, st));
 		}
 		memcpy(b->h_rsrc.p, L.rsrc.data(), (size_t) n * sizeof(RowSrc));
@@ -275,7 +197,7 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 			hw[i].n_chars = tiles[i].ref_len;
 		}
 		HIP_TRY(hipMemcpyAsync(b->d_win.p, hw, (size_t) n * sizeof(WindowDesc), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemsetAsync(b->d_seq.p + L.ref_base + L.ref_bytes, 0, (size_t) (L.seq_total - L.ref_base - L.ref_bytes), st));
+		RC_TRY(issue(sch.n_staged, sch.copies.size()));
 		HIP_TRY(launch_decode_windows(genome->d_bin.p, genome->d_starts.p, genome->n_starts, b->d_win.p, n, b->d_seq.p, st));
 		/* the decoded characters back to the host, 1 byte per reference base under everything that follows: a caller whose
 		 * text stage runs on the host (MD needs the reference base of every mismatch and deletion) reads them there
@@ -901,8 +823,8 @@ int cvx_corridor_rows(cvx_handle h, const cvx_tile *tile, int32_t *offset, int32
 int cvx_pack_probe(int32_t n, const cvx_tile *tiles, int32_t iters, int32_t assume_page_locked, double *ms_per_iter, uint64_t *bytes_touched) {
 	ABI_GUARD_BEGIN
 	if (n < 0 || (n > 0 && !tiles) || iters <= 0 || !ms_per_iter) { set_err("cvx_pack_probe: bad argument"); return CVX_ERR_ARG; }
-	/* what stage_upload does on the host, minus every HIP call: layout, packing into (ordinary) staging on the
-	 * process's pack threads.  Nothing is aligned -- this measures the submit side, it computes nothing. */
+	/* what stage_upload does on the host, minus every HIP call: layout, the upload schedule, its pieces packed into
+	 * (ordinary) staging on the process's pack threads.  Nothing is aligned -- this measures the submit side, it computes nothing. */
 	std::vector<uint8_t> hseq, hdelta;
 	uint64_t touched = 0;
 	const auto c0 = std::chrono::steady_clock::now();
@@ -912,19 +834,13 @@ int cvx_pack_probe(int32_t n, const cvx_tile *tiles, int32_t iters, int32_t assu
 		int bad = -1;
 		const int lrc = upload_layout(n, tiles, tin, L, &bad, false);
 		if (lrc != kLayoutOk) { set_err("cvx_pack_probe: tile %d malformed / batch too large", bad); return CVX_ERR_ARG; }
-		const bool zc_qry = assume_page_locked && L.qry_contig, zc_ref = assume_page_locked && L.ref_contig;
+		UploadSchedule sch;
+		build_upload_schedule(L, tin, n, assume_page_locked != 0, assume_page_locked != 0, PackPool::get().size(), sch);
 		if (hseq.size() < L.seq_total + 256) hseq.resize((size_t) L.seq_total + 256);
 		if (hdelta.size() < L.delta_total + 256) hdelta.resize((size_t) L.delta_total + 256);
-		uint64_t pack_work = L.delta_total * 9ull + (zc_qry ? 0 : L.qry_bytes) + (zc_ref ? 0 : L.ref_bytes);
-		int threads = PackPool::get().size();
-		if (pack_work < (8u << 20)) threads = 1;
-		std::vector<RowOverflow> overflow((size_t) threads + 1);
-		std::atomic<int> slot(0);
-		if (pack_work > 0)
-			parallel_ranges(n, L.wprefix, threads, [&](int bg, int en) {
-				upload_pack(bg, en, tiles, tin, hseq.data(), hdelta.data(), L.rsrc, overflow[(size_t) slot.fetch_add(1)], !zc_qry, !zc_ref);
-			});
-		touched = 2 * ((zc_qry ? 0 : L.qry_bytes) + (zc_ref ? 0 : L.ref_bytes)) + L.delta_total * 9ull + (uint64_t) n * (sizeof(TileIn) + sizeof(RowSrc) + sizeof(cvx_tile));
+		std::vector<RowOverflow> overflow;
+		for (const UploadPiece &pc : sch.pieces) upload_pack_piece(sch, pc, tiles, tin, L, hseq.data(), hdelta.data(), overflow);
+		touched = 2 * ((sch.zc_qry ? 0 : L.qry_bytes) + (sch.zc_ref ? 0 : L.ref_bytes)) + L.delta_total * 9ull + (uint64_t) n * (sizeof(TileIn) + sizeof(RowSrc) + sizeof(cvx_tile));
 	}
 	const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - c0).count();
 	*ms_per_iter = dt * 1e3 / iters;

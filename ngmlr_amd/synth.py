@@ -331,8 +331,8 @@ DESC_DTYPE = np.dtype([("kind", np.int32), ("k", np.float32), ("d", np.float32),
 class TileSet:
     """n tiles in flat arrays: ref / qry bytes back to back in tile order, one (offset, length) per read row, and
     (optionally) the closed form of every corridor.  `closed_form`: the tile table hands the C ABI the closed forms
-    instead of the row arrays.  pin(lib): the sequences move into page-locked memory (cvx_host_alloc), from where the
-    device pulls them without any packing on the host."""
+    instead of the row arrays.  pin(lib): the sequences (or one of the two blocks) move into page-locked memory
+    (cvx_host_alloc), from where the device pulls them without any packing on the host."""
 
     def __init__(self, ref, ref_off, qry, qry_off, row_offset, row_length, tag="", desc=None):
         self.ref, self.ref_off = ref, ref_off
@@ -376,33 +376,35 @@ class TileSet:
         self.closed_form, self._table = bool(on), None
         return self
 
-    def pin(self, lib) -> bool:
-        """Moves ref / qry into page-locked arenas from cvx_host_alloc (False, nothing changed, when that fails: no device)."""
+    def pin(self, lib, which=("ref", "qry")) -> bool:
+        """Moves ref / qry (`which`: either or both) into page-locked arenas from cvx_host_alloc (False, nothing changed, when
+        that fails: no device)."""
         import ctypes as C
         if self._pinned is not None:
             return True
+        names = [name for name in ("ref", "qry") if name in which]
         ptrs = []
-        for arr in (self.ref, self.qry):
+        for name in names:
             p = C.c_void_p()
-            if lib.cvx_host_alloc(max(int(arr.nbytes), 1), C.byref(p)) != 0:
+            if lib.cvx_host_alloc(max(int(getattr(self, name).nbytes), 1), C.byref(p)) != 0:
                 for q in ptrs:
                     lib.cvx_host_free(q)
                 return False
             ptrs.append(p)
-        views = []
-        for p, arr in zip(ptrs, (self.ref, self.qry)):
+        for p, name in zip(ptrs, names):
+            arr = getattr(self, name)
             v = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(max(int(arr.nbytes), 1),))[:arr.nbytes]
             v[:] = arr
-            views.append(v)
-        self.ref, self.qry = views
-        self._pinned = (lib, ptrs)
+            setattr(self, name, v)
+        self._pinned = (lib, ptrs, names)
         self._table = None
         return True
 
     def unpin(self) -> None:
         if self._pinned is not None:
-            lib, ptrs = self._pinned
-            self.ref, self.qry = self.ref.copy(), self.qry.copy()
+            lib, ptrs, names = self._pinned
+            for name in names:
+                setattr(self, name, getattr(self, name).copy())
             for p in ptrs:
                 lib.cvx_host_free(p)
             self._pinned, self._table = None, None

@@ -1,7 +1,8 @@
 // CPU test of the device-independent host logic (ngmlr_amd/csrc/cvx_host_logic.h): upload layout and
 // packing (ragged, empty and strided tiles, multi-threaded == single-threaded), kernel-class choice,
 // arena offsets and the LPT work lists, and the compute stage's launch schedule (list contents, launch order, stream slots,
-// residency cap of chained classes, lanes of the backtrack walks).  Built with plain g++ by tests/test_host_logic_cpu.py.
+// residency cap of chained classes, lanes of the backtrack walks), and the upload stage's copy schedule (executed with memcpy in
+// place of the device: final arena contents, 256-byte grid, pads, order, the parent's sequences of transfers).  Built with plain g++ by tests/test_host_logic_cpu.py.
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +18,291 @@ static int fails = 0;
 #define CHECK(c) do { if (!(c)) { printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #c); ++fails; } } while (0)
 
 struct CorridorLine16 { int32_t offset, length; uint64_t offsetInMatrix; };   // the reference's 16-byte row
+
+// ---------------------------------------------------------------- the upload schedule, executed with memcpy in place of the device
+
+// a batch as a caller with two arenas hands it over: reads and references back to back in tile order, some non-zero bytes
+// behind either block (what a copy rounded up to dwords picks up), one (offset, length) array pair per tile
+enum { kFits = 0, kClosed = 1, kWidthChange = 2, kBigStep = 3 };      // a tile's corridor: rows in the one-byte form, a closed form, two kinds of misfit
+struct UpBatch {
+	std::vector<uint8_t> qry_block, ref_block;
+	std::vector<std::vector<int32_t>> off, len;
+	std::vector<cvx_tile> tiles;
+	uint64_t qry_bytes = 0, ref_bytes = 0;
+};
+static void make_batch(UpBatch &b, const std::vector<int> &W, const std::vector<int> &H, const std::vector<int> &kind, bool windows) {
+	const int n = (int) W.size();
+	for (int i = 0; i < n; ++i) { b.qry_bytes += (uint64_t) H[i]; b.ref_bytes += (uint64_t) W[i]; }
+	b.qry_block.assign(b.qry_bytes + 8, 0xEE); b.ref_block.assign(b.ref_bytes + 8, 0xEE);
+	for (uint64_t k = 0; k < b.qry_bytes; ++k) b.qry_block[k] = (uint8_t) (1 + k % 61);
+	for (uint64_t k = 0; k < b.ref_bytes; ++k) b.ref_block[k] = (uint8_t) (70 + k % 53);
+	b.off.resize(n); b.len.resize(n); b.tiles.resize(n);
+	uint64_t q = 0, r = 0;
+	for (int i = 0; i < n; ++i) {
+		cvx_tile &t = b.tiles[i];
+		memset(&t, 0, sizeof(t));
+		t.qry = reinterpret_cast<const char *>(b.qry_block.data() + q); t.qry_len = H[i]; q += (uint64_t) H[i];
+		t.ref = windows ? nullptr : reinterpret_cast<const char *>(b.ref_block.data() + r); t.ref_len = W[i]; r += (uint64_t) W[i];
+		if (kind[i] == kClosed) { t.corridor_kind = CVX_CORRIDOR_CONST; t.corridor_width = 40 + i % 9; t.corridor_offset = -7; continue; }
+		b.off[i].resize((size_t) H[i] + 1); b.len[i].resize((size_t) H[i] + 1);      // (+ 1: a pointer for H = 0 too)
+		for (int y = 0; y < H[i]; ++y) {
+			b.off[i][y] = y - 20 + (y * 7 + i) % 3 + (kind[i] == kBigStep && y > H[i] / 2 ? 500 : 0);
+			b.len[i][y] = 50 + (kind[i] == kWidthChange && y == H[i] - 1 ? 1 : 0);
+		}
+		t.row_offset = b.off[i].data(); t.row_length = b.len[i].data(); t.row_stride_bytes = 4;
+	}
+}
+
+struct UpCase { bool windows = false, qry_pinned = false, ref_pinned = false; int threads = 1; uint64_t thread_bytes = kPackThreadBytes; };
+
+// executes the schedule of a case and checks it against one single-threaded packing of the whole batch; returns the schedule
+static UploadSchedule run_upload(const UpBatch &b, const UpCase &c, const char *name) {
+	const int before = fails;
+	const int n = (int) b.tiles.size();
+	const cvx_tile *tiles = n ? b.tiles.data() : nullptr;
+	UploadLayout L;
+	std::vector<TileIn> tin;
+	int bad = -1;
+	CHECK(upload_layout(n, tiles, tin, L, &bad, c.windows) == kLayoutOk);
+	const std::vector<RowSrc> rsrc0 = L.rsrc;
+	UploadSchedule s;
+	build_upload_schedule(L, tin, n, c.qry_pinned, c.ref_pinned, c.threads, s, c.thread_bytes);
+
+	// the flags and sizes: the expressions stage_upload has always used
+	const bool zc_qry = n > 0 && L.qry_contig && L.qry_bytes > 0 && c.qry_pinned;
+	const bool zc_ref = n > 0 && !c.windows && L.ref_contig && L.ref_bytes > 0 && c.ref_pinned;
+	CHECK(s.zc_qry == zc_qry && s.zc_ref == zc_ref);
+	CHECK(s.zero_copy_bytes == (zc_qry ? L.qry_bytes : 0) + (zc_ref ? L.ref_bytes : 0));
+	CHECK(s.pack_seq == !(zc_qry && (zc_ref || c.windows)));
+	CHECK(s.pack_work == L.delta_total * 9ull + (zc_qry ? 0 : L.qry_bytes) + (zc_ref || c.windows ? 0 : L.ref_bytes));
+	CHECK(s.threads == (s.pack_work < c.thread_bytes ? 1 : std::max(1, c.threads)));
+	CHECK(s.pieces.size() == (size_t) (s.threads > 1 ? kUploadPieces : 1));
+	CHECK((s.zero_bytes != 0) == (zc_qry || zc_ref));
+	// pieces: consecutive tile ranges over [0, n), consecutive record ranges between the leading records and the tail
+	{
+		int t = 0;
+		size_t r = s.n_leading;
+		for (const UploadPiece &p : s.pieces) { CHECK(p.t0 == t && p.t1 >= p.t0 && p.rec0 == r && p.rec1 >= p.rec0); t = p.t1; r = p.rec1; }
+		CHECK(t == n && r == s.n_staged && s.n_staged <= s.copies.size());
+	}
+
+	// the device arenas and the job's staging: poison everywhere but where upload_zero_pads writes
+	const uint64_t seq_cap = L.seq_total + 256, delta_cap = L.delta_total + 256;       // what stage_upload ensures
+	std::vector<uint8_t> dseq(seq_cap, 0xCD), ddelta(delta_cap, 0xCD), hseq(seq_cap, 0xCD), hdelta(delta_cap, 0xCD), zeros(s.zero_bytes, 0);
+	if (s.pack_seq) upload_zero_pads(L, hseq.data());
+	const uint8_t *from[] = { hseq.data(), hdelta.data(), zeros.data(), b.qry_block.data(), b.ref_block.data() };
+	const uint64_t from_cap[] = { seq_cap, delta_cap, s.zero_bytes, L.qry_bytes + 4, L.ref_bytes + 4, 0 };      // (a block: what in_pinned_block was asked about)
+	std::vector<uint8_t> by_host(L.seq_total + 256, 0);      // arena bytes written by staged / zero / clear records
+	auto apply = [&](size_t r0, size_t r1) {
+		for (size_t r = r0; r < r1; ++r) {
+			const UploadCopy &u = s.copies[r];
+			std::vector<uint8_t> &dst = u.dst == kToSeq ? dseq : ddelta;
+			CHECK(u.dst == kToSeq || u.dst == kToDelta);
+			CHECK(u.len > 0 && u.dst_off + u.len <= dst.size());
+			if (u.dst_off + u.len > dst.size()) continue;
+			if (u.src == kClearOnDevice) { memset(dst.data() + u.dst_off, 0, u.len); }
+			else {
+				CHECK(u.src >= kFromSeqStaging && u.src <= kFromRefBlock && u.src_off + u.len <= from_cap[u.src]);
+				if (u.src_off + u.len > from_cap[u.src]) continue;
+				memcpy(dst.data() + u.dst_off, from[u.src] + u.src_off, u.len);
+			}
+			const bool block = u.src == kFromQryBlock || u.src == kFromRefBlock;
+			if (block) {
+				const uint64_t bytes = u.src == kFromQryBlock ? L.qry_bytes : L.ref_bytes;
+				CHECK(u.dst == kToSeq && u.src_off == 0 && u.dst_off == (u.src == kFromQryBlock ? L.qry_base : L.ref_base));
+				CHECK(u.dst_off % 256 == 0 && u.len % 4 == 0 && u.len >= bytes && u.len < bytes + 4);
+			} else if (u.src == kClearOnDevice) {
+				CHECK(c.windows && u.dst == kToSeq && r >= s.n_staged);
+			} else {
+				CHECK(u.dst_off % 256 == 0 && u.len % 256 == 0);
+				CHECK((u.src == kFromDeltaStaging) == (u.dst == kToDelta));
+				if (u.src != kFromZeros) CHECK(u.src_off == u.dst_off && r >= s.n_leading && r < s.n_staged);
+				else CHECK(r < s.n_leading);
+			}
+			if (!block && u.dst == kToSeq) for (uint64_t k = 0; k < u.len; ++k) by_host[u.dst_off + k] = 1;
+		}
+	};
+	apply(0, s.n_leading);
+	std::vector<RowOverflow> overflow;
+	for (const UploadPiece &p : s.pieces) {
+		upload_pack_piece(s, p, tiles, tin, L, hseq.data(), hdelta.data(), overflow);      // this piece only: a record that runs ahead copies poison
+		apply(p.rec0, p.rec1);
+	}
+	apply(s.n_staged, s.copies.size());
+
+	// the reference: pads + one single-threaded packing of everything
+	std::vector<uint8_t> rseq(seq_cap, 0xCD), rdelta(delta_cap, 0xCD);
+	std::vector<RowSrc> rs = rsrc0;
+	RowOverflow ro;
+	upload_zero_pads(L, rseq.data());
+	if (c.windows && n) memset(rseq.data() + L.ref_base + L.ref_bytes, 0, L.seq_total - L.ref_base - L.ref_bytes);      // (cleared on the device)
+	upload_pack(0, n, tiles, tin, rseq.data(), rdelta.data(), rs, ro, true, !c.windows);
+	uint64_t seq_diff = 0;
+	for (uint64_t x = 0; x < L.seq_total; ++x) {
+		if (dseq[x] == rseq[x]) continue;
+		if (c.windows && x >= L.ref_base && x < L.ref_base + L.ref_bytes) continue;            // the device decodes these
+		if (zc_qry && x >= L.qry_base + L.qry_bytes && x < L.qry_base + (L.qry_bytes + 3) / 4 * 4) continue;      // the dword spill
+		if (zc_ref && x >= L.ref_base + L.ref_bytes && x < L.ref_base + (L.ref_bytes + 3) / 4 * 4) continue;
+		seq_diff++;
+	}
+	CHECK(seq_diff == 0);
+	CHECK(L.delta_total == 0 || memcmp(ddelta.data(), rdelta.data(), L.delta_total) == 0);
+	// every pad byte comes from a staged, zero or clear record
+	uint64_t pad_missed = 0;
+	for (uint64_t x = 0; x < L.seq_total; ++x) {
+		// (an empty batch of windows has nobody to clear its last pad, and nothing that reads it)
+		const bool in_pad = x < L.qry_base || (x >= L.qry_base + L.qry_bytes && x < L.ref_base) || (x >= L.ref_base + L.ref_bytes && !(c.windows && n == 0));
+		if (in_pad && !by_host[x]) pad_missed++;
+	}
+	CHECK(pad_missed == 0);
+	// staged records into one arena are pairwise disjoint; a zero record under a block's rounded-up copy precedes it
+	for (size_t i = 0; i < s.copies.size(); ++i)
+		for (size_t j = i + 1; j < s.copies.size(); ++j) {
+			const UploadCopy &u = s.copies[i], &v = s.copies[j];
+			if (u.dst != v.dst || u.dst_off + u.len <= v.dst_off || v.dst_off + v.len <= u.dst_off) continue;
+			const bool ub = u.src == kFromQryBlock || u.src == kFromRefBlock, vb = v.src == kFromQryBlock || v.src == kFromRefBlock;
+			CHECK(u.src == kFromZeros && vb && !ub);      // the only overlap there may be, in this order
+		}
+	// the misfits, renumbered: every tile's rows come back as the caller gave them
+	std::vector<RowDesc> hx(misfit_rows(overflow) + 1);
+	CHECK(misfit_rows(overflow) == ro.rows.size());
+	place_misfits(overflow, tin, L.rsrc, hx.data());
+	uint64_t rows_wrong = 0;
+	for (int i = 0; i < n; ++i) {
+		if (b.tiles[i].corridor_kind != CVX_CORRIDOR_ROWS) { CHECK(L.rsrc[i].fmt == kRowsConst); continue; }
+		CHECK(L.rsrc[i].fmt == rs[i].fmt);
+		const int H = b.tiles[i].qry_len;
+		std::vector<RowDesc> rows((size_t) H + 1);
+		expand_rows_host(L.rsrc[i], H, ddelta.data(), hx.data(), rows.data());
+		for (int y = 0; y < H; ++y) if (rows[y].off != b.off[i][y] || rows[y].len != b.len[i][y]) rows_wrong++;
+	}
+	CHECK(rows_wrong == 0);
+	if (fails != before) printf("  (upload case: %s)\n", name);
+	return s;
+}
+
+// (arena, offset, length) of a schedule's records in issue order, against a recorded sequence
+struct Xfer { int dst; uint64_t off, len; };
+static bool same_sequence(const UploadSchedule &s, const std::vector<Xfer> &want) {
+	if (s.copies.size() != want.size()) return false;
+	for (size_t i = 0; i < want.size(); ++i)
+		if (s.copies[i].dst != want[i].dst || s.copies[i].dst_off != want[i].off || s.copies[i].len != want[i].len) return false;
+	return true;
+}
+
+// the batches of the parent comparison (sizes only: the sequences of transfers depend on nothing else)
+static void parent_case_sizes(int which, std::vector<int> &W, std::vector<int> &H, std::vector<int> &kind) {
+	const int n = which == 0 ? 48 : 120;
+	for (int i = 0; i < n; ++i) {
+		if (which == 0) { W.push_back(300 + (i * 977) % 3700); H.push_back(300 + (i * 613) % 3700); kind.push_back(i % 3 == 1 ? kClosed : i % 11 == 5 ? kBigStep : kFits); }
+		else { W.push_back(7000 + (i * 977) % 2000); H.push_back(7000 + (i * 613) % 2000); kind.push_back(i % 13 == 6 ? kWidthChange : kFits); }
+	}
+}
+
+static void test_upload_schedule() {
+	// small batches: n = 0 and 1, empty reads / references, every input form with row arrays, closed forms and both
+	for (int n : {0, 1, 2, 37}) for (int rows = 0; rows < 3; ++rows) for (int form = 0; form < 6; ++form) {
+		std::vector<int> W, H, kind;
+		for (int i = 0; i < n; ++i) {
+			W.push_back(i % 7 == 3 ? 0 : 1 + (i * 389) % 900); H.push_back(i % 5 == 2 ? 0 : 1 + (i * 211) % 700);
+			kind.push_back(rows == 0 ? (i % 6 == 4 ? kWidthChange : kFits) : rows == 1 ? kClosed : (i % 3 == 0 ? kClosed : i % 4 == 1 ? kBigStep : kFits));
+		}
+		UpCase c;
+		c.windows = form >= 4; c.qry_pinned = form == 0 || form == 2 || form == 5; c.ref_pinned = form == 1 || form == 2;
+		UpBatch b;
+		make_batch(b, W, H, kind, c.windows);
+		for (int threads : {1, 16}) {
+			c.threads = threads;
+			// one piece below the threshold, eight at it (given threads)
+			UploadLayout L; std::vector<TileIn> tin; int bad = -1;
+			upload_layout(n, n ? b.tiles.data() : nullptr, tin, L, &bad, c.windows);
+			UploadSchedule probe;
+			build_upload_schedule(L, tin, n, c.qry_pinned, c.ref_pinned, threads, probe);
+			CHECK(probe.pieces.size() == 1);                                     // far below 8 MiB
+			c.thread_bytes = probe.pack_work + 1;
+			CHECK(run_upload(b, c, "small, one byte below the threshold").pieces.size() == 1);
+			c.thread_bytes = probe.pack_work;
+			CHECK(run_upload(b, c, "small, at the threshold").pieces.size() == (size_t) (threads > 1 ? kUploadPieces : 1));
+		}
+	}
+	// thousands of tiles of a few bytes around one large tile: piece boundaries that round down into the same 256-byte unit
+	// (nothing to copy for a piece) and pieces without tiles
+	for (int form = 0; form < 6; ++form) {
+		std::vector<int> W, H, kind;
+		for (int i = 0; i < 3000; ++i) { W.push_back(i % 4); H.push_back((i * 3) % 5); kind.push_back(i % 7 == 1 ? kClosed : i % 50 == 9 ? kWidthChange : kFits); }
+		W[1200] = 30000; H[1200] = 30000; kind[1200] = kFits;
+		UpCase c;
+		c.windows = form >= 4; c.qry_pinned = form == 0 || form == 2 || form == 5; c.ref_pinned = form == 1 || form == 2;
+		c.threads = 16; c.thread_bytes = 1;
+		UpBatch b;
+		make_batch(b, W, H, kind, c.windows);
+		const UploadSchedule s = run_upload(b, c, "tiny tiles");
+		int empty_pieces = 0, silent_pieces = 0;
+		for (const UploadPiece &p : s.pieces) { if (p.t1 == p.t0) empty_pieces++; if (p.rec1 == p.rec0) silent_pieces++; }
+		CHECK(s.pieces.size() == (size_t) kUploadPieces && empty_pieces > 0 && silent_pieces > 0);
+	}
+	// tiles with row arrays only in the first piece, only in the last: the step stream's cut-off when no later tile has steps
+	for (int where = 0; where < 2; ++where) {
+		std::vector<int> W(64, 500), H(64, 500), kind(64, kClosed);
+		for (int k = 0; k < 2; ++k) { const int i = where ? 62 + k : k; W[i] = H[i] = 200; kind[i] = kFits; }
+		UpCase c;
+		c.threads = 16; c.thread_bytes = 1;
+		UpBatch b;
+		make_batch(b, W, H, kind, false);
+		const UploadSchedule s = run_upload(b, c, where ? "row arrays in the last piece" : "row arrays in the first piece");
+		CHECK(s.pieces.size() == (size_t) kUploadPieces);
+		if (s.pieces.size() == (size_t) kUploadPieces) CHECK(where ? s.pieces.back().t0 <= 62 && s.pieces[6].t0 <= s.pieces[6].t1 && s.pieces.back().t0 > 2 : s.pieces[0].t1 >= 2);
+		// 400 bytes of steps.  In the first piece: their whole 256-byte units travel with it, the rest with the last piece; in the
+		// last piece: nothing travels before it (the cut-off of every earlier piece is the first step of tile 62)
+		int delta_copies = 0;
+		for (size_t k = 0; k < s.pieces.size(); ++k)
+			for (size_t r = s.pieces[k].rec0; r < s.pieces[k].rec1; ++r) {
+				if (s.copies[r].dst != kToDelta) continue;
+				delta_copies++;
+				CHECK(k == s.pieces.size() - 1 || (!where && k == 0 && s.copies[r].len == 256));
+			}
+		CHECK(delta_copies == (where ? 1 : 2));
+	}
+	// misfits spread over many packing ranges of every piece
+	{
+		std::vector<int> W, H, kind;
+		for (int i = 0; i < 640; ++i) { W.push_back(50 + (i * 31) % 200); H.push_back(40 + (i * 17) % 150); kind.push_back(i % 5 == 2 ? kBigStep : i % 9 == 4 ? kWidthChange : i % 8 == 7 ? kClosed : kFits); }
+		for (int form : {3, 0, 5}) {
+			UpCase c;
+			c.windows = form >= 4; c.qry_pinned = form == 0 || form == 5;
+			c.threads = 16; c.thread_bytes = 1;
+			UpBatch b;
+			make_batch(b, W, H, kind, c.windows);
+			CHECK(run_upload(b, c, "misfits").pieces.size() == (size_t) kUploadPieces);
+		}
+	}
+	// the parent's sequences of transfers for three batches (its inline expressions, evaluated on the same layouts:
+	// profiles/r10_upload_schedule.txt): one piece; eight pieces with row arrays; eight pieces with the reads pinned
+	{
+		static const std::vector<Xfer> want[3] = {
+			{ {0, 0, 134400}, {0, 134400, 111104}, {1, 0, 82176} },
+			{ {0, 0, 149760}, {0, 1003520, 131072}, {1, 0, 127488}, {0, 149760, 113152}, {0, 1134592, 111872}, {1, 127488, 113152},
+			  {0, 262912, 119040}, {0, 1246464, 115200}, {1, 240640, 119296}, {0, 381952, 126976}, {0, 1361664, 132608}, {1, 359936, 126720},
+			  {0, 508928, 120320}, {0, 1494272, 119552}, {1, 486656, 120320}, {0, 629248, 120064}, {0, 1613824, 117504}, {1, 606976, 120320},
+			  {0, 749312, 112896}, {0, 1731328, 115456}, {1, 727296, 112640}, {0, 862208, 141312}, {0, 1846784, 141056}, {1, 839936, 119296} },
+			{ {0, 0, 22272}, {0, 980992, 22528}, {0, 22272, 958820}, {0, 1003520, 131072}, {1, 0, 127488}, {0, 1134592, 111872},
+			  {1, 127488, 113152}, {0, 1246464, 115200}, {1, 240640, 119296}, {0, 1361664, 132608}, {1, 359936, 126720}, {0, 1494272, 119552},
+			  {1, 486656, 120320}, {0, 1613824, 117504}, {1, 606976, 120320}, {0, 1731328, 115456}, {1, 727296, 112640}, {0, 1846784, 141056},
+			  {1, 839936, 119296} },
+		};
+		for (int which = 0; which < 3; ++which) {
+			std::vector<int> W, H, kind;
+			parent_case_sizes(which, W, H, kind);
+			UpCase c;
+			c.threads = 16; c.qry_pinned = which == 2;
+			UpBatch b;
+			make_batch(b, W, H, kind, false);
+			const UploadSchedule s = run_upload(b, c, "parent comparison");
+			CHECK(s.pieces.size() == (size_t) (which == 0 ? 1 : kUploadPieces));
+			CHECK(same_sequence(s, want[which]));
+		}
+	}
+}
 
 int main() {
 	std::mt19937 rng(7);
@@ -110,13 +396,8 @@ int main() {
 	for (uint64_t k = 0; k < L.pad; ++k) if (a[k] != 0 || a[L.seq_total - 1 - k] != 0) { CHECK(!"pads zeroed"); break; }
 	// the misfits' rows get their place in the verbatim buffer (what stage_upload does after the parallel phase)
 	auto place = [&](std::vector<RowOverflow> &lists, std::vector<RowSrc> &rs, std::vector<RowDesc> &rowsx) {
-		uint64_t at = 0;
-		for (RowOverflow &o : lists) {
-			uint64_t r = 0;
-			for (int32_t ti : o.tiles) { rs[ti].src_off = at + r; r += (uint64_t) tin[ti].H; }
-			rowsx.insert(rowsx.end(), o.rows.begin(), o.rows.end());
-			at += o.rows.size();
-		}
+		rowsx.resize(misfit_rows(lists));
+		place_misfits(lists, tin, rs, rowsx.data());
 	};
 	std::vector<RowDesc> xa, xb;
 	std::vector<RowOverflow> la(1, oa);
@@ -609,6 +890,7 @@ int main() {
 			CHECK(walk_plan(20000, 20000, 0, 3000, list.data(), tin.data()).n_long == 0 && walk_plan(20000, 20000, 0, 2999, list.data(), tin.data()).n_long == 1);
 		}
 	}
+	test_upload_schedule();
 	printf(fails ? "host_logic_test: %d FAILED\n" : "host_logic_test: ok\n", fails);
 	return fails ? 1 : 0;
 }
