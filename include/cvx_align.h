@@ -479,7 +479,8 @@ int cvx_score_kernel_ms(cvx_handle h, float *ms);
  * events on the stream they ran on -- CVX_STAGE_SCORE: cvx_score_batch; CVX_STAGE_DECODE: decode_windows_kernel of
  * cvx_genome_decode; CVX_STAGE_SEARCH: every kernel of cvx_search_batch(_ex) (count, vote batches of each attempt of the
  * ladder, compaction) summed, without the host round trips between them. */
-enum { CVX_STAGE_SCORE = 0, CVX_STAGE_DECODE = 1, CVX_STAGE_SEARCH = 2 };
+enum { CVX_STAGE_SCORE = 0, CVX_STAGE_DECODE = 1, CVX_STAGE_SEARCH = 2,
+	CVX_STAGE_SCORE_WINDOWS = 3 /* stage_score_windows_kernel alone, of the last cvx_score_windows* call waited for (its time is part of CVX_STAGE_SCORE too) */ };
 int cvx_stage_kernel_ms(cvx_handle h, int32_t stage, float *ms);
 
 /* Asynchronous sub-read scoring (ABI 9, additive): the scores cvx_score_batch returns, for callers that must not block
@@ -500,6 +501,43 @@ int cvx_score_poll(cvx_score_job job);
 /* blocks (sleeping, not spinning) until the job is done, writes its n scores in call order, releases the job -- also when
  * it returns an error (ABI 9, additive) */
 int cvx_score_wait(cvx_score_job job, float *scores);
+
+/* Scoring against the resident genome (ABI 9, additive): the preparation loop of ScoreBuffer::DoRun and scoreShortRead
+ * (reference src/ScoreBuffer.cpp:94-121, :245-265) on the device.  A pair names a read of the call's read block, a strand and
+ * a window of the genome; stage_score_windows_kernel (cvx_score_stage.hip) writes both strings into the scoring job's
+ * sequence arena and the scoring kernels above run behind it, so neither the decoded window nor a reverse-complemented read
+ * crosses PCIe.
+ *   window  DecodeRefSequence(buf, 0, position, buffer_len) (src/SequenceProvider.cpp:567-625; NOT DecodeRefSequenceExact:
+ *           no chromosome logic, the 1000-N spacers decode as N).  With L = GetConcatRefLen() = n_nibbles - 1: position >= L
+ *           fails; len = buffer_len - 2, shortened by end = position + len - L when that is positive; (position & 1) +
+ *           2 * ((len + 1) / 2) characters from the genome, the last of them 'x' when len is odd, then `end` more 'x'.  The
+ *           string scored is that many characters (buf is taken to be NUL behind them, as at both call sites).
+ *   query   the read as it is, or (reverse != 0) MappedRead::computeReverseSeq (src/MappedRead.cpp:35-73): reversed, A<->T,
+ *           C<->G, every other byte unchanged.
+ *   reads   as in cvx_search_batch_arena: read r = arena[offsets[r] .. offsets[r + 1] - 1), its NUL at offsets[r + 1] - 1;
+ *           copied inside the call, never modified; one read may serve any number of pairs of either strand.
+ * status[i] = 1 and scores[i] = -1.0f where DecodeRefSequence returns false (such pairs are not scored), else status[i] = 0.
+ * CVX_ERR_ARG for buffer_len < 3, a read index outside [0, n_reads), offsets that do not ascend, or g on another device than h. */
+typedef struct { uint64_t position; int32_t buffer_len; int32_t read; int32_t reverse; } cvx_score_window;
+int cvx_score_windows_submit(cvx_handle h, cvx_genome g, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets,
+		int32_t n, const cvx_score_window *pairs, cvx_score_job *job);   /* then cvx_score_poll / cvx_score_wait */
+int cvx_score_windows(cvx_handle h, cvx_genome g, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets,
+		int32_t n, const cvx_score_window *pairs, float *scores, int32_t *status /* may be NULL */);
+/* The strings the device scores, back on the host (diagnosis and tests): pair i's window is the NUL-terminated string at
+ * out + ref_off[i], its query the one at out + qry_off[i] (a pair whose decode fails has an empty window).  *used = bytes
+ * written; CVX_ERR_CAPACITY with *used = the need when cap is smaller.  status may be NULL. */
+int cvx_stage_windows(cvx_handle h, cvx_genome g, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets,
+		int32_t n, const cvx_score_window *pairs, uint8_t *out, uint64_t cap, uint64_t *ref_off, uint64_t *qry_off,
+		int32_t *status, uint64_t *used);
+/* the same strings, built on the host from an encoded genome (cvx_genome_encode's output or ngmlr's own binRef): a plain
+ * restatement of the two rules, no device needed.  Read them through ref_off / qry_off: the offsets follow the slot order, which
+ * goes by shape class, and equal cvx_stage_windows' only on a handle with its default classes (not under
+ * CVX_TUNE_SCORE_NO_DIAG, which this entry knows nothing of). */
+int cvx_stage_windows_host(const uint8_t *bin_ref, uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts,
+		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n, const cvx_score_window *pairs,
+		uint8_t *out, uint64_t cap, uint64_t *ref_off, uint64_t *qry_off, int32_t *status, uint64_t *used);
+/* GetConcatRefLen() (src/SequenceProvider.cpp:638-640) of an encoded genome: the L of the window rule */
+int cvx_genome_concat_len(uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts, uint64_t *concat_len);
 
 /* Host-side text stage (convertCigar, src/ConvexAlignFast.cpp:112-333, and the
  * N-clip flags of :493-528).  Pure host code, no device needed. */

@@ -560,6 +560,43 @@ class StrippedSWHip:
         capi.check(self.lib.cvx_score_submit(self._al.h, n, r, q, C.byref(job)))
         return ScoreJob(self, job, n)
 
+    def score_windows(self, genome: "Genome", reads, pairs):
+        """cvx_score_windows: every pair scored against a window of the resident genome, both strings written on the device.
+        reads: a sequence of bytes, or (arena, offsets) from KmerIndex.make_arena; pairs: (position, buffer_len, read, reverse)
+        tuples or a WINDOW_DTYPE array.  -> (scores float32[n], status int32[n]); status 1 (score -1.0): the reference's
+        DecodeRefSequence fails for that position."""
+        arena, offsets, n_reads = _window_reads(reads)
+        tab = _window_pairs(pairs)
+        n = len(tab)
+        scores = np.zeros(max(n, 1), dtype=np.float32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        capi.check(self.lib.cvx_score_windows(self._al.h, genome.g, n_reads, arena.ctypes.data, offsets.ctypes.data, n, tab.ctypes.data,
+                                              scores.ctypes.data, status.ctypes.data))
+        return scores[:n], status[:n]
+
+    def submit_windows(self, genome: "Genome", reads, pairs) -> "ScoreJob":
+        """cvx_score_windows_submit: the same, returning at once (the reads are copied before it returns); wait() gives the scores,
+        -1.0 where the decode fails."""
+        arena, offsets, n_reads = _window_reads(reads)
+        tab = _window_pairs(pairs)
+        job = C.c_void_p()
+        capi.check(self.lib.cvx_score_windows_submit(self._al.h, genome.g, n_reads, arena.ctypes.data, offsets.ctypes.data, len(tab), tab.ctypes.data,
+                                                     C.byref(job)))
+        return ScoreJob(self, job, len(tab))
+
+    def stage_windows(self, genome: "Genome", reads, pairs):
+        """cvx_stage_windows: the strings the device would score -> (windows, queries, status), lists of bytes in pair order."""
+        arena, offsets, n_reads = _window_reads(reads)
+        tab = _window_pairs(pairs)
+        return _stage_windows(lambda *out: self.lib.cvx_stage_windows(self._al.h, genome.g, n_reads, arena.ctypes.data, offsets.ctypes.data,
+                                                                      len(tab), tab.ctypes.data, *out), tab, offsets)
+
+    def stage_kernel_ms(self) -> float:
+        """of that time, stage_score_windows_kernel alone (CVX_STAGE_SCORE_WINDOWS; 0 after a call on strings)"""
+        ms = C.c_float()
+        capi.check(self.lib.cvx_stage_kernel_ms(self._al.h, capi.STAGE_SCORE_WINDOWS, C.byref(ms)))
+        return ms.value
+
     def kernel_ms(self) -> float:
         """device time of the kernels of the handle's last scoring call (cvx_stage_kernel_ms, CVX_STAGE_SCORE)"""
         ms = C.c_float()
@@ -568,6 +605,64 @@ class StrippedSWHip:
 
     def close(self) -> None:
         self._al.close()
+
+
+WINDOW_DTYPE = np.dtype([("position", np.uint64), ("buffer_len", np.int32), ("read", np.int32), ("reverse", np.int32), ("pad", np.int32)])
+assert WINDOW_DTYPE.itemsize == C.sizeof(capi.CvxScoreWindow)
+
+
+def _window_reads(reads):
+    if isinstance(reads, tuple) and len(reads) == 2 and isinstance(reads[0], np.ndarray):
+        arena, offsets = reads
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        return np.ascontiguousarray(arena, dtype=np.uint8), offsets, len(offsets) - 1
+    arena, offsets, _ = KmerIndex.make_arena(list(reads))
+    return arena, offsets, len(offsets) - 1
+
+
+def _window_pairs(pairs) -> np.ndarray:
+    if isinstance(pairs, np.ndarray) and pairs.dtype == WINDOW_DTYPE:
+        return np.ascontiguousarray(pairs)
+    tab = np.zeros(len(pairs), dtype=WINDOW_DTYPE)
+    for i, (position, buffer_len, read, reverse) in enumerate(pairs):
+        tab[i] = (int(position) & 0xFFFFFFFFFFFFFFFF, buffer_len, read, 1 if reverse else 0, 0)
+    return tab
+
+
+def _stage_windows(call, tab, offsets):
+    n = len(tab)
+    ref_off = np.zeros(max(n, 1), dtype=np.uint64)
+    qry_off = np.zeros(max(n, 1), dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    used = C.c_uint64()
+    # every window is at most buffer_len characters, every query its read: an upper bound without asking first
+    rl = (offsets[1:] - offsets[:-1]).astype(np.int64)
+    cap = int(tab["buffer_len"].astype(np.int64).clip(0).sum() + rl[tab["read"].clip(0, max(len(rl) - 1, 0))].sum() + n + 64) if n and len(rl) else 64
+    out = np.zeros(cap, dtype=np.uint8)
+    capi.check(call(out.ctypes.data, cap, ref_off.ctypes.data, qry_off.ctypes.data, status.ctypes.data, C.byref(used)))
+    blob = out[:int(used.value)].tobytes()
+
+    def cstr(at):
+        return blob[at:blob.index(b"\0", at)]
+    return [cstr(int(ref_off[i])) for i in range(n)], [cstr(int(qry_off[i])) for i in range(n)], status[:n]
+
+
+def stage_windows_host(lib, binref, nibbles, starts, reads, pairs):
+    """cvx_stage_windows_host: the same strings built on the host from an encoded genome (no device)."""
+    arena, offsets, n_reads = _window_reads(reads)
+    tab = _window_pairs(pairs)
+    b = np.ascontiguousarray(binref, dtype=np.uint8)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    return _stage_windows(lambda *out: lib.cvx_stage_windows_host(b.ctypes.data, int(nibbles), st.ctypes.data, len(st), n_reads, arena.ctypes.data,
+                                                                  offsets.ctypes.data, len(tab), tab.ctypes.data, *out), tab, offsets)
+
+
+def genome_concat_len(lib, nibbles, starts) -> int:
+    """cvx_genome_concat_len: GetConcatRefLen() of an encoded genome"""
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    out = C.c_uint64()
+    capi.check(lib.cvx_genome_concat_len(int(nibbles), st.ctypes.data, len(st), C.byref(out)))
+    return int(out.value)
 
 
 class ScoreJob:

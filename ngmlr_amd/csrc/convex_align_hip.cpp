@@ -37,6 +37,14 @@ bool const g_deviceDecode = [] { const char * e = getenv("CVX_DEVICE_DECODE"); r
 
 bool DeviceWindows::Enabled() { return g_deviceDecode; }
 bool DeviceWindows::HaveGenome() { return g_binRef != 0; }
+bool DeviceWindows::Genome(void const * & binRef, unsigned long long & nNibbles, unsigned long long const * & startTable, int & nStarts) {
+	if (g_binRef == 0) return false;
+	binRef = g_binRef;
+	nNibbles = g_nNibbles;
+	startTable = (unsigned long long const *) g_startTable.data();
+	nStarts = (int) g_startTable.size();
+	return true;
+}
 
 void DeviceWindows::SetGenome(void const * binRef, unsigned long long nNibbles, unsigned long long const * startTable, int nStarts) {
 	g_startTable.assign(startTable, startTable + (nStarts > 0 ? nStarts : 0));

@@ -155,6 +155,8 @@ struct DeviceWindows {
 	 * bound): the pointers must stay valid; each aligner uploads it to its own device at its first window launch */
 	static void SetGenome(void const * binRef, unsigned long long nNibbles, unsigned long long const * startTable, int nStarts);
 	static bool HaveGenome();
+	/* what SetGenome was given (false before it): StrippedSWHip::BatchScoreWindows uploads it once per logical device */
+	static bool Genome(void const * & binRef, unsigned long long & nNibbles, unsigned long long const * & startTable, int & nStarts);
 	/* buf[0 .. length) stands for DecodeRefSequenceExact(buf, position, length, 0): length - 1 characters and a NUL */
 	static void Placeholder(char * buf, unsigned long long position, int length);
 	static bool Lookup(char const * buf, unsigned long long & position, int & length);

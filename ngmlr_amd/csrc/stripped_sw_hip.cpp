@@ -1,6 +1,7 @@
 /* stripped_sw_hip.cpp -- see stripped_sw_hip.h */
 #include "stripped_sw_hip.h"
 #include "service_device.h"
+#include "convex_align_hip.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +22,8 @@ cvx_handle g_handle[kMaxDevices][kLanes] = {{0}};
 int g_users[kMaxDevices] = {0};
 long g_joined[kMaxDevices] = {0};
 /* statistics, printed when the last scorer of a device goes (like SharedAligner's line) */
-struct DevStats { std::atomic<long> calls{0}, pairs{0}, single{0}; std::atomic<long long> ns{0}, ctorNs{0}; };
+struct DevStats { std::atomic<long> calls{0}, pairs{0}, single{0}, winCalls{0}, winPairs{0}, winFailed{0}; std::atomic<long long> ns{0}, ctorNs{0}; };
+cvx_genome g_genome[kMaxDevices] = {0};      /* DeviceWindows' genome on the logical device: one per device, shared by its lanes */
 DevStats g_st[kMaxDevices];      /* per logical device: the line of a device says what ran THERE */
 std::chrono::steady_clock::time_point const g_loaded = std::chrono::steady_clock::now();      /* ~ process start */
 double g_firstCtorBegin = -1.0, g_firstCtorEnd = -1.0;
@@ -53,6 +55,7 @@ StrippedSWHip::~StrippedSWHip() {
 		std::chrono::steady_clock::time_point const d0 = std::chrono::steady_clock::now();
 		for (int l = 0; l < kLanes; ++l) {
 			std::lock_guard<std::mutex> d(g_mtx[device][l]);
+			if (g_genome[device] && g_handle[device][l]) { cvx_genome_free(g_handle[device][l], g_genome[device]); g_genome[device] = 0; }
 			if (g_handle[device][l]) cvx_destroy(g_handle[device][l]);
 			g_handle[device][l] = 0;
 		}
@@ -66,7 +69,8 @@ StrippedSWHip::~StrippedSWHip() {
 				"(%.3f ms per call), %.2f s constructing, %.2f s destroying the handles\n", st.calls.load(), where, st.single.load(), st.pairs.load(),
 				st.ns.load() * 1e-9, st.calls.load() ? st.ns.load() * 1e-6 / (double) st.calls.load() : 0.0, st.ctorNs.load() * 1e-9,
 				std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count());
-		st.calls = 0; st.pairs = 0; st.single = 0; st.ns = 0; st.ctorNs = 0;
+		fprintf(stderr, "StrippedSWHip: %ld window calls%s, %ld pairs, %ld through the string path\n", st.winCalls.load(), where, st.winPairs.load(), st.winFailed.load());
+		st.calls = 0; st.pairs = 0; st.single = 0; st.ns = 0; st.ctorNs = 0; st.winCalls = 0; st.winPairs = 0; st.winFailed = 0;
 		fprintf(stderr, "StrippedSWHip: library loaded at 0, first scorer constructed %.2f - %.2f s, last one gone at %.2f s\n", g_firstCtorBegin, g_firstCtorEnd, since_load());
 	}
 }
@@ -83,6 +87,41 @@ int StrippedSWHip::BatchScore(int const mode, int const batchSize, char const * 
 		fprintf(stderr, "StrippedSWHip: %s\n", cvx_last_error());
 		throw 1;
 	}
+	return batchSize;
+}
+
+void StrippedSWHip::CountStringPath(int const pairs) { g_st[device].winFailed += pairs; }
+
+/* Locks: the lane's mutex first, then -- for the device's first call only -- the table's, held while the genome is uploaded
+ * (seconds for a genome of gigabytes: constructors and destructors of other scorers wait that long, once per device).  The
+ * destructor takes them the other way round, table then lanes, but only when the device's last scorer goes, i.e. when no
+ * thread can be inside a call on one of that device's lanes: the two orders never meet on the same device. */
+int StrippedSWHip::BatchScoreWindows(int const nReads, unsigned char const * const arena, unsigned long long const * const offsets,
+		int const batchSize, cvx_score_window const * const pairs, float * const results, int * const status) {
+	std::chrono::steady_clock::time_point const t0 = std::chrono::steady_clock::now();
+	std::lock_guard<std::mutex> d(g_mtx[device][lane]);
+	DevStats & st = g_st[device];
+	st.calls += 1; st.pairs += batchSize; st.winCalls += 1; st.winPairs += batchSize;
+	struct Stop { std::chrono::steady_clock::time_point t; DevStats * s; ~Stop() { s->ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count(); } } stop{t0, &st};
+	if (__atomic_load_n(&g_genome[device], __ATOMIC_ACQUIRE) == 0) {      /* (read again under the table's lock: another lane of the device may be uploading it) */
+		std::lock_guard<std::mutex> g(g_tableMtx);
+		if (g_genome[device] == 0) {
+			void const * binRef = 0; unsigned long long nNibbles = 0; unsigned long long const * starts = 0; int nStarts = 0;
+			if (!Convex::DeviceWindows::Genome(binRef, nNibbles, starts, nStarts)) throw "StrippedSWHip::BatchScoreWindows: no genome (Convex::DeviceWindows::SetGenome)";
+			cvx_genome up = 0;
+			if (cvx_genome_upload(g_handle[device][lane], (uint8_t const *) binRef, nNibbles, (uint64_t const *) starts, nStarts, &up) != CVX_OK) {
+				fprintf(stderr, "StrippedSWHip: %s\n", cvx_last_error());
+				throw 1;
+			}
+			__atomic_store_n(&g_genome[device], up, __ATOMIC_RELEASE);
+		}
+	}
+	cvx_genome const genome = __atomic_load_n(&g_genome[device], __ATOMIC_ACQUIRE);
+	if (cvx_score_windows(g_handle[device][lane], genome, nReads, arena, (uint64_t const *) offsets, batchSize, pairs, results, status) != CVX_OK) {
+		fprintf(stderr, "StrippedSWHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	if (status) for (int i = 0; i < batchSize; ++i) st.winFailed += status[i] != 0;
 	return batchSize;
 }
 

@@ -32,6 +32,16 @@ public:
 			char const * const * const qrySeqList, float * const results, void * extData);
 	virtual int SingleScore(int const mode, int const corridor, char const * const refSeq,
 			char const * const qrySeq, float & result, void * extData);
+	/* Not part of IAlignment (the vtable stays as it is): BatchScore for pairs given as (window of the genome, read, strand) --
+	 * cvx_score_windows on this worker's lane, the strings of ScoreBuffer::DoRun's preparation loop written on the device
+	 * (reference src/ScoreBuffer.cpp:94-121).  The genome is the one Convex::DeviceWindows::SetGenome announced, uploaded once per
+	 * logical device by the first call there, shared by the device's lanes and freed with its last scorer.  reads as in
+	 * cvx_search_batch_arena.  results[i] = -1 and status[i] = 1 (status may be 0) where DecodeRefSequence would return false: the
+	 * caller scores those through the strings.  Returns batchSize; throws without a genome. */
+	int BatchScoreWindows(int const nReads, unsigned char const * const arena, unsigned long long const * const offsets,
+			int const batchSize, cvx_score_window const * const pairs, float * const results, int * const status);
+	/* pairs a binding sent through BatchScore's strings because a window of their call does not decode (the exit line's K) */
+	void CountStringPath(int const pairs);
 	virtual int BatchAlign(int const, int const, char const * const * const, char const * const * const,
 			Align * const, void *) { throw "StrippedSWHip: score-only backend"; }
 	virtual int SingleAlign(int const, int const, char const * const, char const * const, Align &, void *) {

@@ -34,6 +34,9 @@ mkdir -p "$REPO/oracle/_ref"
 #                      (lqCheckAligner, src/AlignmentBuffer.cpp:1217) scored on the device: Convex::SharedScorer proxies in place of
 #                      their private StrippedSW, one BatchingScorer per device (batching_scorer.h); CVX_CHECK_SCORER=0 puts the
 #                      reference's StrippedSW back at run time (tests/test_gpu_e2e_checks.py)
+#   ngmlr_hip_scorewin ngmlr_hip_all + the scoring calls of ScoreBuffer::DoRun and scoreShortRead as windows of the resident genome
+#                      (score_windows_binding.inc: StrippedSWHip::BatchScoreWindows, no computeReverseSeq / DecodeRefSequence on the CS
+#                      thread); CVX_SCORE_WINDOWS=0 keeps the string path inside the same binary (tests/test_gpu_e2e_scorewin.py)
 #   ngmlr_index_cpu    the reference's CPU code with only that table builder bound: the table file it writes against the unmodified
 #                      binary's, without a GPU (tests/test_index_cpu.py)
 #   ngmlr_pool_cpu     the reference's CPU aligners + the same pool: the pool's own correctness without a GPU (tests/test_pool_cpu.py)
@@ -41,13 +44,14 @@ mkdir -p "$REPO/oracle/_ref"
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
+SCOREWIN = sys.argv[10]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -166,6 +170,22 @@ if POOL:
     s = open(p).read()
     s = sub1(s, 'BUFFER_LIMIT =  10000000;', 'BUFFER_LIMIT =  262144;', 'BUFFER_LIMIT')
     open(p, 'w').write(s)
+if SCOREWIN:
+    # the scoring calls of ScoreBuffer as windows of the resident genome (ngmlr_amd/csrc/score_windows_binding.inc; needs the scorer
+    # plugin and the genome announced in _SequenceProvider::Init, i.e. SCORER, INDEX and POOL)
+    assert SCORER and INDEX and POOL
+    p = T + '/src/ScoreBuffer.cpp'
+    s = open(p).read()
+    s = sub1(s, '#include "StrippedSW.h"', '#include "StrippedSW.h"\n#include "score_windows_binding.h"', 'ScoreBuffer include (score windows)')
+    s = sub1(s, '\t\t//Prepare for score computation\n\t\tfor (int i = 0; i < iScores; ++i) {',
+             '\t\t//Prepare for score computation\n\t\tbool cvxWindows = false;\n#define CVX_SCORE_WINDOWS_SITE 1\n#include "score_windows_binding.inc"\n#undef CVX_SCORE_WINDOWS_SITE\n'
+             '\t\tfor (int i = 0; i < (cvxWindows ? 0 : iScores); ++i) {', 'ScoreBuffer::DoRun loop')
+    s = sub1(s, 'int res = aligner->BatchScore(0, iScores, m_RefBuffer, m_QryBuffer, m_ScoreBuffer, 0);',
+             'int res = cvxWindows ? iScores : aligner->BatchScore(0, iScores, m_RefBuffer, m_QryBuffer, m_ScoreBuffer, 0);', 'ScoreBuffer::DoRun BatchScore')
+    s = sub1(s, '\tfor (int i = 0; i < read->numScores(); ++i) {\n\t\tint corridor = read->length * 0.3 + 256;\n',
+             '\tbool cvxWindows = false;\n#define CVX_SCORE_WINDOWS_SITE 2\n#include "score_windows_binding.inc"\n#undef CVX_SCORE_WINDOWS_SITE\n'
+             '\tfor (int i = 0; i < (cvxWindows ? 0 : read->numScores()); ++i) {\n\t\tint corridor = read->length * 0.3 + 256;\n', 'ScoreBuffer::scoreShortRead loop')
+    open(p, 'w').write(s)
 if SAM:
     p = T + '/src/SAMWriter.cpp'
     s = open(p).read()
@@ -224,10 +244,11 @@ bv ngmlr_pool_cpu cpu "" "" pool
 bv ngmlr_pool_parked Convex::ParkingCpuAligner "" "" pool      # CPU aligner behind a park / wake per SingleAlign (tests/cpp/parking_cpu_aligner.h)
 bv ngmlr_hip_all Convex::SharedAligner StrippedSWHip sam pool search index
 bv ngmlr_hip_checks Convex::SharedAligner StrippedSWHip sam pool search index checks
+bv ngmlr_hip_scorewin Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
