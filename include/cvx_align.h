@@ -287,6 +287,17 @@ int cvx_batch_upload(cvx_handle h, int32_t n_tiles, const cvx_tile *tiles, cvx_b
 int cvx_batch_run(cvx_handle h, cvx_batch b);            /* enqueue + wait */
 int cvx_batch_timing(cvx_batch b, cvx_timing *t);
 int cvx_batch_ops_total(cvx_batch b, uint64_t *n_ops);
+/* the device-side summary of the batch's last run as it came back with the result records: ops of all valid tiles, number of
+ * valid tiles (status CVX_TILE_OK), tiles that took the second fill pass in THAT run */
+int cvx_batch_summary(cvx_batch b, uint64_t *ops_total, int32_t *n_valid, int32_t *n_redone);
+/* the corridor analysis of tiles [first, first + count) as the device wrote it (read-only; for tests and diagnosis): first and
+ * one-past-last anti-diagonal with a cell, ring slots the fill needs, flags (1 row starts / ends not monotone, 2 no cell inside
+ * the window, 4 larger than max_matrix_mb, 8 a gap run can pass SHRT_MAX), cells of the corridor and those inside [0, W) */
+typedef struct cvx_tile_plan {
+	int32_t r0, rend, need, flags;
+	uint64_t cells, active;
+} cvx_tile_plan;
+int cvx_batch_plan(cvx_batch b, int32_t first, int32_t count, cvx_tile_plan *out);
 /* i in [0, timing.n_fill_launches) */
 int cvx_batch_launch_info(cvx_batch b, int32_t i, cvx_launch_info *info);
 int cvx_batch_download(cvx_handle h, cvx_batch b, cvx_result *results,

@@ -24,7 +24,7 @@ TILE_STATUS = {0: "ok", 1: "invalid-row0", 2: "invalid-edge", 3: "invalid-length
 
 EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_count", "cvx_device_synchronize", "cvx_create", "cvx_destroy",
            "cvx_align_batch", "cvx_batch_upload", "cvx_batch_run", "cvx_batch_timing",
-           "cvx_batch_ops_total", "cvx_batch_launch_info", "cvx_batch_download", "cvx_batch_free",
+           "cvx_batch_ops_total", "cvx_batch_summary", "cvx_batch_plan", "cvx_batch_launch_info", "cvx_batch_download", "cvx_batch_free",
            "cvx_submit", "cvx_wait", "cvx_job_timing", "cvx_job_launch_info", "cvx_job_release",
            "cvx_format_alignment", "cvx_format_batch", "cvx_score_batch",
            "cvx_genome_encoded_bytes", "cvx_genome_encode", "cvx_genome_upload", "cvx_genome_free",
@@ -170,6 +170,8 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_batch_timing.argtypes = [C.c_void_p, C.POINTER(CvxTiming)]
     lib.cvx_batch_launch_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CvxLaunchInfo)]
     lib.cvx_batch_ops_total.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.cvx_batch_summary.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.cvx_batch_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.cvx_batch_download.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CvxResult), C.c_void_p,
                                        C.c_uint64, C.POINTER(C.c_uint64)]
     lib.cvx_batch_free.argtypes = [C.c_void_p, C.c_void_p]

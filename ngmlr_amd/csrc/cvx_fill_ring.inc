@@ -61,9 +61,12 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	 * address and the cell update reads its penalty with one ds_read_b32 -- the LDS pipe is otherwise idle in the step
 	 * loop -- instead of v_mul + v_add + v_min.  The penalty is constant from some run on (27 with the default scoring:
 	 * gext + run * decay has reached gem); the host enables this form only when that run is below kPenClamp
-	 * (FillArgs::pen_table), and the run registers are clamped to kPenClamp at every group end -- a run register only ever
-	 * selects a penalty, so the clamp changes nothing, and the table needs kPenClamp + 5 entries whatever the corridor
-	 * (gap runs through zero-score cells are as long as a row is wide). */
+	 * (FillArgs::pen_table), and the run registers are clamped to kPenClamp once per 32-step block, in the branch that
+	 * flushes the direction words -- a run register only ever selects a penalty, so the clamp changes nothing, and it need
+	 * only run often enough that the address stays inside the table: a register grows by one entry per step at most, so
+	 * the table has kPenClamp + kPenClampSteps + 1 entries or more whatever the corridor (gap runs through zero-score
+	 * cells are as long as a row is wide).  A gang's wave clamps what it takes from its neighbour's record as well (a
+	 * scalar min): that register was offered one step before the neighbour's own clamp. */
 	__shared__ float s_pen[TAB ? kPenEntries : 1];
 
 	int t;                          /* tile */
@@ -324,6 +327,13 @@ CVX_FILL_KERNEL(const FillArgs a) {
 			const unsigned dl = (unsigned) tid * (M * 2);
 #pragma unroll
 			for (int j = 0; j < M; ++j) { d[dl + 2 * j] = accA[j]; d[dl + 2 * j + 1] = accB[j]; }
+			if (TAB) {
+				/* the clamp of the run registers, once per kPenClampSteps steps (one register per slot: the deletion and the
+				 * insertion run of a cell share it in this form) */
+				static_assert(kPenClampSteps == 32, "the run registers are clamped where the direction words are flushed");
+#pragma unroll
+				for (int j = 0; j < M; ++j) { const int c = min((int) drun[j], 4 * kPenClamp); drun[j] = (run_t) c; irun[j] = (run_t) c; }
+			}
 		}
 
 #pragma unroll
@@ -371,7 +381,9 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				if (lane == 0) {
 					uV0 = vv;
 					uS0 = sc;
-					uI0 = TAB ? (run_t) (int) (run16 << 2) : (run_t) (float) run16;
+					/* (TAB: the neighbour's register of the step before, which may be the last step before its clamp; clamped here
+					 * it obeys this wave's bound -- kPenClamp plus the steps since this wave's own clamp -- like every other one) */
+					uI0 = TAB ? (run_t) (int) ((run16 < (unsigned) kPenClamp ? run16 : (unsigned) kPenClamp) << 2) : (run_t) (float) run16;
 				}
 				mIu0 = (mIu0 & ~1ull) | (u64) ins;
 			};
@@ -566,11 +578,6 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				}
 				take_row(j, s_rec[CHAIN ? 0 : wv * M + j][lane], r, false);
 			}
-		}
-		if (TAB) {
-			/* (one register per slot: the deletion and the insertion run of a cell share it in this form) */
-#pragma unroll
-			for (int j = 0; j < M; ++j) { const int c = min((int) drun[j], 4 * kPenClamp); drun[j] = (run_t) c; irun[j] = (run_t) c; }
 		}
 		if (stage_now) {
 			stage_rows(stage_next, stage_slot);

@@ -33,6 +33,7 @@
 
 #include "cvx_types.h"
 #include "cvx_launch.h"
+#include "cvx_plan_logic.h"
 
 namespace cvx {
 
@@ -48,20 +49,16 @@ CVX_DEV float rot1_f(float v) {
 
 /* ------------------------------------------------------------------ plan */
 
-/* gs(y): anti-diagonal of the first cell of row y; ge(y): one past the last.
- * Row y covers x in [max(0,off), min(off+len, W))  (src/ConvexAlignFast.cpp:948-950). */
-CVX_DEV void row_span(const int2 ol, int W, int y, int &gs, int &ge) {
-	long long lo = ol.x > 0 ? ol.x : 0;
-	long long hi = (long long) ol.x + (long long) ol.y;
-	if (hi > W) hi = W;
-	if (hi < lo) hi = lo;
-	gs = (int) (lo + y);
-	ge = (int) (hi + y);
-}
-
-/* TPT threads per tile, 256 / TPT tiles per workgroup: 256 for batches of long reads, 64 (a wave
+/* The per-tile logic is cvx_plan_logic.h (compiled for the host too: tests/cpp/plan_logic_test.cpp); here the threads of a
+ * tile share its rows out and combine what they add up to.
+ *
+ * TPT threads per tile, 256 / TPT tiles per workgroup: 256 for batches of long reads, 64 (a wave
  * per tile) for batches of short ones, where a 256-thread group per 150-row tile was mostly idle
- * threads and workgroup launches (short-read config: 1.7 of 8.9 ms per 100 000 tiles) */
+ * threads and workgroup launches (short-read config: 1.7 of 8.9 ms per 100 000 tiles).
+ *
+ * TPT = 256 stages the row spans of a strip in LDS and evaluates every row once (plan_row_staged); TPT = 64 keeps the
+ * on-demand form (plan_row_ondemand: about six evaluations per row): its tiles are a few hundred rows, four of them
+ * share a workgroup, and a ring per tile would cost the kernel its occupancy for rows that are few anyway. */
 template <int TPT>
 __global__ void __launch_bounds__(256)
 plan_kernel(const int2 *rows, const RowSrc *rsrc, const TileIn *tin, TilePlan *plan, int n_tiles, unsigned long long max_matrix_mb) {
@@ -71,11 +68,14 @@ plan_kernel(const int2 *rows, const RowSrc *rsrc, const TileIn *tin, TilePlan *p
 	const int t = blockIdx.x * TPB + sub;
 	const bool live = t < n_tiles;
 	const TileIn ti = tin[live ? t : 0];
-	/* rows of a closed-form corridor are evaluated in registers (RowView): the analysis of such a tile reads nothing
+	/* rows of a closed-form corridor are evaluated in registers: the analysis of such a tile reads nothing
 	 * but its 32-byte description -- it used to read 8 H bytes a handful of times (3.5 ms per 49 152 PacBio tiles, and
 	 * most of a fill's duration when it ran beside one) */
-	const RowView rv = row_view(rsrc[live ? t : 0], reinterpret_cast<const RowDesc2 *>(rows), ti.row_off);
-	auto row = [&](const int y) { const RowDesc2 q = row_at(rv, y); return make_int2(q.x, q.y); };
+	const RowSrc rs = rsrc[live ? t : 0];
+	PlanRows pr;
+	pr.rows = reinterpret_cast<const RowDesc2 *>(rows) + ti.row_off;
+	pr.fmt = rs.fmt; pr.width = rs.width; pr.off0 = rs.off0;
+	pr.k = rs.k; pr.d = rs.d; pr.right = rs.right;
 	const int H = live ? ti.H : 0, W = ti.W;
 
 	__shared__ unsigned long long s_cells[TPB], s_active[TPB];
@@ -83,110 +83,39 @@ plan_kernel(const int2 *rows, const RowSrc *rsrc, const TileIn *tin, TilePlan *p
 	if (ltid == 0) { s_cells[sub] = 0; s_active[sub] = 0; s_need[sub] = 1; s_flags[sub] = 0; s_maxlen[sub] = 0; s_rend[sub] = -0x7fffffff; s_r0[sub] = 0x7fffffff; }
 	__syncthreads();
 
-	unsigned long long cells = 0, active = 0;
-	int need = 1, flags = 0, maxlen = 0, rendmax = -0x7fffffff, r0min = 0x7fffffff;
-	for (int y = ltid; y < H; y += TPT) {
-		const int2 ol = row(y);
-		int gs, ge;
-		row_span(ol, W, y, gs, ge);
-		cells += (unsigned long long) (long long) ol.y;
-		active += (unsigned long long) (ge - gs);
-		if (ol.y > maxlen) maxlen = ol.y;
-		if (ge > rendmax) rendmax = ge;
-		if (gs < r0min) r0min = gs;
-		if (y > 0) {
-			int pgs, pge;
-			row_span(row(y - 1), W, y - 1, pgs, pge);
-			if (gs <= pgs) flags |= kPlanIrregular;  /* ring schedule needs increasing row starts */
-			/* ... and rows that end in order: the fill hands slots over in row order (its staged row
-			 * records are overwritten on that assumption).  True for every corridor the reference builds
-			 * (one width, offsets that never decrease); a corridor whose rows shrink goes to the catch-all kernel. */
-			if (ge < pge) flags |= kPlanIrregular;
+	PlanAcc acc = plan_acc_init();
+	if constexpr (TPT == 256) {
+		/* (one tile per workgroup: H is uniform, every thread meets every barrier) */
+		__shared__ int s_gs[kPlanCap], s_ge[kPlanCap];
+		int staged = 0;
+		for (int Y = 0; Y < H; Y += kPlanStrip) {
+			const int end = plan_strip_staged(Y, H);
+			__syncthreads();                       /* the strip before has been read */
+			for (int r = staged + ltid; r < end; r += TPT) plan_stage_row(pr, W, r, s_gs, s_ge);
+			staged = end;
+			__syncthreads();
+			const int yend = min(H, Y + kPlanStrip);
+			for (int y = Y + ltid; y < yend; y += TPT) plan_row_staged(acc, pr, W, H, y, staged, s_gs, s_ge);
 		}
-		/* first row y' > y that starts at or after ge + margin (gs is increasing): gallop out from
-		 * a guess -- row starts advance by about two anti-diagonals per row in a sloped corridor --
-		 * then bisect; a handful of row reads instead of log2(H) */
-		const int lim = ge + kSwitchMargin;
-		auto starts_before = [&](int yy) {       /* gs(yy) < lim */
-			int mgs, mge;
-			row_span(row(yy), W, yy, mgs, mge);
-			return mgs < lim;
-		};
-		int lo = y + 1, hi = H;                  /* rows < lo start before lim, rows >= hi do not */
-		int g = y + 1 + ((lim - gs) >> 1);
-		g = g < lo ? lo : g;
-		if (g < hi) {
-			if (starts_before(g)) {
-				lo = g + 1;
-				for (int step = 1; lo < hi; step <<= 1) {
-					const int p = (lo + step - 1 < hi) ? lo + step - 1 : hi - 1;
-					if (starts_before(p)) lo = p + 1; else { hi = p; break; }
-				}
-			} else {
-				hi = g;
-				for (int step = 1; lo < hi; step <<= 1) {
-					const int p = (hi - step > lo) ? hi - step : lo;
-					if (starts_before(p)) { lo = p + 1; break; } else hi = p;
-				}
-			}
-		}
-		while (lo < hi) {
-			const int mid = (lo + hi) >> 1;
-			if (starts_before(mid)) lo = mid + 1; else hi = mid;
-		}
-		const int n = lo - y + 1;
-		if (n > need) need = n;
-		if (H > 32767) {
-			/* How long can a gap run get in this corridor?  A deletion run stays inside one row (<= its length, tracked
-			 * above); an insertion run stays inside one column, i.e. inside the consecutive rows that contain it: for the
-			 * last column of row y those are the rows up to the first one that starts at or behind hi(y) (row starts do not
-			 * decrease in a regular corridor).  Only when such a stretch exceeds SHRT_MAX can the reference's `short
-			 * indelRun` wrap (src/AlignmentMatrixFast.h:43) and the int16-emulating kernels are needed -- a 100 kb read on
-			 * a 350-column corridor never gets there, and the float-run kernels are three times as fast. */
-			long long lo_y = ol.x > 0 ? ol.x : 0;
-			long long hi_y = (long long) ol.x + (long long) ol.y;
-			if (hi_y > W) hi_y = W;
-			if (hi_y < lo_y) hi_y = lo_y;
-			int a = y + 1, b = H;                    /* rows < a start before hi(y), rows >= b do not */
-			while (a < b) {
-				const int mid = (a + b) >> 1;
-				const int2 om = row(mid);
-				const long long lo_m = om.x > 0 ? om.x : 0;
-				if (lo_m < hi_y) a = mid + 1; else b = mid;
-			}
-			if (a - y > maxlen) maxlen = a - y;      /* folded into the same maximum: either kind of run past 32767 needs the wrap kernels */
-		}
+	} else {
+		for (int y = ltid; y < H; y += TPT) plan_row_ondemand(acc, pr, W, H, y);
 	}
 	if (H > 0) {
-		atomicAdd(&s_cells[sub], cells);
-		atomicAdd(&s_active[sub], active);
-		atomicMax(&s_need[sub], need);
-		atomicOr(&s_flags[sub], flags);
-		atomicMax(&s_maxlen[sub], maxlen);
-		atomicMax(&s_rend[sub], rendmax);
-		atomicMin(&s_r0[sub], r0min);
+		atomicAdd(&s_cells[sub], acc.cells);
+		atomicAdd(&s_active[sub], acc.active);
+		atomicMax(&s_need[sub], acc.need);
+		atomicOr(&s_flags[sub], acc.flags);
+		atomicMax(&s_maxlen[sub], acc.maxlen);
+		atomicMax(&s_rend[sub], acc.rendmax);
+		atomicMin(&s_r0[sub], acc.r0min);
 	}
 	__syncthreads();
 
 	if (ltid == 0 && live) {
-		TilePlan p;
-		p.cells = s_cells[sub];
-		p.active = s_active[sub];
-		p.need = s_need[sub];
-		int f = s_flags[sub];
-		int r0 = 0, rend = 0;
-		if (H > 0) { r0 = s_r0[sub]; rend = s_rend[sub]; }   /* first / one-past-last anti-diagonal with a cell */
-		if (H <= 0 || s_active[sub] == 0) f |= kPlanEmpty;
-		/* src/AlignmentMatrixFast.cpp:45: (ulong)(matrixSize / 1000.0f / 1000.0f) < maxMatrixSizeMB */
-		const float mb = (float) s_cells[sub] / 1000.0f / 1000.0f;
-		if (!((unsigned long long) mb < max_matrix_mb)) f |= kPlanTooLarge;
-		/* longest possible deletion (row length) or insertion (column extent, rows above) run; the column bound needs
-		 * row starts that do not decrease, so an irregular corridor that tall keeps the old rule */
-		if (s_maxlen[sub] > 32767 || (H > 32767 && (f & kPlanIrregular))) f |= kPlanWrap16;
-		p.r0 = r0;
-		p.rend = rend;
-		p.flags = f;
-		plan[t] = p;
+		PlanAcc all;
+		all.cells = s_cells[sub]; all.active = s_active[sub]; all.need = s_need[sub]; all.flags = s_flags[sub];
+		all.maxlen = s_maxlen[sub]; all.rendmax = s_rend[sub]; all.r0min = s_r0[sub];
+		plan[t] = plan_finish(all, H, max_matrix_mb);
 	}
 }
 
@@ -938,70 +867,115 @@ backtrack_kernel(const BacktrackArgs a, const int32_t *order, const int n_order)
 }
 
 /*
- * finalize_kernel -- what the host used to do between backtrack and compaction, on the device:
- * exclusive prefix sum of the op counts of the valid tiles (= each tile's slice of the dense ops
- * arena), the caller-facing result records (cvx_result layout) and the batch summary.  One
- * workgroup; a thread takes a contiguous chunk of tiles.
+ * finalize -- what the host used to do between backtrack and compaction, on the device: exclusive prefix
+ * sum of the op counts of the valid tiles (= each tile's slice of the dense ops arena), the caller-facing
+ * result records (cvx_result layout) and the batch summary.  Three small launches over blocks of
+ * kFinalizeTile tiles, one tile per thread (one workgroup walking 192 tiles per thread took 0.42 ms of the
+ * serial stretch between walk and compaction, all of it load latency):
+ *
+ *   finalize_sum_kernel    per block: ops and number of the valid tiles             -> part[b], part[nblk + b]
+ *   finalize_scan_kernel   one workgroup: exclusive scan of part[0 .. nblk) in place, the batch summary,
+ *                          and the batch's counters zeroed (it is their last reader)
+ *   finalize_write_kernel  per block: part[b] + the scan inside the block           -> res[t], dst_off[t]
+ *
+ * Every workgroup has 256 threads = one wave per SIMD: a workgroup that finds room on a CU the next
+ * batch's fill already occupies (a 1024-thread group waited ~50 ms for sixteen free wave slots on one CU).
  */
-__global__ void __launch_bounds__(256)
-finalize_kernel(const TileOut *tout, const TilePlan *plan, uint64_t *dst_off, ResultRec *res,
-		BatchSummary *sum, int32_t *counters, int n_tiles, unsigned long long dense_cap) {
-	/* 256 threads = one wave per SIMD: a workgroup that finds room on a CU the next batch's fill
-	 * already occupies (a 1024-thread group waited ~50 ms for sixteen free wave slots on one CU) */
-	constexpr int T = 256;
-	__shared__ unsigned long long s_part[T];
+/* inclusive scan of v over the 256 threads of a workgroup (s_wave: four slots of LDS); total = the sum of all */
+CVX_DEV unsigned long long finalize_block_scan(unsigned long long v, unsigned long long *s_wave, unsigned long long &total) {
+	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+	for (int k = 1; k < 64; k <<= 1) {
+		const unsigned long long u = __shfl_up(v, k, 64);
+		if (lane >= k) v += u;
+	}
+	__syncthreads();              /* (s_wave may still be read from the scan before) */
+	if (lane == 63) s_wave[w] = v;
+	__syncthreads();
+	unsigned long long before = 0, all = 0;
+#pragma unroll
+	for (int i = 0; i < kFinalizeTile / 64; ++i) {
+		const unsigned long long x = s_wave[i];
+		if (i < w) before += x;
+		all += x;
+	}
+	total = all;
+	return v + before;
+}
+
+__global__ void __launch_bounds__(kFinalizeTile)
+finalize_sum_kernel(const TileOut *tout, unsigned long long *part, int n_tiles, int nblk) {
+	__shared__ unsigned long long s_wave[kFinalizeTile / 64];
+	const int t = blockIdx.x * kFinalizeTile + threadIdx.x;
+	unsigned long long ops = 0, valid = 0;
+	if (t < n_tiles) {
+		const int status = tout[t].status, n_ops = tout[t].n_ops;
+		if (status == 0) { valid = 1; if (n_ops > 0) ops = (unsigned long long) n_ops; }
+	}
+	/* ops < 2^31 per tile and 256 tiles: both sums in one word, the count above bit 40 */
+	unsigned long long total;
+	finalize_block_scan(ops | (valid << 40), s_wave, total);
+	if (threadIdx.x == 0) {
+		part[blockIdx.x] = total & ((1ull << 40) - 1);
+		part[nblk + blockIdx.x] = total >> 40;
+	}
+}
+
+__global__ void __launch_bounds__(kFinalizeTile)
+finalize_scan_kernel(unsigned long long *part, int nblk, BatchSummary *sum, int32_t *counters, unsigned long long dense_cap) {
+	__shared__ unsigned long long s_wave[kFinalizeTile / 64];
 	const int tid = threadIdx.x;
-	const int per = (n_tiles + T - 1) / T;
-	const int t0 = min(n_tiles, tid * per), t1 = min(n_tiles, t0 + per);
-	unsigned long long mine = 0;
-	for (int t = t0; t < t1; ++t) {
-		const TileOut o = tout[t];
-		if (o.status == 0 && o.n_ops > 0) mine += (unsigned long long) o.n_ops;
+	unsigned long long carry = 0, valid = 0;
+	for (int b0 = 0; b0 < nblk; b0 += kFinalizeTile) {
+		const int b = b0 + tid;
+		const unsigned long long mine = b < nblk ? part[b] : 0ull;
+		unsigned long long total;
+		const unsigned long long incl = finalize_block_scan(mine, s_wave, total);
+		if (b < nblk) part[b] = carry + incl - mine;
+		carry += total;
+		finalize_block_scan(b < nblk ? part[nblk + b] : 0ull, s_wave, total);
+		valid += total;
 	}
-	s_part[tid] = mine;
-	__syncthreads();
-	/* Hillis-Steele inclusive scan over the partial sums */
-	for (int d = 1; d < T; d <<= 1) {
-		const unsigned long long v = (tid >= d) ? s_part[tid - d] : 0ull;
-		__syncthreads();
-		s_part[tid] += v;
-		__syncthreads();
-	}
-	unsigned long long off = s_part[tid] - mine;
-	int n_valid = 0;
-	for (int t = t0; t < t1; ++t) {
-		const TileOut o = tout[t];
-		ResultRec r;
-		r.score = o.score;
-		r.status = o.status;
-		r.best_x = o.best_x; r.best_y = o.best_y;
-		r.ref_position = o.ref_position; r.qstart = o.qstart; r.qend = o.qend;
-		r.n_ops = (o.status == 0) ? o.n_ops : 0;
-		r.ops_begin = off;
-		r.cells = plan[t].cells;
-		res[t] = r;
-		dst_off[t] = off;
-		if (o.status == 0) { n_valid += 1; if (o.n_ops > 0) off += (unsigned long long) o.n_ops; }
-	}
-	__shared__ int s_valid;
-	if (tid == 0) s_valid = 0;
-	__syncthreads();
-	if (n_valid) atomicAdd(&s_valid, n_valid);
-	__syncthreads();
-	if (tid == T - 1) {
-		BatchSummary b;
-		b.ops_total = s_part[T - 1];
-		b.dense_cap = dense_cap;
-		b.n_valid = s_valid;
-		b.n_redone = counters ? counters[0] : 0;
-		b.chain_task_ticks = counters ? reinterpret_cast<const unsigned long long *>(counters + kCtrChainTicks)[0] : 0ull;
-		b.chain_poll_ticks = counters ? reinterpret_cast<const unsigned long long *>(counters + kCtrChainTicks)[1] : 0ull;
-		*sum = b;
+	if (tid == 0) {
+		BatchSummary s;
+		s.ops_total = carry;
+		s.dense_cap = dense_cap;
+		s.n_valid = (int32_t) valid;
+		s.n_redone = counters ? counters[0] : 0;
+		s.chain_task_ticks = counters ? reinterpret_cast<const unsigned long long *>(counters + kCtrChainTicks)[0] : 0ull;
+		s.chain_poll_ticks = counters ? reinterpret_cast<const unsigned long long *>(counters + kCtrChainTicks)[1] : 0ull;
+		*sum = s;
 	}
 	/* last reader of the batch's counters (redo statistics, chain tickets): leave them zeroed for the
 	 * batch's next run (after the summary above has read the redo count) */
 	__syncthreads();
 	if (counters && tid < 64) counters[tid] = 0;
+}
+
+__global__ void __launch_bounds__(kFinalizeTile)
+finalize_write_kernel(const TileOut *tout, const TilePlan *plan, const unsigned long long *part, uint64_t *dst_off, ResultRec *res, int n_tiles) {
+	__shared__ unsigned long long s_wave[kFinalizeTile / 64];
+	const int t = blockIdx.x * kFinalizeTile + threadIdx.x;
+	const bool live = t < n_tiles;
+	TileOut o;
+	unsigned long long ops = 0;
+	if (live) {
+		o = tout[t];
+		if (o.status == 0 && o.n_ops > 0) ops = (unsigned long long) o.n_ops;
+	}
+	unsigned long long total;
+	const unsigned long long off = part[blockIdx.x] + finalize_block_scan(ops, s_wave, total) - ops;
+	if (!live) return;
+	ResultRec r;
+	r.score = o.score;
+	r.status = o.status;
+	r.best_x = o.best_x; r.best_y = o.best_y;
+	r.ref_position = o.ref_position; r.qstart = o.qstart; r.qend = o.qend;
+	r.n_ops = (o.status == 0) ? o.n_ops : 0;
+	r.ops_begin = off;
+	r.cells = plan[t].cells;
+	res[t] = r;
+	dst_off[t] = off;
 }
 
 /* dense[dst_off[t] .. +n_ops) = region of tile t (tiles that do not fit the arena are skipped:
@@ -1162,10 +1136,14 @@ hipError_t launch_backtrack(const BacktrackArgs &a, const int32_t *order, int n_
 	return hipGetLastError();
 }
 
-hipError_t launch_finalize(const TileOut *tout, const TilePlan *plan, uint64_t *dst_off, ResultRec *res,
+hipError_t launch_finalize(const TileOut *tout, const TilePlan *plan, uint64_t *dst_off, uint64_t *part, ResultRec *res,
 		BatchSummary *sum, int32_t *counters, int n_tiles, uint64_t dense_cap, hipStream_t st) {
-	hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, tout, plan, dst_off, res, sum, counters,
-			n_tiles, (unsigned long long) dense_cap);
+	/* part: 2 * finalize_blocks(n_tiles) words of scratch; an empty batch still gets its summary and its counters zeroed */
+	const int nblk = finalize_blocks(n_tiles);
+	unsigned long long *p = reinterpret_cast<unsigned long long *>(part);
+	if (nblk > 0) hipLaunchKernelGGL(finalize_sum_kernel, dim3(nblk), dim3(kFinalizeTile), 0, st, tout, p, n_tiles, nblk);
+	hipLaunchKernelGGL(finalize_scan_kernel, dim3(1), dim3(kFinalizeTile), 0, st, p, nblk, sum, counters, (unsigned long long) dense_cap);
+	if (nblk > 0) hipLaunchKernelGGL(finalize_write_kernel, dim3(nblk), dim3(kFinalizeTile), 0, st, tout, plan, p, dst_off, res, n_tiles);
 	return hipGetLastError();
 }
 

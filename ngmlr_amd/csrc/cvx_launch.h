@@ -117,7 +117,11 @@ hipError_t launch_plan(const RowDesc *rows, const RowSrc *rsrc, const TileIn *ti
  * anything else: one wave per tile.  Tiles are taken from order[0, n_order) (longest read first); order == NULL (one wave
  * per tile only): tile b for block b over all a.n_tiles */
 hipError_t launch_backtrack(const BacktrackArgs &a, const int32_t *order, int n_order, int group, hipStream_t st);
-hipError_t launch_finalize(const TileOut *tout, const TilePlan *plan, uint64_t *dst_off, ResultRec *res,
+/* result records, dst_off (each valid tile's slice of the dense ops arena) and the batch summary, over blocks of kFinalizeTile
+ * tiles; part: 2 * finalize_blocks(n_tiles) words of device scratch (per-block sums, then their scan) */
+static const int kFinalizeTile = 256;
+inline int finalize_blocks(int n_tiles) { return n_tiles > 0 ? (n_tiles + kFinalizeTile - 1) / kFinalizeTile : 0; }
+hipError_t launch_finalize(const TileOut *tout, const TilePlan *plan, uint64_t *dst_off, uint64_t *part, ResultRec *res,
 		BatchSummary *sum, int32_t *counters, int n_tiles, uint64_t dense_cap, hipStream_t st);
 hipError_t launch_compact(const int32_t *regions, const TileRun *trun, const TileOut *tout,
 		const uint64_t *dst_off, uint32_t *dense, int n_tiles, uint64_t dense_cap, hipStream_t st);

@@ -9,7 +9,7 @@
  *   compute  host: kernel class / arena offsets / LPT lists from the plan records, then the launch schedule
  *            (build_schedule, cvx_host_logic.h: list contents, one record per fill launch, stream slots, walk lanes);
  *            fill_ring_kernel per class (+ exact redo pass)                   (streams `main` + `aux`)
- *            backtrack_kernel, finalize_kernel (device-side prefix sums and result records),
+ *            backtrack_kernel, the finalize kernels (device-side prefix sums and result records),
  *            compact_ops_kernel, result records back to pinned memory               (stream `main`;
  *            optionally `post`, beside the next batch's fills: measured to gain nothing, see stage_compute)
  *   finish   dense ops back to pinned memory                                          (stream `io`)
@@ -127,7 +127,7 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	RC_TRY(b->d_plan.ensure(n1));
 	RC_TRY(b->d_trun.ensure(n1));
 	RC_TRY(b->d_tout.ensure(n1));
-	RC_TRY(b->d_dstoff.ensure(n1));
+	RC_TRY(b->d_dstoff.ensure(n1 + 2 * (size_t) finalize_blocks(n)));      /* ... + launch_finalize's per-block sums behind the n offsets */
 	RC_TRY(b->d_lists.ensure(2 * n1));             /* fill lists + backtrack order */
 	if (b->d_counters.cap < 64) {
 		RC_TRY(b->d_counters.ensure(64));
@@ -368,7 +368,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	HIP_TRY(hipMemcpyAsync(b->d_trun.p, b->h_trun.p, (size_t) n * sizeof(TileRun), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(b->d_tout.p, b->h_tout.p, (size_t) n * sizeof(TileOut), hipMemcpyHostToDevice, st));
 	if (sch.n_listed) HIP_TRY(hipMemcpyAsync(b->d_lists.p, b->h_lists.p, sch.n_listed * sizeof(int32_t), hipMemcpyHostToDevice, st));
-	/* (the batch's counters are zero: cleared when the arena was allocated and again by finalize_kernel,
+	/* (the batch's counters are zero: cleared when the arena was allocated and again by finalize_scan_kernel,
 	 * their last reader -- a memset here would be a tiny kernel that has to find a free wave slot among
 	 * the previous batch's 24 576 backtrack waves before this batch's fills may start: measured 7 ms) */
 	HIP_TRY(hipEventRecord(b->ev[4], st));        /* inputs of the fills are in place */
@@ -444,7 +444,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	if (!sch.per_class) RC_TRY(issue_walk(b, ba, sch.walk, sch.bt_begin, sch.n_walk, st, S_aux[0]));
 	ResultRec *d_rec = reinterpret_cast<ResultRec *>(b->d_res.p);
 	BatchSummary *d_sum = reinterpret_cast<BatchSummary *>(b->d_res.p + (size_t) n * sizeof(ResultRec));
-	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
+	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, b->d_dstoff.p + n, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
 	HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, n, b->dense_cap, st));
 	HIP_TRY(hipEventRecord(b->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(b->h_res.p, b->d_res.p, (size_t) n * sizeof(ResultRec) + sizeof(BatchSummary), hipMemcpyDeviceToHost, st));
@@ -593,6 +593,26 @@ int cvx_batch_ops_total(cvx_batch b, uint64_t *n_ops) {
 	ABI_GUARD_BEGIN
 	if (!b || !n_ops || b->state < kFinished) { set_err("cvx_batch_ops_total: batch not run"); return CVX_ERR_ARG; }
 	*n_ops = b->ops_total;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_batch_summary(cvx_batch b, uint64_t *ops_total, int32_t *n_valid, int32_t *n_redone) {
+	ABI_GUARD_BEGIN
+	if (!b || !ops_total || !n_valid || !n_redone || b->state < kFinished) { set_err("cvx_batch_summary: NULL argument / batch not run"); return CVX_ERR_ARG; }
+	*ops_total = 0; *n_valid = 0; *n_redone = 0;
+	if (b->n == 0) return CVX_OK;
+	const BatchSummary *s = b->summary();
+	*ops_total = s->ops_total; *n_valid = s->n_valid; *n_redone = s->n_redone;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_batch_plan(cvx_batch b, int32_t first, int32_t count, cvx_tile_plan *out) {
+	ABI_GUARD_BEGIN
+	static_assert(sizeof(cvx_tile_plan) == sizeof(TilePlan), "cvx_tile_plan mirrors TilePlan");
+	if (!b || b->state < kFinished || first < 0 || count < 0 || (int64_t) first + count > b->n || (count > 0 && !out)) { set_err("cvx_batch_plan: bad range / batch not run"); return CVX_ERR_ARG; }
+	if (count) memcpy(out, b->plan() + first, (size_t) count * sizeof(TilePlan));
 	return CVX_OK;
 	ABI_GUARD_END
 }

@@ -53,10 +53,16 @@ static const int kLateMinGroups = 128;
 static const int kLateShift = 5;       /* exactly tracked tail = max(kLateMinGroups, groups >> kLateShift): a 10 kb tile tracks its last 161 groups
                                         * = 644 steps, two corridor widths (round 3: groups / 8; 109.1 -> 107.9 ms per 49 120 tiles, still no tile redone) */
 static const int kPadRedo = 2;
-/* fill_ring_kernel<.., TAB>: entries of the LDS penalty table, and the run from which the run registers are clamped (the
- * penalty must be constant from kPenClamp on: checked by the host per scoring; a run grows by at most four between two clamps) */
-static const int kPenEntries = 64;
-static const int kPenClamp = kPenEntries - 8;
+/* fill_ring_kernel<.., TAB>: the run to which the run registers are clamped (the penalty must be constant from kPenClamp
+ * on: checked by the host per scoring), the steps between two clamps (the clamp sits in the direction flush, once per 32-step
+ * block) and the entries of the LDS penalty table.  A register grows by at most one run per step, so the largest run a step
+ * looks up is kPenClamp + kPenClampSteps - 1 and the largest a register holds, right before the next clamp, is
+ * kPenClamp + kPenClampSteps (88: fits the 16 bits a gang's boundary record has for it). */
+static const int kPenClamp = 56;
+static const int kPenClampSteps = 32;
+static const int kPenEntries = 96;
+static_assert(kPenEntries >= kPenClamp + kPenClampSteps + 1, "the penalty table must cover every run reachable between two clamps");
+static_assert(kPenClamp + kPenClampSteps < 65536, "a gang's boundary record keeps the run in 16 bits");
 static const int kGangDepth = 8;       /* fill_ring_kernel<.., G > 1>: steps of lane-boundary records a wave keeps for its successor (> G) */
 static const int kChainChunk = 16;     /* chained row blocks: steps per boundary hand-off (multiple of 4, power of two, <= 64) */
 
@@ -219,7 +225,7 @@ struct TileOut {
 	int32_t pad;           /* 0 filled, 1 backtracked, kPadRedo: needs the exact-tracking fill pass */
 };
 
-struct ResultRec {         /* same layout as cvx_result (include/cvx_align.h), written by finalize_kernel */
+struct ResultRec {         /* same layout as cvx_result (include/cvx_align.h), written by finalize_write_kernel */
 	float score;
 	int32_t status;
 	int32_t best_x, best_y;
