@@ -491,7 +491,9 @@ int cvx_score_kernel_ms(cvx_handle h, float *ms);
  * cvx_genome_decode; CVX_STAGE_SEARCH: every kernel of cvx_search_batch(_ex) (count, vote batches of each attempt of the
  * ladder, compaction) summed, without the host round trips between them. */
 enum { CVX_STAGE_SCORE = 0, CVX_STAGE_DECODE = 1, CVX_STAGE_SEARCH = 2,
-	CVX_STAGE_SCORE_WINDOWS = 3 /* stage_score_windows_kernel alone, of the last cvx_score_windows* call waited for (its time is part of CVX_STAGE_SCORE too) */ };
+	CVX_STAGE_SCORE_WINDOWS = 3 /* stage_score_windows_kernel alone, of the last cvx_score_windows* call waited for (its time is part of CVX_STAGE_SCORE too) */,
+	CVX_STAGE_SEARCH_SCORE = 4 /* the plan + stage + score kernels of the handle's last cvx_search_score_arena (0 when it had no candidate); its search
+	                            * kernels are reported by CVX_STAGE_SEARCH as for any search */ };
 int cvx_stage_kernel_ms(cvx_handle h, int32_t stage, float *ms);
 
 /* Asynchronous sub-read scoring (ABI 9, additive): the scores cvx_score_batch returns, for callers that must not block
@@ -547,6 +549,32 @@ int cvx_stage_windows(cvx_handle h, cvx_genome g, int32_t n_reads, const uint8_t
 int cvx_stage_windows_host(const uint8_t *bin_ref, uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts,
 		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n, const cvx_score_window *pairs,
 		uint8_t *out, uint64_t cap, uint64_t *ref_off, uint64_t *qry_off, int32_t *status, uint64_t *used);
+/* Search and score in one call (ABI 9, additive): cvx_search_batch_arena and, behind it on the same stream, the scoring
+ * cvx_score_windows would do for every candidate of every list -- ngmlr's CS::RunBatch followed by ScoreBuffer::DoRun for the
+ * sub-reads of a batch -- without the lists visiting the host in between: plan_candidate_windows_kernel (cvx_score_cands.hip)
+ * turns the search's dense list into one window descriptor per candidate where it lies, stage_score_windows_kernel reads the
+ * resident genome g and the read block the vote has just used, score_diag_kernel scores.  One upload of the reads; the waits of
+ * the search's ladder stay as they are (one per attempt), the second call with its upload, its launch and its wait is gone.
+ *   outputs   everything cvx_search_batch_arena returns means what it means there (cands[q].score is the vote's score);
+ *   sw_scores[q], parallel to cands: the float cvx_score_windows returns for the pair (cands[q].location - window_lead in
+ *             uint64 arithmetic, buffer_len, the read that owns q, cands[q].reverse) -- for ScoreBuffer: buffer_len = refMaxLen,
+ *             window_lead = corridor >> 1 (src/ScoreBuffer.h:65-72, ScoreBuffer.cpp:111);
+ *   sw_status[q] (may be NULL): 0 scored; 1 DecodeRefSequence returns false for that position (at or behind GetConcatRefLen(),
+ *             a location inside the lead that wrapped included), sw_scores[q] = -1.0f; 2 the read's list has max_cmrs entries
+ *             or more -- CS::CollectResultsStd does not hand such a list to AllocScores (src/CS.cpp:264-266), nothing of it is
+ *             scored -- sw_scores[q] = -1.0f (2 wins over 1).
+ * Only the shape of the CS feed: CVX_ERR_ARG for buffer_len < 3 or > 2048, a read of more than 511 characters (every pair goes to
+ * score_diag_kernel -- cvx_score_windows' diagonal class, and beside it the one window of buffer_len 2048 that is 2 048 characters
+ * long, a byte past that class's line, which the kernel holds and scores exactly; CVX_TUNE_SCORE_NO_DIAG does not apply to this
+ * entry), window_lead < 0, max_cmrs < 1, g on another
+ * device than h, sw_scores == NULL with cand_capacity > 0.  Other shapes keep the two calls.  CVX_ERR_CAPACITY as for the
+ * search, with *cand_used set and nothing scored.  A call without a candidate launches none of the three kernels. */
+int cvx_search_score_arena(cvx_handle h, cvx_index ix, cvx_genome g, int32_t n, const uint8_t *arena, const uint64_t *offsets,
+		float sensitivity, float min_kmer_hits, int32_t bin_shift, int32_t first_bits,
+		int32_t buffer_len, int32_t window_lead, int32_t max_cmrs,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+		float *max_hit, int32_t *kmer_misses,
+		float *sw_scores /* parallel to cands */, int32_t *sw_status /* parallel to cands; may be NULL */);
 /* GetConcatRefLen() (src/SequenceProvider.cpp:638-640) of an encoded genome: the L of the window rule */
 int cvx_genome_concat_len(uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts, uint64_t *concat_len);
 

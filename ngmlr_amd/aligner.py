@@ -519,6 +519,36 @@ class KmerIndex:
             break
         return ncand[:n], begin[:n], cands[:int(used.value)], max_hit[:n], misses[:n]
 
+    def search_score_arena(self, genome: "Genome", arena: np.ndarray, offsets: np.ndarray, buffer_len: int, window_lead: int, max_cmrs: int,
+                           sensitivity: float = 0.8, min_kmer_hits: float = 0.0, bin_shift: int = 4, first_bits: int = 0):
+        """cvx_search_score_arena: search_arena and, in the same device call, every candidate scored against its window of the resident
+        genome (position = location - window_lead, buffer_len characters of buffer) -> what search_arena returns plus
+        (sw_scores float32[used], sw_status int32[used]), parallel to cands; status 1: no window at that position, 2: the read's list
+        has max_cmrs entries or more (both score -1.0)."""
+        n = len(offsets) - 1
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        max_hit = np.zeros(max(n, 1), dtype=np.float32)
+        misses = np.zeros(max(n, 1), dtype=np.int32)
+        ncand = np.zeros(max(n, 1), dtype=np.int32)
+        begin = np.zeros(max(n, 1), dtype=np.uint64)
+        used = C.c_uint64()
+        cap = 1 << 16
+        while True:
+            cands = np.zeros(cap, dtype=CANDIDATE_DTYPE)
+            sw_scores = np.zeros(cap, dtype=np.float32)
+            sw_status = np.zeros(cap, dtype=np.int32)
+            rc = self.al.lib.cvx_search_score_arena(self.al.h, self.ix, genome.g, n, arena.ctypes.data, offsets.ctypes.data, sensitivity, min_kmer_hits,
+                                                   bin_shift, first_bits, buffer_len, window_lead, max_cmrs,
+                                                   ncand.ctypes.data, begin.ctypes.data, cands.ctypes.data, cap, C.byref(used),
+                                                   max_hit.ctypes.data, misses.ctypes.data, sw_scores.ctypes.data, sw_status.ctypes.data)
+            if rc == -6 and used.value > cap:
+                cap = int(used.value) + int(used.value) // 8 + 64
+                continue
+            capi.check(rc)
+            break
+        u = int(used.value)
+        return ncand[:n], begin[:n], cands[:u], max_hit[:n], misses[:n], sw_scores[:u], sw_status[:u]
+
     def free(self) -> None:
         if self.ix:
             self.al.lib.cvx_index_free(self.al.h, self.ix)

@@ -16,7 +16,7 @@ CVX_OK = 0
 CREATE_SERVICE, CREATE_SCALAR_TWIN = 1, 2      # cvx_create_ex flags
 FORMAT_SCALAR_TWIN = 1                         # cvx_format_alignment_ex / cvx_format_batch_ex flags
 NOT_WRITTEN = -1                               # cigar_op_count / sv_type of the scalar twin's text stage
-STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS = 0, 1, 2, 3      # cvx_stage_kernel_ms
+STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS, STAGE_SEARCH_SCORE = 0, 1, 2, 3, 4      # cvx_stage_kernel_ms
 ERR_NAMES = {0: "CVX_OK", -1: "CVX_ERR_NO_DEVICE", -2: "CVX_ERR_PARAMS", -3: "CVX_ERR_ARG",
              -4: "CVX_ERR_OOM", -5: "CVX_ERR_HIP", -6: "CVX_ERR_CAPACITY"}
 TILE_STATUS = {0: "ok", 1: "invalid-row0", 2: "invalid-edge", 3: "invalid-length", 4: "too-large",
@@ -35,7 +35,8 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_sam_record_text", "cvx_sam_unmapped_text", "cvx_sam_batch", "cvx_stage_kernel_ms", "cvx_search_last_attempts", "cvx_index_build", "cvx_index_build_device",
            "cvx_corridor_fit", "cvx_corridor_fit_batch", "cvx_create_ex", "cvx_runtime_regime", "cvx_search_batch_arena",
            "cvx_score_submit", "cvx_score_poll", "cvx_score_wait", "cvx_format_alignment_ex", "cvx_format_batch_ex",
-           "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len")
+           "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len",
+           "cvx_search_score_arena")
 
 
 class CvxParams(C.Structure):
@@ -224,6 +225,9 @@ def load(path: str = None) -> C.CDLL:
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
     lib.cvx_search_batch_arena.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+    lib.cvx_search_score_arena.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.cvx_score_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.cvx_stage_kernel_ms.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float)]
     lib.cvx_search_last_attempts.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

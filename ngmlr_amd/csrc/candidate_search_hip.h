@@ -47,12 +47,28 @@ public:
 		std::vector<float> maxHit;           /* maxHitNumber -> MappedRead::s */
 		std::vector<int32_t> kmerMisses;     /* kCount: k-mers of the read the table knows in neither orientation */
 		std::vector<int32_t> attempts;       /* table sizes tried: > 1 = the first attempt overflowed (CS::m_Overflows counts those) */
+		/* SearchAndScore only: parallel to cands, what ScoreBuffer::DoRun would score for the entry (cvx_search_score_arena); the
+		 * reads back to back, as that entry takes them */
+		std::vector<float> swScores;
+		std::vector<int32_t> swStatus;       /* 0 scored; 1 no window at that position; 2 the list has maxCmrs entries or more (both score -1) */
+		std::vector<unsigned char> arena;
+		std::vector<uint64_t> offsets;
 	};
 	/* throws 1 on a device error */
 	void Search(Batch & b, float sensitivity, float minKmerHits, int binShift, int firstTableBits = 16);
+	/* Search, and in the same device call the score of every candidate against its window of the genome
+	 * Convex::DeviceWindows::SetGenome announced (cvx_search_score_arena): position = location - windowLead, bufferLen bytes of
+	 * buffer -- ScoreBuffer's refMaxLen and corridor >> 1 -- lists of maxCmrs entries or more left unscored.  The genome is the
+	 * device's shared copy (device_genome.h: the one StrippedSWHip::BatchScoreWindows uses, uploaded once per logical device).
+	 * Only for sub-reads of at most 511 bases and bufferLen in 3 .. 2048; throws 1 on a device error or a shape outside that. */
+	void SearchAndScore(Batch & b, float sensitivity, float minKmerHits, int binShift, int firstTableBits, int bufferLen, int windowLead, int maxCmrs);
+	/* a batch the binding (cs_feed_binding.inc) sent through Search and the scorer's own call, and why: the exit line's counts */
+	enum { kFeedOff = 0, kFeedNoGenome, kFeedScorer, kFeedShape, kFeedReasons };
+	static void NoteTwoCallBatch(int why);
 
 private:
 	CandidateSearchHip() { }
+	void run(Batch & b, float sensitivity, float minKmerHits, int binShift, int firstTableBits, int const * scoreShape);
 	/* what Get() was given: a device's copy of the table is uploaded on that device's first search */
 	int kmerLength; void const * refTableIndex; uint32_t const * refTable; uint32_t nLocations; uint64_t unitOffset;
 };

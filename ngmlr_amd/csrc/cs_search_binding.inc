@@ -49,7 +49,14 @@
 			 * it runs as ONE attempt at 2^20 here, where the reference runs one attempt at the size given: said once, not silently (ADVICE r5) */
 			static bool const cvxClampSaid = [](int bits) { if (bits > 20) Log.Message("CandidateSearchHip: --search-table-length %d runs as 2^20 on the device (one attempt, like the reference's single attempt at the user's size)", bits); return true; }(Config.getCsSearchTableLength() != 0 ? c_SrchTableBitLen : 0);
 			(void) cvxClampSaid;
-			cvxSearch->Search(cvxBatch, m_CsSensitivity, (float) Config.getMinKmerHits(), Config.getBinSize(), cvxFirstBits < 8 ? 8 : (cvxFirstBits > 20 ? 20 : cvxFirstBits));
+			int const cvxBits = cvxFirstBits < 8 ? 8 : (cvxFirstBits > 20 ? 20 : cvxFirstBits);
+			bool cvxFused = false;      /* the batch was searched and scored in one call (cs_feed_binding.inc, variant ngmlr_hip_feed) */
+#ifdef CVX_CS_FEED_BINDING
+#define CVX_CS_FEED_SITE 1
+#include "cs_feed_binding.inc"
+#undef CVX_CS_FEED_SITE
+#endif
+			if (!cvxFused) cvxSearch->Search(cvxBatch, m_CsSensitivity, (float) Config.getMinKmerHits(), Config.getBinSize(), cvxBits);
 			static int const cvxMaxScores = Config.getMaxCMRs();
 			int cvxScoresSum = 0;
 			for (size_t i = 0; i < cvxN; ++i) {
@@ -82,7 +89,13 @@
 						read->AllocScores(tmp, n);
 					cvxScoresSum += n;
 				}
-				SendToBuffer(read, sw, out);
+				bool cvxSent = false;
+#ifdef CVX_CS_FEED_BINDING
+#define CVX_CS_FEED_SITE 2
+#include "cs_feed_binding.inc"
+#undef CVX_CS_FEED_SITE
+#endif
+				if (!cvxSent) SendToBuffer(read, sw, out);
 			}
 			return cvxScoresSum;
 		}

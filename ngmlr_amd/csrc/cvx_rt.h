@@ -148,6 +148,7 @@ int ensure_streams(cvx_context *c);
 /* the per-handle state of the search and of the scoring, owned by their files (cvx_destroy) */
 void search_state_free(cvx_search_state *ss);
 float search_kernel_ms(const cvx_search_state *ss);      /* of the handle's last search (cvx_stage_kernel_ms) */
+float search_score_kernel_ms(const cvx_search_state *ss);      /* the plan + stage + score kernels of its last cvx_search_score_arena */
 void score_state_free(cvx_score_state *ss);
 
 }  // namespace cvx

@@ -15,6 +15,8 @@
 
 #include "cvx_index_build.h"
 #include "cvx_rt.h"
+#include "cvx_score_cands.h"
+#include "cvx_score_stage.h"
 
 /* Per-handle state of the candidate search: staging and device buffers live as long as the handle, so that the steady
  * state of a caller that searches batch after batch (ngmlr's CS threads: a few hundred sub-reads per call) allocates
@@ -38,6 +40,16 @@ struct cvx_search_state {
 	std::vector<hipEvent_t> kev;
 	size_t kev_used = 0;
 	float kernel_ms = 0.0f;
+	/* cvx_search_score_arena: one descriptor, pair, score and status per candidate, the strings of all of them, and the scores and
+	 * status words on their way back; the plan + stage + score kernels of the last such call between ev_f0 and ev_f1 */
+	DevBuf<ScoreWinDesc> d_fdesc;
+	DevBuf<ScorePair> d_fpairs;
+	DevBuf<uint8_t> d_fseq;
+	DevBuf<float> d_fout;
+	DevBuf<int32_t> d_fstatus;
+	PinBuf h_fout;
+	hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr;
+	float fused_ms = 0.0f;
 	int kmark(hipStream_t st) {
 		if (kev_used == kev.size()) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); kev.push_back(e); }
 		HIP_TRY(hipEventRecord(kev[kev_used++], st));
@@ -49,8 +61,20 @@ struct cvx_search_state {
 		h_seq.release(); h_meta.release(); h_out.release();
 		d_seq.release(); d_off.release(); d_listoff.release(); d_begin.release(); d_srcoff.release(); h_srcoff.release(); d_len.release(); d_ncand.release(); d_work.release(); d_miss.release();
 		d_events.release(); d_maxhit.release(); d_scores.release(); d_rlist.release(); d_undo.release(); d_ticket.release(); d_cand.release(); d_dense.release(); d_keys.release();
+		d_fdesc.release(); d_fpairs.release(); d_fseq.release(); d_fout.release(); d_fstatus.release(); h_fout.release();
+		if (ev_f0) { (void) hipEventDestroy(ev_f0); ev_f0 = nullptr; }
+		if (ev_f1) { (void) hipEventDestroy(ev_f1); ev_f1 = nullptr; }
 		if (done) { (void) hipEventDestroy(done); done = nullptr; }
 	}
+};
+
+/* what cvx_search_score_arena adds to a search: the scoring of every candidate behind the compaction (checked by the entry) */
+struct SearchScoreArgs {
+	const cvx_genome_s *g;
+	int32_t buffer_len, window_lead, max_cmrs;
+	uint64_t max_read_bytes;         /* the longest read of the call, its NUL included */
+	float *sw_scores;
+	int32_t *sw_status;              /* may be NULL */
 };
 
 namespace {
@@ -71,6 +95,7 @@ void search_state_free(cvx_search_state *ss) {
 }
 
 float search_kernel_ms(const cvx_search_state *ss) { return ss ? ss->kernel_ms : 0.0f; }
+float search_score_kernel_ms(const cvx_search_state *ss) { return ss ? ss->fused_ms : 0.0f; }
 }  // namespace cvx
 
 extern "C" {
@@ -299,7 +324,7 @@ void cvx_index_free(cvx_handle h, cvx_index ix) {
 static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *const *seqs, const int32_t *lens, const uint8_t *arena, const uint64_t *offsets,
 		float sensitivity, float min_hits, int32_t bin_shift, int32_t first_bits,
 		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
-		float *max_hit, int32_t *kmer_misses) {
+		float *max_hit, int32_t *kmer_misses, const SearchScoreArgs *fs = nullptr) {
 	static_assert(sizeof(SearchCandidate) == sizeof(cvx_candidate), "SearchCandidate mirrors cvx_candidate");
 	/* bin_shift >= 1: the "bin is listed" flag lives in bit 63 of the vote table's key, and with a shift of 0 a vote near the
 	 * start of the genome (location - offset in the read < 0) would set that bit itself; ngmlr's bin size is 4 */
@@ -309,6 +334,7 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 	}
 	if (ix->device != h->device) { set_err("cvx_search_batch: the index lives on device %d, the handle on %d", ix->device, h->device); return CVX_ERR_ARG; }
 	if (cand_used) *cand_used = 0;
+	if (fs && h->search) h->search->fused_ms = 0.0f;      /* (CVX_STAGE_SEARCH_SCORE is this call's from here on, also when it launches nothing) */
 	if (n == 0) return CVX_OK;
 	HIP_TRY(hipSetDevice(h->device));
 	if (!h->search) { h->search = new (std::nothrow) cvx_search_state(); if (!h->search) return CVX_ERR_OOM; }
@@ -335,13 +361,13 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 	const uint8_t *src = arena ? arena + offsets[0] : nullptr;
 	const bool zero_copy = arena && in_pinned_block(reinterpret_cast<const char *>(src), bytes + 4);
 	if (!zero_copy) RC_TRY(ss->h_seq.ensure((size_t) bytes + 64));
-	/* meta: [off u64 n][list_off u64 n][begin u64 n][len i32 n][work i32 n] */
-	RC_TRY(ss->h_meta.ensure(n1 * (8 + 8 + 8 + 4 + 4) + 64));
+	/* meta: [off u64 n][list_off u64 n][begin u64 n + 1][len i32 n][work i32 n] */
+	RC_TRY(ss->h_meta.ensure(n1 * (8 + 8 + 8 + 4 + 4) + 8 + 64));
 	/* out: [events u64 n][ncand i32 n][miss i32 n][maxhit f32 n] (the dense candidates get their own buffer below) */
 	RC_TRY(ss->h_out.ensure(n1 * (8 + 4 + 4 + 4) + 64));
 	uint8_t *hseq = zero_copy ? nullptr : ss->h_seq.as<uint8_t>();
 	uint64_t *h_off = ss->h_meta.as<uint64_t>(), *h_listoff = h_off + n1, *h_begin = h_listoff + n1;
-	int32_t *h_len = reinterpret_cast<int32_t *>(h_begin + n1), *h_work = h_len + n1;
+	int32_t *h_len = reinterpret_cast<int32_t *>(h_begin + n1 + 1), *h_work = h_len + n1;
 	unsigned long long *h_events = ss->h_out.as<unsigned long long>();
 	int32_t *h_ncand = reinterpret_cast<int32_t *>(h_events + n1), *h_miss = h_ncand + n1;
 	float *h_maxhit = reinterpret_cast<float *>(h_miss + n1);
@@ -360,7 +386,7 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 		memset(hseq + at, 0, 64);
 	}
 	RC_TRY(ss->d_seq.ensure((size_t) bytes + 64));
-	RC_TRY(ss->d_off.ensure(n1)); RC_TRY(ss->d_listoff.ensure(n1)); RC_TRY(ss->d_begin.ensure(n1));
+	RC_TRY(ss->d_off.ensure(n1)); RC_TRY(ss->d_listoff.ensure(n1)); RC_TRY(ss->d_begin.ensure(n1 + 1));
 	RC_TRY(ss->d_len.ensure(n1)); RC_TRY(ss->d_ncand.ensure(n1)); RC_TRY(ss->d_work.ensure(n1)); RC_TRY(ss->d_miss.ensure(n1));
 	RC_TRY(ss->d_events.ensure(n1)); RC_TRY(ss->d_maxhit.ensure(n1));
 	SearchArgs a;
@@ -571,7 +597,10 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 	 * two slots per vote) */
 	uint64_t need = 0;
 	for (int i = 0; i < n; ++i) { h_begin[i] = need; cand_begin[i] = need; n_candidates[i] = h_ncand[i]; if (h_ncand[i] > 0) need += (uint64_t) h_ncand[i]; }
+	h_begin[n] = need;              /* (plan_candidate_windows_kernel's end of the last list) */
 	if (cand_used) *cand_used = need;
+	/* (the launchers behind the compaction count slots in an int; refused here, where nothing of the call is queued any more) */
+	if (fs && need > 0x7fffffffull) { set_err("cvx_search_score_arena: %llu candidates in one call", (unsigned long long) need); return CVX_ERR_ARG; }
 	if (max_hit || kmer_misses) {
 		HIP_TRY(hipMemcpyAsync(h_maxhit, ss->d_maxhit.p, n1 * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(h_miss, ss->d_miss.p, n1 * 4, hipMemcpyDeviceToHost, st));
@@ -583,16 +612,44 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 	}
 	if (need) {
 		RC_TRY(ss->d_dense.ensure((size_t) need + 64));
-		HIP_TRY(hipMemcpyAsync(ss->d_begin.p, h_begin, n1 * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(ss->d_begin.p, h_begin, (n1 + 1) * 8, hipMemcpyHostToDevice, st));
 		HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
 		RC_TRY(ss->kmark(st));
 		HIP_TRY(launch_search_compact(ss->d_cand.p, ss->d_srcoff.p, ss->d_ncand.p, ss->d_begin.p, ss->d_dense.p, n, st));
 		RC_TRY(ss->kmark(st));
+		if (fs) {
+			/* The scoring of every candidate, queued behind the compaction: the lists are planned where they lie (d_dense), the
+			 * strings come from the resident genome and from the read block the vote has just used, and both launchers run over all
+			 * `need` slots -- a candidate that is not scored is two empty strings there.  Nothing is uploaded. */
+			const CandWinSlots slots = cand_windows_slots(fs->buffer_len, fs->max_read_bytes, need);
+			RC_TRY(ss->d_fdesc.ensure((size_t) need)); RC_TRY(ss->d_fpairs.ensure((size_t) need));
+			RC_TRY(ss->d_fout.ensure((size_t) need)); RC_TRY(ss->d_fstatus.ensure((size_t) need));
+			RC_TRY(ss->d_fseq.ensure((size_t) slots.seq_bytes + 256));
+			RC_TRY(ss->h_fout.ensure((size_t) need * 8));
+			if (!ss->ev_f0) { HIP_TRY(hipEventCreate(&ss->ev_f0)); HIP_TRY(hipEventCreate(&ss->ev_f1)); }
+			HIP_TRY(hipEventRecord(ss->ev_f0, st));
+			HIP_TRY(launch_plan_candidate_windows(ss->d_dense.p, ss->d_begin.p, ss->d_ncand.p, ss->d_off.p, ss->d_len.p, n, need,
+					score_windows_concat_len(fs->g->n_nibbles), fs->buffer_len, fs->window_lead, fs->max_cmrs, slots, ss->d_fdesc.p, ss->d_fstatus.p, st));
+			HIP_TRY(launch_stage_score_windows(fs->g->d_bin.p, ss->d_seq.p, ss->d_fdesc.p, (int) need, ss->d_fseq.p, ss->d_fpairs.p, st));
+			HIP_TRY(launch_score_diag(ss->d_fseq.p, ss->d_fpairs.p, ss->d_fout.p, (int) need, st));
+			HIP_TRY(hipEventRecord(ss->ev_f1, st));
+		}
 		/* (straight into the caller's memory: pageable unless it came from cvx_host_alloc, then the copy is staged by the runtime) */
 		HIP_TRY(hipMemcpyAsync(cands, ss->d_dense.p, (size_t) need * sizeof(SearchCandidate), hipMemcpyDeviceToHost, st));
+		if (fs) {
+			HIP_TRY(hipMemcpyAsync(ss->h_fout.p, ss->d_fout.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(ss->h_fout.as<uint8_t>() + (size_t) need * 4, ss->d_fstatus.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
+		}
 	}
 	RC_TRY(search_wait(ss, st));
 	for (size_t q = 0; q + 1 < ss->kev_used; q += 2) ss->kernel_ms += ev_ms(ss->kev[q], ss->kev[q + 1]);
+	if (fs && need) {
+		ss->fused_ms = ev_ms(ss->ev_f0, ss->ev_f1);
+		const float *o = ss->h_fout.as<float>();
+		const int32_t *os = reinterpret_cast<const int32_t *>(o + need);
+		for (uint64_t q = 0; q < need; ++q) fs->sw_scores[q] = os[q] == kCandScored ? o[q] : -1.0f;
+		if (fs->sw_status) memcpy(fs->sw_status, os, (size_t) need * 4);
+	}
 	if (trace) fprintf(stderr, "cvx_search_batch: %d reads, %llu bases, %llu candidates, %.2f ms:%s\n", n, (unsigned long long) bytes - (unsigned long long) n, (unsigned long long) need, tr_ms(), tr.c_str());
 	if (max_hit) memcpy(max_hit, h_maxhit, n1 * 4);
 	if (kmer_misses) memcpy(kmer_misses, h_miss, n1 * 4);
@@ -615,6 +672,36 @@ int cvx_search_batch_arena(cvx_handle h, cvx_index ix, int32_t n, const uint8_t 
 	ABI_GUARD_BEGIN
 	if (n > 0 && (!arena || !offsets)) { set_err("cvx_search_batch_arena: NULL arena"); return CVX_ERR_ARG; }
 	return search_common(h, ix, n, nullptr, nullptr, arena ? arena : reinterpret_cast<const uint8_t *>(""), offsets, sensitivity, min_hits, bin_shift, first_bits, n_candidates, cand_begin, cands, cand_capacity, cand_used, max_hit, kmer_misses);
+	ABI_GUARD_END
+}
+
+int cvx_search_score_arena(cvx_handle h, cvx_index ix, cvx_genome g, int32_t n, const uint8_t *arena, const uint64_t *offsets,
+		float sensitivity, float min_hits, int32_t bin_shift, int32_t first_bits,
+		int32_t buffer_len, int32_t window_lead, int32_t max_cmrs,
+		int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+		float *max_hit, int32_t *kmer_misses, float *sw_scores, int32_t *sw_status) {
+	ABI_GUARD_BEGIN
+	if (!h || !g || (n > 0 && (!arena || !offsets))) { set_err("cvx_search_score_arena: NULL handle, genome or arena"); return CVX_ERR_ARG; }
+	if (g->device != h->device) { set_err("cvx_search_score_arena: the genome lies on device %d, the handle on %d", g->device, h->device); return CVX_ERR_ARG; }
+	/* The shape score_diag_kernel takes: reads of at most 511 characters (its exactness needs min(Q, R) <= 512 with the NULs) and a
+	 * window of at most 2 048 characters.  score_class draws its line at 2 048 bytes WITH the NUL, and one window of buffer_len
+	 * 2 048 is a byte longer: the 'x' tail behind an odd position gives 2 048 characters.  The two-call path scores that pair with
+	 * the wave kernel; here it goes to score_diag_kernel like the rest, which holds it -- its row of reference codes is
+	 * kDiagMaxRef + 64 = 2 112 bytes (cvx_score.hip) and the result is exact whatever R is -- and returns the same float
+	 * (tests/test_gpu_search_score.py pins that shape against the two calls, tests/cpp/cand_windows_logic_test.cpp its slot). */
+	if (buffer_len < 3 || buffer_len > 2048 || max_cmrs < 1 || window_lead < 0) {
+		set_err("cvx_search_score_arena: buffer_len %d (3..2048), window_lead %d (>= 0), max_cmrs %d (>= 1)", buffer_len, window_lead, max_cmrs); return CVX_ERR_ARG;
+	}
+	if (cand_capacity > 0 && !sw_scores) { set_err("cvx_search_score_arena: NULL sw_scores"); return CVX_ERR_ARG; }
+	SearchScoreArgs fs = {g, buffer_len, window_lead, max_cmrs, 1, sw_scores, sw_status};
+	for (int32_t i = 0; i < n; ++i) {
+		if (offsets[i + 1] <= offsets[i]) continue;      /* (refused by the search, with its own message) */
+		const uint64_t rb = offsets[i + 1] - offsets[i];
+		if (rb > 512) { set_err("cvx_search_score_arena: read %d has %llu characters (at most 511: the diagonal kernel's shape)", i, (unsigned long long) rb - 1); return CVX_ERR_ARG; }
+		fs.max_read_bytes = std::max(fs.max_read_bytes, rb);
+	}
+	return search_common(h, ix, n, nullptr, nullptr, arena ? arena : reinterpret_cast<const uint8_t *>(""), offsets, sensitivity, min_hits, bin_shift, first_bits,
+			n_candidates, cand_begin, cands, cand_capacity, cand_used, max_hit, kmer_misses, &fs);
 	ABI_GUARD_END
 }
 

@@ -17,6 +17,14 @@
 
 #include "cvx_align.h"
 
+/* score_window_shape is the one statement of the window rule: plan_candidate_windows_kernel (cvx_score_cands.hip) calls it on the
+ * device.  A plain C++ compiler sees no qualifier. */
+#if defined(__HIPCC__)
+#define CVX_HOST_DEVICE __host__ __device__
+#else
+#define CVX_HOST_DEVICE
+#endif
+
 namespace cvx {
 
 /* shape classes of cvx_score_submit, in launch order */
@@ -52,7 +60,7 @@ struct ScoreWinShape {
 	int32_t n_plain;       /* leading characters that are the nibbles position, position + 1, ... */
 	int32_t ref_chars;     /* strlen of the window: n_plain, the 'x' of an odd len, the `end` 'x' behind the genome */
 };
-inline ScoreWinShape score_window_shape(uint64_t position, int32_t buffer_len, uint64_t L) {
+CVX_HOST_DEVICE inline ScoreWinShape score_window_shape(uint64_t position, int32_t buffer_len, uint64_t L) {
 	ScoreWinShape s = {true, 0, 0};
 	if (position >= L) return s;
 	uint64_t len = (uint64_t) buffer_len - 2, end = 0;                   /* (buffer_len >= 3) */

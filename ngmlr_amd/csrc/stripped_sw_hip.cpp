@@ -2,6 +2,7 @@
 #include "stripped_sw_hip.h"
 #include "service_device.h"
 #include "convex_align_hip.h"
+#include "device_genome.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -23,7 +24,6 @@ int g_users[kMaxDevices] = {0};
 long g_joined[kMaxDevices] = {0};
 /* statistics, printed when the last scorer of a device goes (like SharedAligner's line) */
 struct DevStats { std::atomic<long> calls{0}, pairs{0}, single{0}, winCalls{0}, winPairs{0}, winFailed{0}; std::atomic<long long> ns{0}, ctorNs{0}; };
-cvx_genome g_genome[kMaxDevices] = {0};      /* DeviceWindows' genome on the logical device: one per device, shared by its lanes */
 DevStats g_st[kMaxDevices];      /* per logical device: the line of a device says what ran THERE */
 std::chrono::steady_clock::time_point const g_loaded = std::chrono::steady_clock::now();      /* ~ process start */
 double g_firstCtorBegin = -1.0, g_firstCtorEnd = -1.0;
@@ -45,17 +45,18 @@ StrippedSWHip::StrippedSWHip(int const deviceId) : device(deviceId >= 0 && devic
 		}
 	}
 	g_users[device] += 1;
+	Convex::DeviceGenome::Retain(device);      /* DeviceWindows' genome on the logical device: one per device, shared by its lanes and the searcher */
 	if (g_firstCtorEnd < 0.0) g_firstCtorEnd = since_load();
 	g_st[device].ctorNs += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - c0).count();
 }
 
 StrippedSWHip::~StrippedSWHip() {
 	std::lock_guard<std::mutex> g(g_tableMtx);
+	Convex::DeviceGenome::Release(device, g_handle[device][lane]);      /* (the device's last user frees it: in front of the handles below) */
 	if (--g_users[device] == 0) {
 		std::chrono::steady_clock::time_point const d0 = std::chrono::steady_clock::now();
 		for (int l = 0; l < kLanes; ++l) {
 			std::lock_guard<std::mutex> d(g_mtx[device][l]);
-			if (g_genome[device] && g_handle[device][l]) { cvx_genome_free(g_handle[device][l], g_genome[device]); g_genome[device] = 0; }
 			if (g_handle[device][l]) cvx_destroy(g_handle[device][l]);
 			g_handle[device][l] = 0;
 		}
@@ -92,10 +93,10 @@ int StrippedSWHip::BatchScore(int const mode, int const batchSize, char const * 
 
 void StrippedSWHip::CountStringPath(int const pairs) { g_st[device].winFailed += pairs; }
 
-/* Locks: the lane's mutex first, then -- for the device's first call only -- the table's, held while the genome is uploaded
- * (seconds for a genome of gigabytes: constructors and destructors of other scorers wait that long, once per device).  The
- * destructor takes them the other way round, table then lanes, but only when the device's last scorer goes, i.e. when no
- * thread can be inside a call on one of that device's lanes: the two orders never meet on the same device. */
+/* Locks: the lane's mutex first, then -- for the device's first call only -- the genome holder's (device_genome.cpp), held while
+ * the genome is uploaded (seconds for a genome of gigabytes: constructors and destructors of that device's other scorers wait
+ * that long, once per device).  The destructor takes the table's mutex, then the holder's, then the lanes', but the lanes' only
+ * when the device's last scorer goes, i.e. when no thread can be inside a call on one of that device's lanes. */
 int StrippedSWHip::BatchScoreWindows(int const nReads, unsigned char const * const arena, unsigned long long const * const offsets,
 		int const batchSize, cvx_score_window const * const pairs, float * const results, int * const status) {
 	std::chrono::steady_clock::time_point const t0 = std::chrono::steady_clock::now();
@@ -103,20 +104,7 @@ int StrippedSWHip::BatchScoreWindows(int const nReads, unsigned char const * con
 	DevStats & st = g_st[device];
 	st.calls += 1; st.pairs += batchSize; st.winCalls += 1; st.winPairs += batchSize;
 	struct Stop { std::chrono::steady_clock::time_point t; DevStats * s; ~Stop() { s->ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count(); } } stop{t0, &st};
-	if (__atomic_load_n(&g_genome[device], __ATOMIC_ACQUIRE) == 0) {      /* (read again under the table's lock: another lane of the device may be uploading it) */
-		std::lock_guard<std::mutex> g(g_tableMtx);
-		if (g_genome[device] == 0) {
-			void const * binRef = 0; unsigned long long nNibbles = 0; unsigned long long const * starts = 0; int nStarts = 0;
-			if (!Convex::DeviceWindows::Genome(binRef, nNibbles, starts, nStarts)) throw "StrippedSWHip::BatchScoreWindows: no genome (Convex::DeviceWindows::SetGenome)";
-			cvx_genome up = 0;
-			if (cvx_genome_upload(g_handle[device][lane], (uint8_t const *) binRef, nNibbles, (uint64_t const *) starts, nStarts, &up) != CVX_OK) {
-				fprintf(stderr, "StrippedSWHip: %s\n", cvx_last_error());
-				throw 1;
-			}
-			__atomic_store_n(&g_genome[device], up, __ATOMIC_RELEASE);
-		}
-	}
-	cvx_genome const genome = __atomic_load_n(&g_genome[device], __ATOMIC_ACQUIRE);
+	cvx_genome const genome = Convex::DeviceGenome::Get(device, g_handle[device][lane]);
 	if (cvx_score_windows(g_handle[device][lane], genome, nReads, arena, (uint64_t const *) offsets, batchSize, pairs, results, status) != CVX_OK) {
 		fprintf(stderr, "StrippedSWHip: %s\n", cvx_last_error());
 		throw 1;

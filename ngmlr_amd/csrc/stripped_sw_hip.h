@@ -35,7 +35,8 @@ public:
 	/* Not part of IAlignment (the vtable stays as it is): BatchScore for pairs given as (window of the genome, read, strand) --
 	 * cvx_score_windows on this worker's lane, the strings of ScoreBuffer::DoRun's preparation loop written on the device
 	 * (reference src/ScoreBuffer.cpp:94-121).  The genome is the one Convex::DeviceWindows::SetGenome announced, uploaded once per
-	 * logical device by the first call there, shared by the device's lanes and freed with its last scorer.  reads as in
+	 * logical device by the first call there, shared by the device's lanes and the searcher (device_genome.h) and freed with the
+	 * device's last user.  reads as in
 	 * cvx_search_batch_arena.  results[i] = -1 and status[i] = 1 (status may be 0) where DecodeRefSequence would return false: the
 	 * caller scores those through the strings.  Returns batchSize; throws without a genome. */
 	int BatchScoreWindows(int const nReads, unsigned char const * const arena, unsigned long long const * const offsets,

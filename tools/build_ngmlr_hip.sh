@@ -37,6 +37,9 @@ mkdir -p "$REPO/oracle/_ref"
 #   ngmlr_hip_scorewin ngmlr_hip_all + the scoring calls of ScoreBuffer::DoRun and scoreShortRead as windows of the resident genome
 #                      (score_windows_binding.inc: StrippedSWHip::BatchScoreWindows, no computeReverseSeq / DecodeRefSequence on the CS
 #                      thread); CVX_SCORE_WINDOWS=0 keeps the string path inside the same binary (tests/test_gpu_e2e_scorewin.py)
+#   ngmlr_hip_feed     ngmlr_hip_scorewin + a CS batch of sub-reads searched AND scored in one device call (cs_feed_binding.inc inside
+#                      cs_search_binding.inc: CandidateSearchHip::SearchAndScore, ScoreBuffer::addScoredRead over the reference's own
+#                      completion block); CVX_CS_FEED=0 keeps the two calls inside the same binary (tests/test_gpu_e2e_feed.py)
 #   ngmlr_index_cpu    the reference's CPU code with only that table builder bound: the table file it writes against the unmodified
 #                      binary's, without a GPU (tests/test_index_cpu.py)
 #   ngmlr_pool_cpu     the reference's CPU aligners + the same pool: the pool's own correctness without a GPU (tests/test_pool_cpu.py)
@@ -44,14 +47,15 @@ mkdir -p "$REPO/oracle/_ref"
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 SCOREWIN = sys.argv[10]
+FEED = sys.argv[11]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -186,6 +190,36 @@ if SCOREWIN:
              '\tbool cvxWindows = false;\n#define CVX_SCORE_WINDOWS_SITE 2\n#include "score_windows_binding.inc"\n#undef CVX_SCORE_WINDOWS_SITE\n'
              '\tfor (int i = 0; i < (cvxWindows ? 0 : read->numScores()); ++i) {\n\t\tint corridor = read->length * 0.3 + 256;\n', 'ScoreBuffer::scoreShortRead loop')
     open(p, 'w').write(s)
+if FEED:
+    # a CS batch searched and scored in one device call (ngmlr_amd/csrc/cs_feed_binding.inc, included by cs_search_binding.inc once
+    # cs_feed_binding.h has defined CVX_CS_FEED_BINDING): ScoreBuffer's completion block becomes a method, addScoredRead calls it
+    assert SEARCH and SCOREWIN
+    p = T + '/src/CS.cpp'
+    s = open(p).read()
+    s = sub1(s, '#include "cs_search_binding.h"', '#include "cs_search_binding.h"\n#include "cs_feed_binding.h"', 'CS include (feed)')
+    open(p, 'w').write(s)
+    p = T + '/src/ScoreBuffer.h'
+    s = open(p).read()
+    s = sub1(s, '\tScoreBuffer(IAlignment * mAligner, AlignmentBuffer * mOut) :',
+             '\t/* cvx (cs_feed_binding.inc): a read whose candidates were scored with its search -- the scores, then the completion block of DoRun */\n'
+             '\tvoid addScoredRead(MappedRead * read, float const * scores);\n\tvoid cvxCompleteRead(MappedRead * cur_read);\n'
+             '\tIAlignment * cvxAligner() const { return aligner; }\n\tuloc cvxRefMaxLen() const { return refMaxLen; }\n\tint cvxCorridor() const { return corridor; }\n\n'
+             '\tScoreBuffer(IAlignment * mAligner, AlignmentBuffer * mOut) :', 'ScoreBuffer.h (feed)')
+    open(p, 'w').write(s)
+    p = T + '/src/ScoreBuffer.cpp'
+    s = open(p).read()
+    head = '\t\t\tif (++cur_read->Calculated == cur_read->numScores()) {\n'
+    tail = '\n\t\t\t}\n\t\t}\n\t\tscoreTime += tmr.ET();'
+    assert s.count(head) == 1 and s.count(tail) == 1
+    a, b = s.index(head) + len(head), s.index(tail)
+    body = s[a:b]      # the reference's own text: topNSE, updateGroupInfo, processLongReadLIS / processShortRead (or what the pool put there)
+    assert 'topNSE(cur_read);' in body and 'updateGroupInfo(cur_read)' in body
+    s = s[:a] + '\t\t\t\tcvxCompleteRead(cur_read);' + s[b:]
+    s = sub1(s, 'void ScoreBuffer::topNSE(MappedRead* read) {', 'void ScoreBuffer::cvxCompleteRead(MappedRead * cur_read) {\n' + body + '\n}\n\n'
+             'void ScoreBuffer::addScoredRead(MappedRead * read, float const * scores) {\n\tint const n = read->numScores();\n'
+             '\tfor (int k = 0; k < n; ++k) read->Scores[k].Score.f = scores[k];\n\tread->Calculated = n;\n\tcvxCompleteRead(read);\n}\n\n'
+             'void ScoreBuffer::topNSE(MappedRead* read) {', 'ScoreBuffer.cpp (feed)')
+    open(p, 'w').write(s)
 if SAM:
     p = T + '/src/SAMWriter.cpp'
     s = open(p).read()
@@ -220,7 +254,7 @@ if CLASS != 'cpu':
     open(p, 'w').write(s)
 p = T + '/src/CMakeLists.txt'
 c = open(p).read()
-c = c.replace('add_executable(ngmlr', ('add_definitions(-DCVX_IN_NGMLR_TREE)\ninclude_directories(${CMAKE_CURRENT_SOURCE_DIR} %s/include %s/ngmlr_amd/csrc REPO_TESTS_CPP)\nadd_executable(ngmlr\n%s/ngmlr_amd/csrc/convex_align_hip.cpp\n%s/ngmlr_amd/csrc/batching_aligner.cpp\n%s/ngmlr_amd/csrc/stripped_sw_hip.cpp\n%s/ngmlr_amd/csrc/candidate_search_hip.cpp\n%s/ngmlr_amd/csrc/cvx_fiber.cpp%s' % (REPO, REPO, REPO, REPO, REPO, REPO, REPO, ('\n%s/ngmlr_amd/csrc/align_pool.cpp' % REPO) if POOL else '') + (('\n%s/ngmlr_amd/csrc/batching_scorer.cpp' % REPO) if CHECKS else '')).replace('REPO_TESTS_CPP', REPO + '/tests/cpp'), 1)
+c = c.replace('add_executable(ngmlr', ('add_definitions(-DCVX_IN_NGMLR_TREE)\ninclude_directories(${CMAKE_CURRENT_SOURCE_DIR} %s/include %s/ngmlr_amd/csrc REPO_TESTS_CPP)\nadd_executable(ngmlr\n%s/ngmlr_amd/csrc/convex_align_hip.cpp\n%s/ngmlr_amd/csrc/batching_aligner.cpp\n%s/ngmlr_amd/csrc/stripped_sw_hip.cpp\n%s/ngmlr_amd/csrc/candidate_search_hip.cpp\n%s/ngmlr_amd/csrc/device_genome.cpp\n%s/ngmlr_amd/csrc/cvx_fiber.cpp%s' % (REPO, REPO, REPO, REPO, REPO, REPO, REPO, REPO, ('\n%s/ngmlr_amd/csrc/align_pool.cpp' % REPO) if POOL else '') + (('\n%s/ngmlr_amd/csrc/batching_scorer.cpp' % REPO) if CHECKS else '')).replace('REPO_TESTS_CPP', REPO + '/tests/cpp'), 1)
 c = c.replace('TARGET_LINK_LIBRARIES(ngmlr ${ZLIB_LIBRARIES})', 'TARGET_LINK_LIBRARIES(ngmlr ${ZLIB_LIBRARIES})\nTARGET_LINK_LIBRARIES(ngmlr %s/ngmlr_amd/libcvxalign.so)\nset_target_properties(ngmlr PROPERTIES BUILD_RPATH "\\$ORIGIN/../../ngmlr_amd;/opt/rocm/lib" SKIP_BUILD_RPATH FALSE)' % REPO, 1)
 open(p, 'w').write(c)
 PY
@@ -245,10 +279,11 @@ bv ngmlr_pool_parked Convex::ParkingCpuAligner "" "" pool      # CPU aligner beh
 bv ngmlr_hip_all Convex::SharedAligner StrippedSWHip sam pool search index
 bv ngmlr_hip_checks Convex::SharedAligner StrippedSWHip sam pool search index checks
 bv ngmlr_hip_scorewin Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin
+bv ngmlr_hip_feed Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin feed
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
