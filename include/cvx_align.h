@@ -43,6 +43,9 @@
  *                             src/SequenceProvider.cpp:333-386,475-565 (next-row f4, decode half)
  * cvx_job_window_refs         the windows cvx_submit_windows decoded, back on the host for a text stage there
  *                             (replaces extractReferenceSequenceForAlignment's decode, src/AlignmentBuffer.cpp:199-223)
+ * cvx_submit_segments / cvx_stage_segments(_host)  AlignmentBuffer::extractReadSeq  src/AlignmentBuffer.cpp:1515-1549
+ *                             (computeReverseSeq :1130-1141, cplBase :1117-1128): the query of an alignment tile as a segment
+ *                             of the call's read block, written on the device
  * cvx_job_text_all / cvx_job_nm_profile_resident  cvx_job_text + cvx_job_nm_profile per finished launch, profile in page-locked memory
  * cvx_index_upload / cvx_search_batch  CS::RunRead's k-mer vote over the CompactPrefixTable
  *                             src/CS.cpp:57-149,219-268,324-398, src/CSstatic.cpp:23-73, src/PrefixTable.cpp:476-532 (f4, search half)
@@ -392,6 +395,45 @@ int cvx_submit_windows(cvx_handle h, cvx_genome g, int32_t n_tiles, const cvx_ti
  * reads the reference bases of mismatches and deletions there and never decodes a window itself. */
 int cvx_job_window_refs(cvx_handle h, cvx_job job, const char **refs);
 
+/* Alignment queries as segments of a read block, built on the device (additive to ABI 9).
+ *
+ * ngmlr builds the query of every SingleAlign on a worker core in AlignmentBuffer::extractReadSeq (reference
+ * src/AlignmentBuffer.cpp:1515-1549): a strncpy of the segment for a forward read, a byte-at-a-time reverse complement for a
+ * reverse one (computeReverseSeq, :1130-1141, over cplBase, :1117-1128), the complement taken a second time with revComp
+ * (:1534-1538).  Here a tile names its query as (read of the call's read block, start, flags), its length being
+ * tiles[i].qry_len; the call's distinct reads go up once, as they lie in MappedRead::Seq, and stage_segments_kernel writes
+ * every tile's query straight into the job's sequence arena:
+ *   flags & CVX_SEG_REVCOMP clear:  query[k] = read[start + k]
+ *   set:                            query[k] = cpl(read[start + qry_len - 1 - k]), cpl swapping A<->T and C<->G and leaving
+ *                                   every other byte (lower case, N, anything) as it is
+ *   extractReadSeq(len, start, isReverse, read, revComp)  ->  flags = (isReverse != revComp): cpl and the reversal are
+ *                                   involutions, the double complement is the forward copy.
+ * The read block has the form of cvx_search_batch_arena and cvx_score_windows: read r is arena[offsets[r] .. offsets[r+1] - 1),
+ * its NUL at offsets[r+1] - 1.
+ *
+ *   cvx_submit_segments     cvx_submit (g NULL: references from tiles[i].ref) or cvx_submit_windows (g given, ref_position
+ *                           as there; cvx_job_window_refs works) with tiles[i].qry ignored -- it may be NULL -- and the query
+ *                           of tile i taken from qry[i].  The arena is copied (or, in memory from cvx_host_alloc, pulled by
+ *                           the device) inside the call and never modified; pulled memory stays unchanged until cvx_wait, as
+ *                           for cvx_submit.  CVX_ERR_ARG: a read index outside [0, n_reads), start < 0, start + qry_len beyond
+ *                           the read, an unknown flag bit, offsets that do not ascend.  Everything behind the upload (plan,
+ *                           fill, walk, records, text) is cvx_submit's.
+ *   cvx_stage_segments      the strings the device builds, back on the host (tests, diagnosis): n strings of len[i] bytes,
+ *                           back to back in out (no NUL between them), qry_off[i] = the first byte of string i, *used = their
+ *                           sum.  CVX_ERR_CAPACITY when cap is smaller (*used and qry_off are set).
+ *   cvx_stage_segments_host the same strings built on the host the way extractReadSeq builds them; no device. */
+enum { CVX_SEG_REVCOMP = 1 };
+typedef struct { int32_t read; int32_t start; int32_t flags; int32_t reserved; } cvx_read_segment;      /* length = tiles[i].qry_len */
+int cvx_submit_segments(cvx_handle h, cvx_genome g, int32_t n_tiles, const cvx_tile *tiles, const uint64_t *ref_position,
+		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, const cvx_read_segment *qry, cvx_job *out);
+int cvx_stage_segments(cvx_handle h, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
+		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used);
+/* bytes of the job's upload that travelled straight from the caller's page-locked memory (cvx_host_alloc), without a staging copy:
+ * blocks of queries / references that lie back to back there, the read block of cvx_submit_segments.  After the submit call. */
+int cvx_job_zero_copy_bytes(cvx_job job, uint64_t *bytes);
+int cvx_stage_segments_host(int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
+		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used);
+
 /* Candidate search (search half): the k-mer vote of CS::RunRead (src/CS.cpp:324-398: PrefixIteration
  * src/CSstatic.cpp:23-73, PrefixSearch / AddLocationStd src/CS.cpp:57-149, CollectResultsStd :219-268) for a batch of
  * (sub-)reads over the reference's k-mer table resident in HBM.
@@ -493,7 +535,8 @@ int cvx_score_kernel_ms(cvx_handle h, float *ms);
 enum { CVX_STAGE_SCORE = 0, CVX_STAGE_DECODE = 1, CVX_STAGE_SEARCH = 2,
 	CVX_STAGE_SCORE_WINDOWS = 3 /* stage_score_windows_kernel alone, of the last cvx_score_windows* call waited for (its time is part of CVX_STAGE_SCORE too) */,
 	CVX_STAGE_SEARCH_SCORE = 4 /* the plan + stage + score kernels of the handle's last cvx_search_score_arena (0 when it had no candidate); its search
-	                            * kernels are reported by CVX_STAGE_SEARCH as for any search */ };
+	                            * kernels are reported by CVX_STAGE_SEARCH as for any search */,
+	CVX_STAGE_SEGMENTS = 5 /* stage_segments_kernel of the handle's last cvx_stage_segments */ };
 int cvx_stage_kernel_ms(cvx_handle h, int32_t stage, float *ms);
 
 /* Asynchronous sub-read scoring (ABI 9, additive): the scores cvx_score_batch returns, for callers that must not block

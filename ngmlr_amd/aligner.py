@@ -138,6 +138,30 @@ class ConvexAlignHip:
         capi.check(self.lib.cvx_submit(self.h, n, arr, C.byref(j)))
         return Job(self, j, n, keep)
 
+    def submit_segments(self, tiles: Sequence, reads, segments, genome: "Genome" = None, ref_positions=None) -> "Job":
+        """cvx_submit_segments: cvx_submit (or, with `genome` and `ref_positions`, cvx_submit_windows) with every tile's query
+        named as a segment of a read block and written on the device.  tiles: Tile objects; of tile.qry only the length is
+        used (the table handed to the library carries NULL query pointers).  reads: a sequence of bytes, or (arena, offsets) as
+        KmerIndex.make_arena returns them.  segments: (read, start, flags) per tile, or a SEGMENT_DTYPE array."""
+        arr, keep = self._pack(tiles)
+        for i in range(len(tiles)):
+            arr[i].qry = None
+        arena, offsets, n_reads = _window_reads(reads)
+        seg = _segments(segments)
+        assert len(seg) == len(tiles), "one segment per tile"
+        pos = np.ascontiguousarray(ref_positions, dtype=np.uint64) if genome is not None else None
+        j = C.c_void_p()
+        capi.check(self.lib.cvx_submit_segments(self.h, genome.g if genome is not None else None, len(tiles), arr,
+                                                pos.ctypes.data if pos is not None else None, n_reads, arena.ctypes.data, offsets.ctypes.data,
+                                                seg.ctypes.data, C.byref(j)))
+        return Job(self, j, len(tiles), (keep, arena, offsets, seg, pos))
+
+    def stage_segments(self, reads, segments, lengths) -> List[bytes]:
+        """cvx_stage_segments: the strings stage_segments_kernel builds for (read, start, flags) + length, back on the host."""
+        arena, offsets, n_reads = _window_reads(reads)
+        seg = _segments(segments)
+        return _stage_segments(lambda *io: self.lib.cvx_stage_segments(self.h, n_reads, arena.ctypes.data, offsets.ctypes.data, len(seg), seg.ctypes.data, *io), lengths)
+
     def nm_regions_ops(self, results, ops_arena, want_regions: bool = True):
         """cvx_nm_regions_ops: the low-identity regions of op lists the caller holds (a capi.CvxResult array or sequence, and
         the uint32 ops arena its ops_begin / n_ops point into), found on the device.
@@ -213,6 +237,12 @@ class Job:
                         .view(RESULT_DTYPE) if self.n else np.zeros(0, RESULT_DTYPE))
         self.ops = (np.ctypeslib.as_array(ops, shape=(int(n_ops.value),)) if n_ops.value else np.zeros(0, np.uint32))
         return self.results, self.ops
+
+    def zero_copy_bytes(self) -> int:
+        """cvx_job_zero_copy_bytes: bytes of this job's upload the device pulled straight out of the caller's page-locked memory"""
+        n = C.c_uint64()
+        capi.check(self.al.lib.cvx_job_zero_copy_bytes(self.j, C.byref(n)))
+        return int(n.value)
 
     def timing(self) -> capi.CvxTiming:
         t = capi.CvxTiming()
@@ -685,6 +715,38 @@ def stage_windows_host(lib, binref, nibbles, starts, reads, pairs):
     st = np.ascontiguousarray(starts, dtype=np.uint64)
     return _stage_windows(lambda *out: lib.cvx_stage_windows_host(b.ctypes.data, int(nibbles), st.ctypes.data, len(st), n_reads, arena.ctypes.data,
                                                                   offsets.ctypes.data, len(tab), tab.ctypes.data, *out), tab, offsets)
+
+
+SEGMENT_DTYPE = np.dtype([("read", np.int32), ("start", np.int32), ("flags", np.int32), ("reserved", np.int32)])
+assert SEGMENT_DTYPE.itemsize == C.sizeof(capi.CvxReadSegment)
+
+
+def _segments(segments) -> np.ndarray:
+    if isinstance(segments, np.ndarray) and segments.dtype == SEGMENT_DTYPE:
+        return np.ascontiguousarray(segments)
+    tab = np.zeros(len(segments), dtype=SEGMENT_DTYPE)
+    for i, (read, start, flags) in enumerate(segments):
+        tab[i] = (read, start, flags, 0)
+    return tab
+
+
+def _stage_segments(call, lengths) -> List[bytes]:
+    ln = np.ascontiguousarray(lengths, dtype=np.int32)
+    n = len(ln)
+    qry_off = np.zeros(max(n, 1), dtype=np.uint64)
+    used = C.c_uint64()
+    cap = int(ln.astype(np.int64).clip(0).sum())
+    out = np.zeros(cap + 64, dtype=np.uint8)
+    capi.check(call(ln.ctypes.data, out.ctypes.data, cap, qry_off.ctypes.data, C.byref(used)))
+    assert int(used.value) == cap
+    return [out[int(qry_off[i]):int(qry_off[i]) + int(ln[i])].tobytes() for i in range(n)]
+
+
+def stage_segments_host(lib, reads, segments, lengths) -> List[bytes]:
+    """cvx_stage_segments_host: the same strings built on the host the way extractReadSeq builds them (no device)."""
+    arena, offsets, n_reads = _window_reads(reads)
+    seg = _segments(segments)
+    return _stage_segments(lambda *io: lib.cvx_stage_segments_host(n_reads, arena.ctypes.data, offsets.ctypes.data, len(seg), seg.ctypes.data, *io), lengths)
 
 
 def genome_concat_len(lib, nibbles, starts) -> int:

@@ -16,7 +16,8 @@ CVX_OK = 0
 CREATE_SERVICE, CREATE_SCALAR_TWIN = 1, 2      # cvx_create_ex flags
 FORMAT_SCALAR_TWIN = 1                         # cvx_format_alignment_ex / cvx_format_batch_ex flags
 NOT_WRITTEN = -1                               # cigar_op_count / sv_type of the scalar twin's text stage
-STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS, STAGE_SEARCH_SCORE = 0, 1, 2, 3, 4      # cvx_stage_kernel_ms
+STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS, STAGE_SEARCH_SCORE, STAGE_SEGMENTS = 0, 1, 2, 3, 4, 5      # cvx_stage_kernel_ms
+SEG_REVCOMP = 1                                # cvx_read_segment.flags
 ERR_NAMES = {0: "CVX_OK", -1: "CVX_ERR_NO_DEVICE", -2: "CVX_ERR_PARAMS", -3: "CVX_ERR_ARG",
              -4: "CVX_ERR_OOM", -5: "CVX_ERR_HIP", -6: "CVX_ERR_CAPACITY"}
 TILE_STATUS = {0: "ok", 1: "invalid-row0", 2: "invalid-edge", 3: "invalid-length", 4: "too-large",
@@ -36,7 +37,7 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_corridor_fit", "cvx_corridor_fit_batch", "cvx_create_ex", "cvx_runtime_regime", "cvx_search_batch_arena",
            "cvx_score_submit", "cvx_score_poll", "cvx_score_wait", "cvx_format_alignment_ex", "cvx_format_batch_ex",
            "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len",
-           "cvx_search_score_arena")
+           "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes")
 
 
 class CvxParams(C.Structure):
@@ -132,6 +133,13 @@ class CvxScoreWindow(C.Structure):
 
 
 assert C.sizeof(CvxScoreWindow) == 24
+
+
+class CvxReadSegment(C.Structure):
+    _fields_ = [("read", C.c_int32), ("start", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(CvxReadSegment) == 16
 
 
 class CvxError(RuntimeError):
@@ -250,6 +258,13 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_score_windows.argtypes = [C.c_void_p, C.c_void_p] + win_in + [C.c_void_p, C.c_void_p]
     lib.cvx_stage_windows.argtypes = [C.c_void_p, C.c_void_p] + win_in + win_out
     lib.cvx_stage_windows_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32] + win_in + win_out
+    # (n_reads, arena, offsets, n, segments, lengths) in, (out, cap, qry_off, used) out
+    seg_io = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.cvx_stage_segments.argtypes = [C.c_void_p] + seg_io
+    lib.cvx_stage_segments_host.argtypes = seg_io
+    lib.cvx_submit_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CvxTile), C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.cvx_job_zero_copy_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.cvx_genome_concat_len.argtypes = [C.c_uint64, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
     lib.cvx_format_alignment.argtypes = [C.POINTER(CvxResult), C.c_void_p, C.c_char_p, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32,

@@ -491,6 +491,11 @@ SharedAligner::~SharedAligner() {
 			ConvexAlignHip::WindowStats(wl, wt, ml);
 			if (wl + ml > 0) fprintf(stderr, "SharedAligner: %ld tiles in %ld launches took their reference as windows of the genome in HBM (cvx_submit_windows; CVX_DEVICE_DECODE=0 turns that off), %ld mixed launches materialised theirs\n", wt, wl, ml);
 		}
+		{
+			long rl = 0, rt = 0, rm = 0;
+			ConvexAlignHip::ReadStats(rl, rt, rm);
+			if (rl + rm > 0) fprintf(stderr, "SharedAligner: %ld tiles in %ld launches took their query as a segment of the launch's read block (cvx_submit_segments; CVX_DEVICE_READS=0 turns that off), %ld mixed launches materialised theirs\n", rt, rl, rm);
+		}
 		if (g_lastTextLaunches > 0) fprintf(stderr, "SharedAligner: text stage on the device for %ld launches (cvx_job_text + cvx_job_nm_profile), %.3f s of the dispatchers' time\n", g_lastTextLaunches, g_lastTextSeconds);
 		fprintf(stderr, "SharedAligner: library loaded at 0, first worker joined at %.2f s, last one left at %.2f s\n",
 				std::chrono::duration<double>(g_firstJoin - g_loaded).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - g_loaded).count());

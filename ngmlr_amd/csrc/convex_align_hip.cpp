@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <unordered_map>
 
 #ifdef CVX_IN_NGMLR_TREE
 #include "IConfig.h"       /* Config.getMaxMatrixSizeMB(), as ConvexAlignFast's ctor reads it (src/ConvexAlignFast.cpp:49) */
@@ -77,6 +78,82 @@ bool DeviceWindows::Lookup(char const * buf, unsigned long long & position, int 
 	position = tl_window.position;
 	length = (int) tl_window.length;
 	return true;
+}
+
+/* ------------------------------------------------------------------ DeviceReads */
+namespace {
+/* what lies behind a placeholder's NUL: the note itself.  The buffer describes itself -- no table, no calling context, nothing
+ * that outlives the buffer or can be overwritten by a later note. */
+struct ReadNote {
+	uint64_t magic;
+	char const * self;      /* the buffer the note was written into: a byte copy of it elsewhere is not a note */
+	char const * seq;
+	int32_t readLen, start, len, flags;
+};
+uint64_t const kReadNoteMagic = 0x43565852534547A5ull;
+/* placeholder character k: bit 7 set (no read character has it), never NUL, different from its neighbours */
+inline char noteChar(int k) { return (char) (0x80 | ((k * 37 + 11) & 0x7F)); }
+std::atomic<long> g_notedLaunches(0), g_notedTiles(0), g_mixedReadLaunches(0);
+bool const g_deviceReads = [] { const char * e = getenv("CVX_DEVICE_READS"); return !(e && atoi(e) == 0); }();
+/* the bytes [off, off + n) of a note's string, the way extractReadSeq builds them (cvx_stage_segments_host) */
+bool readString(char const * seq, int readLen, int start, int len, int flags, int off, int n, char * out) {
+	uint64_t const offsets[2] = { 0, (uint64_t) readLen + 1 };      /* (Seq carries its NUL) */
+	/* a piece of a forward string is a later piece of the read, a piece of a reverse-complemented one an earlier piece */
+	cvx_read_segment const s = { 0, (flags & CVX_SEG_REVCOMP) ? start + len - off - n : start + off, flags, 0 };
+	int32_t const l = n;
+	uint64_t at = 0, used = 0;
+	return cvx_stage_segments_host(1, (uint8_t const *) seq, offsets, 1, &s, &l, (uint8_t *) out, (uint64_t) n, &at, &used) == CVX_OK;
+}
+bool readNote(char const * buf, ReadNote & note) {
+	if (buf == 0) return false;
+	int k = 0;
+	while (buf[k] != '\0') { if (buf[k] != noteChar(k)) return false; ++k; }      /* a string of anything else ends the walk at its first character */
+	if (k == 0) return false;
+	memcpy(&note, buf + k + 1, sizeof(note));
+	return note.magic == kReadNoteMagic && note.self == buf && note.len == k;
+}
+}
+
+bool DeviceReads::Enabled() { return g_deviceReads; }
+int DeviceReads::BufferBytes(int length) { return length + 1 + (int) sizeof(ReadNote); }
+
+void DeviceReads::Placeholder(char * buf, char const * readSeq, int readLength, int start, int length, int flags) {
+	for (int k = 0; k < length; ++k) buf[k] = noteChar(k);
+	buf[length] = '\0';
+	ReadNote note;
+	memset(&note, 0, sizeof(note));
+	note.magic = kReadNoteMagic; note.self = buf; note.seq = readSeq;
+	note.readLen = readLength; note.start = start; note.len = length; note.flags = flags;
+	memcpy(buf + length + 1, &note, sizeof(note));
+}
+
+bool DeviceReads::Lookup(char const * buf, char const * & readSeq, int & readLength, int & start, int & length, int & flags) {
+	ReadNote note;
+	if (!readNote(buf, note)) return false;
+	readSeq = note.seq; readLength = note.readLen; start = note.start; length = note.len; flags = note.flags;
+	return true;
+}
+
+bool DeviceReads::Materialise(char * buf) {
+	ReadNote note;
+	if (!readNote(buf, note)) return false;
+	if (!readString(note.seq, note.readLen, note.start, note.len, note.flags, 0, note.len, buf)) { fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error()); throw 1; }
+	return true;      /* the buffer holds characters now: Lookup no longer takes it for a placeholder */
+}
+
+void DeviceReads::CopyOut(char * dst, char const * src, int offset, int n) {
+	ReadNote note;
+	if (!readNote(src, note)) { strncpy(dst, src + offset, (size_t) n); return; }
+	if (offset < 0 || n < 0 || offset + n > note.len || !readString(note.seq, note.readLen, note.start, note.len, note.flags, offset, n, dst)) {
+		fprintf(stderr, "ConvexAlignHip: DeviceReads::CopyOut of [%d, %d) from a query of %d characters\n", offset, offset + n, note.len);
+		throw 1;
+	}
+}
+
+void ConvexAlignHip::ReadStats(long & notedLaunches, long & notedTiles, long & mixedLaunches) {
+	notedLaunches = g_notedLaunches.load();
+	notedTiles = g_notedTiles.load();
+	mixedLaunches = g_mixedReadLaunches.load();
 }
 
 void ConvexAlignHip::WindowStats(long & windowLaunches, long & windowTiles, long & mixedLaunches) {
@@ -163,7 +240,16 @@ void ConvexAlignHip::Prepare(Tile & t, bool const scalarTwin) {
 	} else {
 		t.refLen = (int) strlen(t.refSeq);
 	}
-	t.qryLen = (int) strlen(t.qrySeq);
+	t.segment = false;
+	t.readSeq = 0;
+	t.readLen = t.segStart = t.segFlags = 0;
+	int segLength = 0;
+	if (g_deviceReads && DeviceReads::Lookup(t.qrySeq, t.readSeq, t.readLen, t.segStart, segLength, t.segFlags)) {
+		t.segment = true;                       /* the binding's placeholder: the string extractReadSeq leaves has segLength characters */
+		t.qryLen = segLength;
+	} else {
+		t.qryLen = (int) strlen(t.qrySeq);
+	}
 	if (t.corridorHeight != t.qryLen) {
 		/* every reference caller passes corridorHeight == strlen(qry); anything else
 		 * indexes the corridor out of bounds in the reference itself */
@@ -214,10 +300,36 @@ cvx_job ConvexAlignHip::Submit(Tile const * tiles, int n) {
 		c.corridor_offset = t.corridorOffset; c.corridor_width = t.corridorWidth;
 		c.reserved = 0;
 	}
-	int nWindows = 0;
-	for (int i = 0; i < n; ++i) nWindows += tiles[i].window ? 1 : 0;
+	int nWindows = 0, nSegments = 0;
+	for (int i = 0; i < n; ++i) { nWindows += tiles[i].window ? 1 : 0; nSegments += tiles[i].segment ? 1 : 0; }
 	cvx_job job = 0;
 	int rc;
+	bool const noted = nSegments == n && n > 0;
+	if (noted) {
+		/* every query of the launch is a segment of a read: the launch's DISTINCT reads, as they lie in MappedRead::Seq, once
+		 * each -- the widening retries and the left / right / inverted tiles of one read share its bytes -- and 16 bytes per tile
+		 * (the reference: src/AlignmentBuffer.cpp:1515-1549 on the worker's core, then the string over PCIe once per tile) */
+		std::unordered_map<char const *, int32_t> index;
+		readArena.clear();
+		readOffsets.assign(1, 0);
+		segments.resize((size_t) n);
+		for (int i = 0; i < n; ++i) {
+			Tile const & t = tiles[i];
+			std::pair<std::unordered_map<char const *, int32_t>::iterator, bool> const at = index.insert(std::make_pair(t.readSeq, (int32_t) index.size()));
+			if (at.second) {
+				readArena.insert(readArena.end(), (uint8_t const *) t.readSeq, (uint8_t const *) t.readSeq + t.readLen);
+				readArena.push_back(0);
+				readOffsets.push_back(readArena.size());
+			}
+			cvx_read_segment & s = segments[(size_t) i];
+			s.read = at.first->second; s.start = t.segStart; s.flags = t.segFlags; s.reserved = 0;
+			packed[(size_t) i].qry = 0;
+		}
+		g_notedLaunches.fetch_add(1, std::memory_order_relaxed);
+		g_notedTiles.fetch_add(n, std::memory_order_relaxed);
+	} else if (nSegments > 0) {
+		materialiseReads(tiles, n);      /* a launch that mixes both forms */
+	}
 	if (nWindows > 0 && genome == 0) {
 		if (cvx_genome_upload(handle, (uint8_t const *) g_binRef, g_nNibbles, g_startTable.data(), (int32_t) g_startTable.size(), &genome) != CVX_OK) {
 			fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
@@ -229,12 +341,15 @@ cvx_job ConvexAlignHip::Submit(Tile const * tiles, int n) {
 		 * straight into the launch's sequence arena (the reference: src/AlignmentBuffer.cpp:199-223 on the worker's core) */
 		positions.resize((size_t) n);
 		for (int i = 0; i < n; ++i) { positions[(size_t) i] = tiles[i].refPosition; packed[(size_t) i].ref = 0; }
-		rc = cvx_submit_windows(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), &job);
+		if (noted) rc = cvx_submit_segments(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), (int32_t) readOffsets.size() - 1,
+				readArena.data(), readOffsets.data(), segments.data(), &job);
+		else rc = cvx_submit_windows(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), &job);
 		g_windowLaunches.fetch_add(1, std::memory_order_relaxed);
 		g_windowTiles.fetch_add(n, std::memory_order_relaxed);
 	} else {
 		if (nWindows > 0) materialiseWindows(tiles, n);      /* a launch that mixes both forms (no ngmlr path builds one) */
-		rc = cvx_submit(handle, n, packed.data(), &job);
+		if (noted) rc = cvx_submit_segments(handle, 0, n, packed.data(), 0, (int32_t) readOffsets.size() - 1, readArena.data(), readOffsets.data(), segments.data(), &job);
+		else rc = cvx_submit(handle, n, packed.data(), &job);
 	}
 	if (rc != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
@@ -264,6 +379,19 @@ void ConvexAlignHip::materialiseWindows(Tile const * tiles, int n) {
 	}
 	for (size_t k = 0; k < who.size(); ++k) memcpy(const_cast<char *>(tiles[who[k]].refSeq), out.data() + off[k], (size_t) len[k]);
 	g_mixedLaunches.fetch_add(1, std::memory_order_relaxed);
+}
+
+/* the noted queries among the tiles built on the host in their callers' placeholder buffers (which the binding allocated
+ * writable, length + 1 bytes), so that the launch can travel as characters */
+void ConvexAlignHip::materialiseReads(Tile const * tiles, int n) {
+	for (int i = 0; i < n; ++i) if (tiles[i].segment) {
+		Tile const & t = tiles[i];
+		if (!readString(t.readSeq, t.readLen, t.segStart, t.qryLen, t.segFlags, 0, t.qryLen, const_cast<char *>(t.qrySeq))) {
+			fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+			throw 1;
+		}
+	}
+	g_mixedReadLaunches.fetch_add(1, std::memory_order_relaxed);
 }
 
 bool ConvexAlignHip::Poll(cvx_job job) {

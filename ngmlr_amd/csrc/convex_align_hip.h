@@ -75,6 +75,12 @@ public:
 		 * below) -- the launch carries (position, length) and the device decodes; Finish needs WindowRefs() first */
 		bool window;
 		unsigned long long refPosition;
+		/* filled by Prepare(): qrySeq is a placeholder for a segment of a read (DeviceReads below) -- the launch carries
+		 * (read, start, flags) and the device writes the query; nothing on the host reads its characters afterwards (the text
+		 * stage takes no query) */
+		bool segment;
+		char const * readSeq;
+		int readLen, segStart, segFlags;
 	};
 	/* n independent corridor alignments in one device launch.  A hard error that belongs to one tile (a corridor no
 	 * kernel covers, a CIGAR that does not fit the caller's buffer) marks that tile `failed` and leaves the others
@@ -118,6 +124,9 @@ public:
 	/* launches that travelled as windows of the resident genome (cvx_submit_windows), and launches that mixed windows with
 	 * decoded references (their windows were materialised with cvx_genome_decode first) */
 	static void WindowStats(long & windowLaunches, long & windowTiles, long & mixedLaunches);
+	/* launches whose queries all travelled as segments of one read block (cvx_submit_segments), their tiles, and launches that
+	 * mixed noted and plain queries (their noted ones were materialised on the host first) */
+	static void ReadStats(long & notedLaunches, long & notedTiles, long & mixedLaunches);
 	/* tiles Prepare() has seen in this process, and how many of them travelled as a closed form */
 	static void CorridorStats(long & prepared, long & closedForm);
 	void FinishText(Tile & t, cvx_result const & r, JobText const & jt, int index) const;
@@ -133,6 +142,11 @@ private:
 	std::vector<unsigned long long> positions;
 	std::vector<char const *> refPtrs;
 	void materialiseWindows(Tile const * tiles, int n);
+	/* DeviceReads: the read block of a noted launch -- every distinct read once -- and one segment per tile */
+	std::vector<uint8_t> readArena;
+	std::vector<uint64_t> readOffsets;
+	std::vector<cvx_read_segment> segments;
+	void materialiseReads(Tile const * tiles, int n);
 };
 
 /*
@@ -160,6 +174,33 @@ struct DeviceWindows {
 	/* buf[0 .. length) stands for DecodeRefSequenceExact(buf, position, length, 0): length - 1 characters and a NUL */
 	static void Placeholder(char * buf, unsigned long long position, int length);
 	static bool Lookup(char const * buf, unsigned long long & position, int & length);
+};
+
+/*
+ * Alignment queries built on the device inside ngmlr's worker flow.
+ *
+ * ngmlr builds the query of every SingleAlign on the worker's core (AlignmentBuffer::extractReadSeq, reference
+ * src/AlignmentBuffer.cpp:1515-1549: a strncpy, or computeReverseSeq's byte-at-a-time reverse complement) and between that call
+ * and SingleAlign only measures the string (strlen in the corridor builders).  Unless CVX_DEVICE_READS=0, the binding
+ * (read_segments_binding.inc) allocates a buffer of BufferBytes(length) and fills it with a placeholder of the same length that
+ * DESCRIBES ITSELF: `length` characters no read holds (bit 7 set, a fixed sequence), the NUL, and behind the NUL the note --
+ * (this buffer, the read's Seq, its length, start, length, flags).  Nothing is kept per calling context: any number of noted
+ * buffers live side by side on a thread or fiber, a note ends with its buffer, and a plain string is never taken for a
+ * placeholder (its first character ends the check).  Prepare() recognises the buffer, and a launch whose tiles are all noted
+ * sends every distinct read once and goes through cvx_submit_segments.  flags = (isReverse != revComp), CVX_SEG_REVCOMP.
+ */
+struct DeviceReads {
+	static bool Enabled();                 /* unless CVX_DEVICE_READS=0 */
+	static int BufferBytes(int length);    /* what a buffer for a placeholder of `length` characters must hold */
+	/* buf (BufferBytes(length) bytes) stands for extractReadSeq's string: length placeholder characters, a NUL, the note.
+	 * readSeq (MappedRead::Seq, readLength bytes) must stay valid until the launch has been submitted. */
+	static void Placeholder(char * buf, char const * readSeq, int readLength, int start, int length, int flags);
+	static bool Lookup(char const * buf, char const * & readSeq, int & readLength, int & start, int & length, int & flags);
+	/* the placeholder in buf replaced by the string itself, built on the host.  false: buf holds no placeholder (nothing is written) */
+	static bool Materialise(char * buf);
+	/* strncpy(dst, src + offset, n) for a caller that reads characters of a query after all (checkForSV,
+	 * src/AlignmentBuffer.cpp:1202): from a placeholder, those n characters of the string it stands for, built on the host */
+	static void CopyOut(char * dst, char const * src, int offset, int n);
 };
 
 }  // namespace Convex

@@ -194,6 +194,7 @@ struct UploadLayout {
 	uint64_t delta_total = 0;       /* bytes of the row-step stream (H bytes, 4-byte aligned, per tile whose rows come as arrays) */
 	std::vector<RowSrc> rsrc;       /* per tile: where its rows come from (src_off = offset into the step stream until packed) */
 	bool windows = false;           /* references decoded on the device from the resident genome: their block is not uploaded */
+	bool segments = false;          /* queries written on the device from the call's read block (cvx_segments.h): their block is neither packed nor uploaded */
 	/* the caller's reads (references) lie back to back in tile order: the block can travel as it is, without
 	 * packing, when the runtime finds it in page-locked memory (cvx_host_alloc) */
 	bool qry_contig = false, ref_contig = false;
@@ -215,14 +216,14 @@ inline bool affine_form_ok(float k, float d, float right, int32_t H) {
 
 /* Validates the tiles and assigns arena offsets (TileIn).  On kLayoutMalformed *bad is the
  * offending tile; kLayoutTooLarge: more than 4 GiB of bases (32-bit sequence offsets). */
-inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin, UploadLayout &L, int *bad, bool windows = false) {
+inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin, UploadLayout &L, int *bad, bool windows = false, bool segments = false) {
 	uint64_t ref_bytes = 0, n_rows = 0, qry_bytes = 0;
 	int64_t max_hw = 0;
-	bool qc = n > 0, rc = n > 0 && !windows;
+	bool qc = n > 0 && !segments, rc = n > 0 && !windows;
 	for (int i = 0; i < n; ++i) {
 		const cvx_tile &t = tiles[i];
 		const bool rows_given = t.corridor_kind == CVX_CORRIDOR_ROWS;
-		if (t.ref_len < 0 || t.qry_len < 0 || (t.ref_len > 0 && !t.ref && !windows) || (t.qry_len > 0 && !t.qry) ||
+		if (t.ref_len < 0 || t.qry_len < 0 || (t.ref_len > 0 && !t.ref && !windows) || (t.qry_len > 0 && !t.qry && !segments) ||
 				(rows_given && t.qry_len > 0 && (!t.row_offset || !t.row_length)) ||
 				(rows_given && ((t.row_stride_bytes & 3) || t.row_stride_bytes < 4)) ||
 				t.corridor_kind < CVX_CORRIDOR_ROWS || t.corridor_kind > CVX_CORRIDOR_CONST ||
@@ -232,7 +233,7 @@ inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin,
 			return kLayoutMalformed;
 		}
 		if (i > 0) {
-			if (tiles[i - 1].qry + tiles[i - 1].qry_len != t.qry) qc = false;
+			if (!segments && tiles[i - 1].qry + tiles[i - 1].qry_len != t.qry) qc = false;
 			if (!windows && tiles[i - 1].ref + tiles[i - 1].ref_len != t.ref) rc = false;
 		}
 		ref_bytes += (uint64_t) t.ref_len;
@@ -248,6 +249,7 @@ inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin,
 	L.seq_total = L.ref_base + ref_bytes + L.pad + 64;
 	L.n_rows = n_rows;
 	L.windows = windows;
+	L.segments = segments;
 	L.qry_contig = qc;
 	L.ref_contig = rc;
 	if (L.seq_total >= 0xFFFF0000ull) return kLayoutTooLarge;
@@ -280,7 +282,7 @@ inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin,
 			dof += ((uint64_t) t.qry_len + 3) / 4 * 4;
 			row_work = 9ull * (uint64_t) t.qry_len;
 		}
-		L.wprefix[(size_t) i + 1] = L.wprefix[(size_t) i] + (windows ? 0 : (uint64_t) t.ref_len) + (uint64_t) t.qry_len + row_work + 64;
+		L.wprefix[(size_t) i + 1] = L.wprefix[(size_t) i] + (windows ? 0 : (uint64_t) t.ref_len) + (segments ? 0 : (uint64_t) t.qry_len) + row_work + 64;
 	}
 	L.delta_total = dof;
 	L.arena_rows = ro;
@@ -289,8 +291,10 @@ inline int upload_layout(int n, const cvx_tile *tiles, std::vector<TileIn> &tin,
 
 /* the kernels prefetch a little past either end of a tile: all three pads must be defined (host staging form) */
 inline void upload_zero_pads(const UploadLayout &L, uint8_t *hseq) {
-	memset(hseq, 0, (size_t) L.qry_base);
-	memset(hseq + (size_t) (L.qry_base + L.qry_bytes), 0, (size_t) (L.ref_base - L.qry_base - L.qry_bytes));
+	if (!L.segments) {      /* (segments: block A never leaves the staging; the device clears the two pads itself) */
+		memset(hseq, 0, (size_t) L.qry_base);
+		memset(hseq + (size_t) (L.qry_base + L.qry_bytes), 0, (size_t) (L.ref_base - L.qry_base - L.qry_bytes));
+	}
 	if (!L.windows) memset(hseq + (size_t) (L.ref_base + L.ref_bytes), 0, (size_t) (L.seq_total - L.ref_base - L.ref_bytes));
 }
 
@@ -442,10 +446,14 @@ inline void place_misfits(const std::vector<RowOverflow> &overflow, const std::v
  * check it: which blocks travel as they are, how the batch is cut into pieces, and one record per transfer in issue order.
  * The stage itself packs a piece, then issues that piece's records. */
 
-enum UploadDst { kToSeq = 0, kToDelta = 1 };            /* the sequence arena, the step-stream arena */
+enum UploadDst { kToSeq = 0, kToDelta = 1, kToReads = 2 };      /* the sequence arena, the step-stream arena, the job's read block (segments) */
 /* the job's sequence / step staging, the page-locked block of zeros, the caller's block of reads / of references;
- * kClearOnDevice: no source, the destination is cleared by the device itself */
-enum UploadSrc { kFromSeqStaging = 0, kFromDeltaStaging = 1, kFromZeros = 2, kFromQryBlock = 3, kFromRefBlock = 4, kClearOnDevice = 5 };
+ * kClearOnDevice: no source, the destination is cleared by the device itself; segments: the caller's read block as it
+ * lies in page-locked memory, or the job's staging of it (copied there piece by piece, each piece in front of its record) */
+enum UploadSrc { kFromSeqStaging = 0, kFromDeltaStaging = 1, kFromZeros = 2, kFromQryBlock = 3, kFromRefBlock = 4, kClearOnDevice = 5,
+	kFromReadBlock = 6, kFromReadStaging = 7 };
+/* a read block that goes through the staging travels in pieces of this many bytes: a piece's DMA runs under the host's copy of the next */
+static const uint64_t kReadPieceBytes = 4ull << 20;
 
 struct UploadCopy {
 	int dst = kToSeq, src = kFromSeqStaging;
@@ -467,21 +475,42 @@ struct UploadSchedule {
 	std::vector<UploadCopy> copies;        /* [0, n_leading): before any packing; then the pieces' ranges; [n_staged, size()): behind the whole upload */
 	size_t n_leading = 0, n_staged = 0;
 	std::vector<UploadPiece> pieces;
+	/* segments mode: the read block, a destination of its own, in issue order in front of everything else (kToReads; one
+	 * record from the caller's arena, or one per piece of the staging); the stage kernel runs behind copies[n_staged, size()) */
+	bool zc_reads = false;
+	int read_threads = 1;                  /* > 1: the staging's pieces are copied side by side on the pack threads, then issued; 1: piece by piece, each DMA under the copy of the next */
+	std::vector<UploadCopy> read_copies;
 };
 
 /* L, tin: of upload_layout, L.rsrc not yet packed (the step-stream cut-offs read src_off); qry_pinned / ref_pinned: the
  * caller's block of reads / references (qry_bytes + 4 / ref_bytes + 4 bytes from the first tile's pointer) lies inside one
  * page-locked block; threads_on_offer: pack threads the handle may use. */
 inline void build_upload_schedule(const UploadLayout &L, const std::vector<TileIn> &tin, int n, bool qry_pinned, bool ref_pinned,
-		int threads_on_offer, UploadSchedule &s, uint64_t thread_bytes = kPackThreadBytes) {
-	const bool windows = L.windows;
+		int threads_on_offer, UploadSchedule &s, uint64_t thread_bytes = kPackThreadBytes, uint64_t read_bytes = 0, bool reads_pinned = false) {
+	const bool windows = L.windows, segments = L.segments;
 	/* a block of sequences that already lies back to back in page-locked memory is not packed: the
 	 * device pulls it out of the caller's arena (the job's staging then holds only what the host wrote) */
-	s.zc_qry = n > 0 && L.qry_contig && L.qry_bytes > 0 && qry_pinned;
+	s.zc_qry = n > 0 && !segments && L.qry_contig && L.qry_bytes > 0 && qry_pinned;
 	s.zc_ref = n > 0 && !windows && L.ref_contig && L.ref_bytes > 0 && ref_pinned;
 	s.zero_copy_bytes = (s.zc_qry ? L.qry_bytes : 0) + (s.zc_ref ? L.ref_bytes : 0);
-	s.pack_seq = !(s.zc_qry && (s.zc_ref || windows));
+	s.pack_seq = !((s.zc_qry || segments) && (s.zc_ref || windows));      /* off when neither block travels from the staging */
 	s.copies.clear(); s.pieces.clear();
+	/* segments: the read block (read_bytes bytes, read_bytes + 4 of them inside one page-locked block when reads_pinned) as it
+	 * is, or through the job's staging; every record a whole number of dwords (the last piece rounds up into the staging's /
+	 * the block's slack), every boundary a multiple of 256 */
+	s.read_copies.clear();
+	s.zc_reads = segments && n > 0 && read_bytes > 0 && reads_pinned;
+	if (segments && n > 0 && read_bytes > 0) {
+		const uint64_t total = (read_bytes + 3) / 4 * 4;
+		if (s.zc_reads) {
+			s.read_copies.push_back(UploadCopy{kToReads, kFromReadBlock, 0, 0, total});
+			s.zero_copy_bytes += read_bytes;
+		} else {
+			for (uint64_t at = 0; at < total; at += kReadPieceBytes)
+				s.read_copies.push_back(UploadCopy{kToReads, kFromReadStaging, at, at, std::min<uint64_t>(kReadPieceBytes, total - at)});
+		}
+	}
+	s.read_threads = (!s.read_copies.empty() && !s.zc_reads && read_bytes >= thread_bytes) ? std::max(1, threads_on_offer) : 1;      /* (the rule of the packing: not worth a thread below ~8 MB) */
 	auto add = [&](int dst, int src, uint64_t dst_off, uint64_t src_off, uint64_t len) { s.copies.push_back(UploadCopy{dst, src, dst_off, src_off, len}); };
 	/* the three pads: uploaded with the packed blocks (upload_zero_pads wrote them into the staging), or copied from zeros
 	 * around the blocks that travel as they are (queued in front of those copies: a copy rounded up to whole dwords may
@@ -514,7 +543,7 @@ inline void build_upload_schedule(const UploadLayout &L, const std::vector<TileI
 	s.n_leading = s.copies.size();
 	/* what the host still moves per tile decides whether packing is worth threads and pieces */
 	s.pack_work = L.delta_total * 9ull;
-	if (!s.zc_qry) s.pack_work += L.qry_bytes;
+	if (!s.zc_qry && !segments) s.pack_work += L.qry_bytes;
 	if (!s.zc_ref && !windows) s.pack_work += L.ref_bytes;
 	s.threads = std::max(1, threads_on_offer);
 	if (s.pack_work < thread_bytes) s.threads = 1;      /* not worth a thread below ~8 MB */
@@ -537,7 +566,7 @@ inline void build_upload_schedule(const UploadLayout &L, const std::vector<TileI
 		 * over PCIe with compute units the fill needs.  The bytes below the rounded-down end are all
 		 * packed (tiles are laid out in order inside either block); the remainder travels with the next
 		 * piece, the last piece runs to the aligned end. */
-		if (!s.zc_qry) {
+		if (!s.zc_qry && !segments) {
 			const uint64_t a_end = (t1 == n) ? a_end_all : (uint64_t) tin[(size_t) t1].qry_off / 256 * 256;
 			if (a_end > a_done) add(kToSeq, kFromSeqStaging, a_done, a_done, a_end - a_done);
 			a_done = std::max(a_done, a_end);
@@ -564,6 +593,12 @@ inline void build_upload_schedule(const UploadLayout &L, const std::vector<TileI
 	s.n_staged = s.copies.size();
 	/* windows: the references are decoded on the device straight into the arena, and the pad behind them is cleared there */
 	if (windows && n) add(kToSeq, kClearOnDevice, L.ref_base + L.ref_bytes, 0, L.seq_total - L.ref_base - L.ref_bytes);
+	/* segments: the queries are written on the device straight into the arena, and the two pads upload_zero_pads would have
+	 * written around their block are cleared there */
+	if (segments && n) {
+		add(kToSeq, kClearOnDevice, 0, 0, L.qry_base);
+		add(kToSeq, kClearOnDevice, L.qry_base + L.qry_bytes, 0, L.ref_base - L.qry_base - L.qry_bytes);
+	}
 }
 
 /* Packs one piece of the schedule into the staging arenas on the schedule's pack threads (upload_pack per range);
@@ -578,7 +613,7 @@ inline void upload_pack_piece(const UploadSchedule &s, const UploadPiece &p, con
 	overflow.resize(first + (size_t) s.threads + 1);
 	std::atomic<int> slot(0);
 	parallel_ranges(p.t1 - p.t0, wp, s.threads, [&](int bg, int en) {
-		upload_pack(base + bg, base + en, tiles, tin, hseq, hdelta, L.rsrc, overflow[first + (size_t) slot.fetch_add(1)], !s.zc_qry, !s.zc_ref && !L.windows);
+		upload_pack(base + bg, base + en, tiles, tin, hseq, hdelta, L.rsrc, overflow[first + (size_t) slot.fetch_add(1)], !s.zc_qry && !L.segments, !s.zc_ref && !L.windows);
 	});
 }
 

@@ -230,6 +230,9 @@ struct cvx_batch_s {
 	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
 	bool have_refs = false;
 	DevBuf<WindowDesc> d_win;
+	PinBuf h_reads;                  /* the read block of cvx_submit_segments on its way up (a caller's block in page-locked memory travels as it is) */
+	PinBuf h_segs;                   /* SegDesc[n] and the SegChunk table behind them (cvx_segments.h) */
+	DevBuf<uint8_t> d_reads, d_segs;
 	PinBuf h_chain;                  /* ChainTask[] of all chain classes, ChainBlk[], tile lists */
 	DevBuf<uint8_t> d_chain;
 	DevBuf<BoundaryRec> d_bnd;
@@ -250,7 +253,7 @@ struct cvx_batch_s {
 	const BatchSummary *summary() const { return reinterpret_cast<const BatchSummary *>(h_res.as<uint8_t>() + (size_t) n * sizeof(ResultRec)); }
 
 	/* the buffers whose size follows the job's tile count or cells: the same buffer of every slot of a handle shares one mark */
-	static const int kSharedMarks = 32;
+	static const int kSharedMarks = 40;
 	void bind(size_t *marks) {
 		int k = 0;
 		PinBuf *pins[] = { &h_seq, &h_delta, &h_rsrc, &h_tin, &h_plan, &h_trun, &h_tout, &h_lists, &h_res, &h_ops, &h_chain };
@@ -262,7 +265,8 @@ struct cvx_batch_s {
 		/* the big buffers of the text stage (strings, profile triples: 125 kB per 10 kb alignment); written by the one thread that
 		 * runs a handle's text stages -- never the thread that submits, and these entries are nobody else's */
 		h_text.hwm = &marks[k++]; h_nm.hwm = &marks[k++]; d_text.hwm = &marks[k++]; d_nm.hwm = &marks[k++];
-		static_assert(11 + 17 + 4 <= kSharedMarks, "marks");
+		h_reads.hwm = &marks[k++]; h_segs.hwm = &marks[k++]; d_reads.hwm = &marks[k++]; d_segs.hwm = &marks[k++];
+		static_assert(11 + 17 + 4 + 4 <= kSharedMarks, "marks");
 	}
 	int make_events() {
 		if (!ev_in) HIP_TRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
@@ -282,6 +286,7 @@ struct cvx_batch_s {
 		d_counters.release(); d_dstoff.release(); d_dense.release(); d_res.release();
 		d_gscratch.release(); d_gscratch_off.release();
 		h_win.release(); d_win.release(); h_refs.release();
+		h_reads.release(); h_segs.release(); d_reads.release(); d_segs.release();
 		h_ext.release(); h_trec.release(); h_toff.release(); h_text.release();
 		d_ext.release(); d_trec.release(); d_tlen.release(); d_text.release();
 		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
@@ -361,6 +366,7 @@ struct cvx_context {
 	std::vector<cvx_batch_s *> pool;
 	std::vector<cvx_batch_s *> pending;      /* streaming jobs whose compute stage is not queued yet */
 	std::vector<cvx_batch_s *> live;         /* every streaming job the caller has not released yet (cvx_destroy frees what is left) */
+	float segments_kernel_ms = 0.0f;   /* stage_segments_kernel of the last cvx_stage_segments (cvx_stage_kernel_ms) */
 	float decode_kernel_ms = 0.0f;     /* decode_windows_kernel of the last cvx_genome_decode (cvx_stage_kernel_ms) */
 	bool score_no_diag = false;   /* test knob (env CVX_TUNE_SCORE_NO_DIAG): always the row-by-row kernels */
 	struct cvx_score_state *score = nullptr;   /* sub-read scoring (cvx_score_batch, cvx_score_submit): jobs kept for reuse once waited for */

@@ -30,9 +30,18 @@
 #include <string>
 #include <vector>
 
+#include "cvx_qry_stage.h"
 #include "cvx_rt.h"
 
 namespace {
+
+/* the queries of a job of cvx_submit_segments: the call's read block and one segment per tile (cvx_segments.h) */
+struct SegmentsIn {
+	int32_t n_reads;
+	const uint8_t *arena;
+	const uint64_t *offsets;
+	const cvx_read_segment *qry;
+};
 
 static const size_t kPoolBatches = 8;      /* (4 until the text stage of a finished job got its own thread: a launch in the fill, one uploading, two in the text stage and those the workers still copy from) */
 
@@ -90,13 +99,13 @@ int fail_job(cvx_batch_s *b, int rc) {
 
 /* ---- stage 1: pack into pinned staging and copy to the device, piece by piece (stream `io`) */
 int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tiles,
-		const cvx_genome_s *genome = nullptr, const uint64_t *ref_position = nullptr) {
+		const cvx_genome_s *genome = nullptr, const uint64_t *ref_position = nullptr, const SegmentsIn *segs = nullptr) {
 	RC_TRY(ensure_streams(h));
 	UploadLayout L;
 	std::vector<TileIn> tin;
 	int bad = -1;
-	const bool windows = genome != nullptr;
-	const int lrc = upload_layout(n, tiles, tin, L, &bad, windows);
+	const bool windows = genome != nullptr, segments = segs != nullptr;
+	const int lrc = upload_layout(n, tiles, tin, L, &bad, windows, segments);
 	if (lrc == kLayoutMalformed) { set_err("tile %d malformed", bad); return CVX_ERR_ARG; }
 	if (lrc == kLayoutTooLarge) {
 		set_err("%llu sequence bytes exceed one batch (4 GiB); split the batch", (unsigned long long) L.seq_total);
@@ -111,6 +120,18 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	b->seq_total = L.seq_total;
 	b->n_rows = L.n_rows;
 	memset(&b->timing, 0, sizeof(b->timing));
+	/* segments: every tile's query checked against the read block and cut into the stage kernel's chunks, before anything is queued */
+	SegPlan sp;
+	if (segments) {
+		int64_t sbad = 0;
+		if (segments_plan(segs->n_reads, segs->offsets, n, segs->qry, [&](int32_t i) { return tiles[i].qry_len; },
+				[&](int32_t i) { return (uint64_t) tin[(size_t) i].qry_off; }, sp, &sbad) != CVX_OK) {
+			if (sbad < 0) set_err("cvx_submit_segments: the offsets of read %lld do not ascend (or span 2 GB)", (long long) (-1 - sbad));
+			else set_err("cvx_submit_segments: tile %lld: read %d of %d, start %d, qry_len %d, flags %d", (long long) sbad, segs->qry[sbad].read,
+					segs->n_reads, segs->qry[sbad].start, tiles[sbad].qry_len, segs->qry[sbad].flags);
+			return CVX_ERR_ARG;
+		}
+	}
 	RC_TRY(b->make_events());
 	const size_t n1 = (size_t) std::max(n, 1);
 	const size_t rows1 = (size_t) std::max<uint64_t>(L.arena_rows, 1);      /* closed-form corridors own no rows (RowView, cvx_types.h) */
@@ -140,8 +161,10 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	 * runtime (does a block of the caller's lie in page-locked memory?) and the issuing */
 	const bool qry_pinned = L.qry_contig && in_pinned_block(tiles[0].qry, L.qry_bytes + 4);      /* (contiguous: n > 0) */
 	const bool ref_pinned = L.ref_contig && in_pinned_block(tiles[0].ref, L.ref_bytes + 4);
+	const uint8_t *read_block = segments && sp.read_bytes ? segs->arena + segs->offsets[0] : nullptr;
+	const bool reads_pinned = read_block && in_pinned_block(read_block, sp.read_bytes + 4);
 	UploadSchedule sch;
-	build_upload_schedule(L, tin, n, qry_pinned, ref_pinned, std::min(h->pack_threads, PackPool::get().size()), sch);
+	build_upload_schedule(L, tin, n, qry_pinned, ref_pinned, std::min(h->pack_threads, PackPool::get().size()), sch, kPackThreadBytes, sp.read_bytes, reads_pinned);
 	b->zero_copy_bytes = sch.zero_copy_bytes;
 	if (sch.pack_seq) RC_TRY(b->h_seq.ensure((size_t) L.seq_total + 256));
 	uint8_t *hseq = b->h_seq.as<uint8_t>();
@@ -152,7 +175,28 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 		if (b->zero_cap != b->h_zero.cap) { memset(b->h_zero.p, 0, b->h_zero.cap); b->zero_cap = b->h_zero.cap; }
 	}
 	hipStream_t st = h->s_io;
-	const void *const from[] = { hseq, hdelta, b->h_zero.p, n ? tiles[0].qry : nullptr, n ? tiles[0].ref : nullptr };      /* UploadSrc */
+	/* segments: the read block first -- as it lies in the caller's page-locked arena, or through the job's staging, each piece
+	 * copied there in front of its record (its DMA runs under the copy of the next, and under the packing below) */
+	if (!sch.read_copies.empty()) {
+		RC_TRY(b->d_reads.ensure((size_t) sp.read_bytes + 256));
+		if (!sch.zc_reads) RC_TRY(b->h_reads.ensure((size_t) sp.read_bytes + 256));
+		auto stage_piece = [&](const UploadCopy &c) {
+			uint8_t *hs = b->h_reads.as<uint8_t>() + c.src_off;
+			const uint64_t have = std::min<uint64_t>(c.len, sp.read_bytes - c.src_off);      /* (the last record is rounded up to whole dwords) */
+			memcpy(hs, read_block + c.src_off, (size_t) have);
+			memset(hs + have, 0, (size_t) (c.len - have));
+		};
+		if (sch.read_threads > 1) PackPool::get().run((int) sch.read_copies.size(), [&](int k) { stage_piece(sch.read_copies[(size_t) k]); });
+		for (const UploadCopy &c : sch.read_copies) {
+			const uint8_t *src = read_block + c.src_off;
+			if (c.src == kFromReadStaging) {
+				if (sch.read_threads <= 1) stage_piece(c);
+				src = b->h_reads.as<uint8_t>() + c.src_off;
+			}
+			HIP_TRY(hipMemcpyAsync(b->d_reads.p + c.dst_off, src, (size_t) c.len, hipMemcpyHostToDevice, st));
+		}
+	}
+	const void *const from[] = { hseq, hdelta, b->h_zero.p, n && !segments ? tiles[0].qry : nullptr, n ? tiles[0].ref : nullptr };      /* UploadSrc */
 	auto issue = [&](size_t r0, size_t r1) -> int {
 		for (size_t r = r0; r < r1; ++r) {
 			const UploadCopy &c = sch.copies[r];
@@ -186,6 +230,19 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 		/* rows arena: only for the tiles whose corridors came as arrays; closed forms are evaluated where they are needed */
 		if (L.arena_rows) HIP_TRY(launch_expand_rows(b->d_rsrc.p, b->d_tin.p, b->d_delta.p, b->d_rowsx.p, b->d_rows.p, n, false, st));
 	}
+	if ((windows || segments) && n) RC_TRY(issue(sch.n_staged, sch.copies.size()));      /* the pads the device clears itself */
+	if (segments && n) {
+		/* the queries: written from the read block straight into the arena, behind the block's copy and the pad clears and in
+		 * front of the event the plan waits for; nothing of them ever lies on the host */
+		const size_t dbytes = (size_t) n * sizeof(SegDesc), cbytes = sp.chunks.size() * sizeof(SegChunk);
+		RC_TRY(b->h_segs.ensure(dbytes + cbytes + 64));
+		RC_TRY(b->d_segs.ensure(dbytes + cbytes + 64));
+		memcpy(b->h_segs.p, sp.desc.data(), dbytes);
+		if (cbytes) memcpy(b->h_segs.as<uint8_t>() + dbytes, sp.chunks.data(), cbytes);
+		HIP_TRY(hipMemcpyAsync(b->d_segs.p, b->h_segs.p, (dbytes + cbytes + 3) / 4 * 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(launch_stage_segments(b->d_reads.p, reinterpret_cast<const SegDesc *>(b->d_segs.p), reinterpret_cast<const SegChunk *>(b->d_segs.p + dbytes),
+				(int) sp.chunks.size(), b->d_seq.p, st));
+	}
 	if (windows && n) {
 		/* the references: decoded from the resident genome straight into the arena (and its last pad cleared) */
 		RC_TRY(b->h_win.ensure((size_t) n * sizeof(WindowDesc)));
@@ -197,7 +254,6 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 			hw[i].n_chars = tiles[i].ref_len;
 		}
 		HIP_TRY(hipMemcpyAsync(b->d_win.p, hw, (size_t) n * sizeof(WindowDesc), hipMemcpyHostToDevice, st));
-		RC_TRY(issue(sch.n_staged, sch.copies.size()));
 		HIP_TRY(launch_decode_windows(genome->d_bin.p, genome->d_starts.p, genome->n_starts, b->d_win.p, n, b->d_seq.p, st));
 		/* the decoded characters back to the host, 1 byte per reference base under everything that follows: a caller whose
 		 * text stage runs on the host (MD needs the reference base of every mismatch and deletion) reads them there
@@ -536,6 +592,29 @@ int pump(cvx_context *h, bool block, const cvx_batch_s *upto) {
 	return CVX_OK;
 }
 
+/* what cvx_stage_segments and cvx_stage_segments_host share: the arguments checked, the strings laid out back to back
+ * (*used, qry_off) and planned; CVX_ERR_CAPACITY when out is too small for them */
+int stage_segments_plan(const char *who, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n, const cvx_read_segment *seg,
+		const int32_t *len, const uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used, SegPlan &sp) {
+	if (!used || n_reads < 0 || n < 0 || !offsets || (n_reads > 0 && !arena) || (n > 0 && (!seg || !len || !qry_off)) || (cap > 0 && !out)) {
+		set_err("%s: bad argument", who);
+		return CVX_ERR_ARG;
+	}
+	*used = 0;
+	int64_t bad = 0;
+	std::vector<uint64_t> dst((size_t) n + 1, 0);
+	for (int32_t i = 0; i < n; ++i) dst[(size_t) i + 1] = dst[(size_t) i] + (uint64_t) std::max(len[i], 0);
+	if (segments_plan(n_reads, offsets, n, seg, [&](int32_t i) { return len[i]; }, [&](int32_t i) { return dst[(size_t) i]; }, sp, &bad) != CVX_OK) {
+		if (bad < 0) set_err("%s: the offsets of read %lld do not ascend (or span 2 GB)", who, (long long) (-1 - bad));
+		else set_err("%s: string %lld: read %d of %d, start %d, length %d, flags %d", who, (long long) bad, seg[bad].read, n_reads, seg[bad].start, len[bad], seg[bad].flags);
+		return CVX_ERR_ARG;
+	}
+	*used = sp.seg_bytes;
+	for (int32_t i = 0; i < n; ++i) qry_off[i] = dst[(size_t) i];
+	if (cap < sp.seg_bytes) { set_err("%s: %llu bytes needed, %llu given", who, (unsigned long long) sp.seg_bytes, (unsigned long long) cap); return CVX_ERR_CAPACITY; }
+	return CVX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -677,7 +756,8 @@ int cvx_align_batch(cvx_handle h, int32_t n, const cvx_tile *tiles, cvx_result *
 
 /* ------------------------------------------------------------------ streaming form */
 
-static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const cvx_genome_s *genome, const uint64_t *ref_position, cvx_job *out) {
+static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const cvx_genome_s *genome, const uint64_t *ref_position, cvx_job *out,
+		const SegmentsIn *segs = nullptr) {
 	if (!h || !out || n < 0 || (n > 0 && !tiles) || (genome && n > 0 && !ref_position)) { set_err("cvx_submit: bad argument"); return CVX_ERR_ARG; }
 	*out = nullptr;
 	if (genome && genome->device != h->device) { set_err("cvx_submit_windows: the genome lives on device %d, the handle on %d", genome->device, h->device); return CVX_ERR_ARG; }
@@ -693,7 +773,7 @@ static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const c
 	if (!b) return CVX_ERR_OOM;
 	b->bind(h->marks);
 	const auto t2 = std::chrono::steady_clock::now();
-	int rc = stage_upload(h, b, n, tiles, genome, ref_position);
+	int rc = stage_upload(h, b, n, tiles, genome, ref_position, segs);
 	const auto t3 = std::chrono::steady_clock::now();
 	if (rc == CVX_OK) rc = stage_plan(h, b, h->s_io);
 	if (rc != CVX_OK) { discard_batch(h, b); return rc; }
@@ -719,6 +799,75 @@ int cvx_submit_windows(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *ti
 	ABI_GUARD_BEGIN
 	if (!g) { set_err("cvx_submit_windows: NULL genome"); return CVX_ERR_ARG; }
 	return submit_common(h, n, tiles, g, ref_position, out);
+	ABI_GUARD_END
+}
+
+int cvx_submit_segments(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position,
+		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, const cvx_read_segment *qry, cvx_job *out) {
+	ABI_GUARD_BEGIN
+	if (n_reads < 0 || !offsets || (n_reads > 0 && !arena) || (n > 0 && !qry) || (!g && ref_position)) { set_err("cvx_submit_segments: bad argument"); return CVX_ERR_ARG; }
+	const SegmentsIn segs = { n_reads, arena, offsets, qry };
+	return submit_common(h, n, tiles, g, ref_position, out, &segs);
+	ABI_GUARD_END
+}
+
+int cvx_job_zero_copy_bytes(cvx_job j, uint64_t *bytes) {
+	ABI_GUARD_BEGIN
+	if (!j || !bytes || j->state < kUploaded) { set_err("cvx_job_zero_copy_bytes: not a submitted job"); return CVX_ERR_ARG; }
+	*bytes = j->zero_copy_bytes;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+/* the kernel alone: the strings back to back in a device arena of their own, and back (nothing here is on the path of a job,
+ * so the buffers are the call's own) */
+int cvx_stage_segments(cvx_handle h, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
+		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used) {
+	ABI_GUARD_BEGIN
+	if (!h) { set_err("cvx_stage_segments: bad argument"); return CVX_ERR_ARG; }
+	SegPlan sp;
+	RC_TRY(stage_segments_plan("cvx_stage_segments", n_reads, arena, offsets, n, seg, len, out, cap, qry_off, used, sp));
+	if (sp.chunks.empty()) return CVX_OK;
+	HIP_TRY(hipSetDevice(h->device));
+	RC_TRY(ensure_streams(h));
+	const size_t dbytes = (size_t) n * sizeof(SegDesc), cbytes = sp.chunks.size() * sizeof(SegChunk);
+	DevBuf<uint8_t> d_reads, d_segs, d_out;
+	int rc = d_reads.ensure((size_t) sp.read_bytes + 256);
+	if (rc == CVX_OK) rc = d_segs.ensure(dbytes + cbytes + 64);
+	if (rc == CVX_OK) rc = d_out.ensure((size_t) sp.seg_bytes + 256);
+	hipError_t e = hipSuccess;
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	if (rc == CVX_OK) {
+		hipStream_t st = h->s_main;
+		e = hipEventCreate(&e0);
+		if (e == hipSuccess) e = hipEventCreate(&e1);
+		if (e == hipSuccess) e = hipMemcpyAsync(d_reads.p, arena + offsets[0], (size_t) sp.read_bytes, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(d_segs.p, sp.desc.data(), dbytes, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(d_segs.p + dbytes, sp.chunks.data(), cbytes, hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) e = hipEventRecord(e0, st);
+		if (e == hipSuccess) e = launch_stage_segments(d_reads.p, reinterpret_cast<const SegDesc *>(d_segs.p), reinterpret_cast<const SegChunk *>(d_segs.p + dbytes),
+				(int) sp.chunks.size(), d_out.p, st);
+		if (e == hipSuccess) e = hipEventRecord(e1, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t) sp.seg_bytes, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e == hipSuccess) h->segments_kernel_ms = ev_ms(e0, e1);
+	}
+	if (e0) (void) hipEventDestroy(e0);
+	if (e1) (void) hipEventDestroy(e1);
+	d_reads.release(); d_segs.release(); d_out.release();
+	if (rc != CVX_OK) return rc;
+	if (e != hipSuccess) { (void) hipGetLastError(); set_err("cvx_stage_segments: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_stage_segments_host(int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
+		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used) {
+	ABI_GUARD_BEGIN
+	SegPlan sp;
+	RC_TRY(stage_segments_plan("cvx_stage_segments_host", n_reads, arena, offsets, n, seg, len, out, cap, qry_off, used, sp));
+	if (sp.seg_bytes > 0) stage_segments_host(arena + offsets[0], sp.desc, out);
+	return CVX_OK;
 	ABI_GUARD_END
 }
 

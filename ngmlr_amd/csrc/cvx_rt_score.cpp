@@ -414,6 +414,7 @@ int cvx_stage_kernel_ms(cvx_handle h, int32_t stage, float *ms) {
 	case CVX_STAGE_DECODE: *ms = h->decode_kernel_ms; return CVX_OK;
 	case CVX_STAGE_SEARCH: *ms = search_kernel_ms(h->search); return CVX_OK;
 	case CVX_STAGE_SEARCH_SCORE: *ms = search_score_kernel_ms(h->search); return CVX_OK;
+	case CVX_STAGE_SEGMENTS: *ms = h->segments_kernel_ms; return CVX_OK;
 	default: set_err("cvx_stage_kernel_ms: unknown stage %d", stage); return CVX_ERR_ARG;
 	}
 	ABI_GUARD_END

@@ -40,6 +40,9 @@ mkdir -p "$REPO/oracle/_ref"
 #   ngmlr_hip_feed     ngmlr_hip_scorewin + a CS batch of sub-reads searched AND scored in one device call (cs_feed_binding.inc inside
 #                      cs_search_binding.inc: CandidateSearchHip::SearchAndScore, ScoreBuffer::addScoredRead over the reference's own
 #                      completion block); CVX_CS_FEED=0 keeps the two calls inside the same binary (tests/test_gpu_e2e_feed.py)
+#   ngmlr_hip_readseg  ngmlr_hip_all + the query of every alignment tile as a segment of the launch's read block, written on the device
+#                      (read_segments_binding.inc at the top of the Interval overload of extractReadSeq, Convex::DeviceReads::CopyOut
+#                      in checkForSV); CVX_DEVICE_READS=0 restores the reference's strings inside the same binary (tests/test_gpu_e2e_readseg.py)
 #   ngmlr_index_cpu    the reference's CPU code with only that table builder bound: the table file it writes against the unmodified
 #                      binary's, without a GPU (tests/test_index_cpu.py)
 #   ngmlr_pool_cpu     the reference's CPU aligners + the same pool: the pool's own correctness without a GPU (tests/test_pool_cpu.py)
@@ -47,15 +50,16 @@ mkdir -p "$REPO/oracle/_ref"
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 SCOREWIN = sys.argv[10]
 FEED = sys.argv[11]
+READSEG = sys.argv[12]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -96,6 +100,16 @@ if INDEX and POOL:
     s = open(p).read()
     s = sub1(s, 'char const * const AlignmentBuffer::extractReferenceSequenceForAlignment(Interval const*& interval, int & refSeqLength) {\n',
              'char const * const AlignmentBuffer::extractReferenceSequenceForAlignment(Interval const*& interval, int & refSeqLength) {\n#include "window_decode_binding.inc"\n', 'extractReferenceSequenceForAlignment')
+    open(p, 'w').write(s)
+if READSEG:
+    # the query of an alignment tile as a segment of the launch's read block (ngmlr_amd/csrc/read_segments_binding.inc,
+    # Convex::DeviceReads in convex_align_hip.h, which AlignmentBuffer.h includes for every device variant)
+    assert CLASS != 'cpu'
+    p = T + '/src/AlignmentBuffer.cpp'
+    s = open(p).read()
+    s = sub1(s, '\t\tInterval const * interval, MappedRead* read,\n\t\tbool const revComp) {\n', '\t\tInterval const * interval, MappedRead* read,\n\t\tbool const revComp) {\n#include "read_segments_binding.inc"\n', 'extractReadSeq (Interval overload)')
+    s = sub1(s, 'strncpy(readSeq, fullReadSeq + inversionMidpointOnRead - readCheckLength, readCheckLength * 2);',
+             'Convex::DeviceReads::CopyOut(readSeq, fullReadSeq, inversionMidpointOnRead - readCheckLength, readCheckLength * 2);', 'checkForSV')
     open(p, 'w').write(s)
 if SEARCH:
     # the k-mer vote of a CS thread's batch on the device (ngmlr_amd/csrc/candidate_search_hip.h, cs_search_binding.inc)
@@ -280,10 +294,11 @@ bv ngmlr_hip_all Convex::SharedAligner StrippedSWHip sam pool search index
 bv ngmlr_hip_checks Convex::SharedAligner StrippedSWHip sam pool search index checks
 bv ngmlr_hip_scorewin Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin
 bv ngmlr_hip_feed Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin feed
+bv ngmlr_hip_readseg Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" readseg
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
