@@ -181,7 +181,10 @@ typedef struct cvx_context *cvx_handle;
 typedef struct cvx_batch_s *cvx_batch;
 typedef struct cvx_batch_s *cvx_job;      /* a batch travelling through the streaming form */
 
-/* Timing of the last cvx_batch_run, measured with HIP events on the library's stream. */
+/* Timing of the last cvx_batch_run, measured with HIP events on the library's stream.  fill_ms runs until the last fill of the batch
+ * has ended and backtrack_ms is the rest of the compute stage: the walk of a class that is walked behind its own fill while another
+ * class still fills lies inside fill_ms, and so does the walk of the head of a class whose last round of tiles is filled by a launch
+ * of its own (CVX_TUNE_TAIL_SPLIT) -- it runs while that tail still fills.  The two always add up to the compute stage. */
 typedef struct {
 	float plan_ms;      /* corridor analysis kernel + plan readback */
 	float fill_ms;      /* all forward-fill launches */

@@ -907,7 +907,34 @@ struct ScheduleTuning {
 	bool bt_per_class = true;
 	bool overlap_post = false;
 	int wide_prio = 1, gang_prio = 0, chain_prio = -1, chain_lds_kb = 48;
+	/* the tail split of a whole-tile class (tail_split below): 0 = none; N > 0 = the last N tiles of every whole-tile class with more
+	 * than N two-phase tiles; kTailAuto = tail_rounds resident rounds of the class, where the class and the batch are large enough */
+	int tail_tiles = 0;
+	float tail_rounds = 1.0f;
+	int tail_waves_per_simd[kNumClasses * 2] = {0};      /* kTailAuto: resident waves per SIMD of each class's two-phase fill (HostPlan::cls index; 0 = unknown, no split) */
 };
+
+enum { kTailAuto = -1 };
+/* kTailAuto splits a class of at least this many resident rounds, in a batch that walks at least this many tiles (where the walk is issue-bound) */
+static const int kTailMinRounds = 4;
+static const int kTailMinWalk = 4096;
+
+/* Tiles at the end of a whole-tile class's list (`two_phase` = count - n_direct entries behind its direct-exact prefix) that are filled
+ * by a launch of their own on the handle's low-priority stream (stage_compute): the class's shortest tiles, the ones dispatched
+ * last anyway.  One wave fills one tile, so from the moment a launch has nothing left to dispatch its resident waves retire over
+ * the length of a tile and the device runs from full to empty; with the last round split off, the head of the class is walked in the
+ * issue slots that the draining tail leaves free.  0 = no split: either part would be empty, the class is a gang, or -- kTailAuto --
+ * the class would not fill the device kTailMinRounds times over or the batch's walk is not issue-bound. */
+inline int tail_split(const ScheduleTuning &t, int cls, int gang, int two_phase, int n_walk, int num_cus) {
+	if (t.tail_tiles == 0 || gang > 1 || t.overlap_post || !t.bt_per_class) return 0;
+	int tail = t.tail_tiles;
+	if (t.tail_tiles == kTailAuto) {
+		const int64_t resident = (int64_t) num_cus * 4 * (int64_t) t.tail_waves_per_simd[cls];
+		if (resident <= 0 || (int64_t) two_phase < kTailMinRounds * resident || n_walk < kTailMinWalk) return 0;
+		tail = (int) ((double) t.tail_rounds * (double) resident + 0.5);
+	}
+	return (tail > 0 && tail < two_phase) ? tail : 0;
+}
 
 /* launch_fill's `mode` (= FillMode of cvx_kernels.hip) */
 enum { kModeTwoPhase = 0, kModeExact = 1, kModeChain = 2 };
@@ -976,9 +1003,14 @@ struct FillLaunch {
 	size_t pad_lds = 0;              /* chained: chain_pad_lds */
 	int prio = 0;                    /* FillArgs::chain_prio: the chain priority, the widest ring class's or the gangs' */
 	int stream = kOnMain;            /* StreamSlot */
+	/* whole tiles only, > 0: the launch is issued as two fills -- the head lists[list_off, + count - tail_count), which keeps the direct-exact
+	 * prefix, on `stream`, and the tail, the last tail_count entries of the same list, on the handle's low-priority stream (tail_split) */
+	int tail_count = 0;
 	size_t bt_off = 0;               /* the launch's backtrack segment: lists[bt_off, + bt_count) */
 	int bt_count = 0;
-	WalkPlan walk;                   /* of that segment (per_class only) */
+	int bt_tail_count = 0;           /* a split launch: the segment holds the head's tiles, then, from bt_count - bt_tail_count on, the tail's, each part longest read first */
+	WalkPlan walk;                   /* of that segment, of its head part when the launch is split (per_class only) */
+	WalkPlan walk_tail;              /* of the tail part */
 	cvx_launch_info info;
 };
 
@@ -987,7 +1019,7 @@ struct ComputeSchedule {
 	size_t n_listed = 0;                   /* entries of `lists`: fill lists, then the backtrack segments from bt_begin on */
 	size_t bt_begin = 0;
 	int n_walk = 0;                        /* tiles of all backtrack segments */
-	bool per_class = false;                /* every launch walks its own segment behind its fill; else one walk (`walk`) behind all fills */
+	bool per_class = false;                /* every launch walks its own segment behind its fill (always so when a launch is split); else one walk (`walk`) behind all fills */
 	WalkPlan walk;
 	/* chained tiles: tasks of every chain class, block table and tile lists in one upload */
 	size_t chain_task_off[kNumChainClasses * 2] = {0}, chain_tile_off[kNumChainClasses * 2] = {0};
@@ -1024,6 +1056,9 @@ inline void build_schedule(HostPlan &hp, const TilePlan *plan, const TileIn *tin
 		memcpy(lists + n_listed, v.data(), v.size() * sizeof(int32_t));
 		n_listed += v.size();
 	}
+	/* (every computed tile is walked: what the backtrack segments will hold) */
+	int n_computed = 0;
+	for (int i = 0; i < n; ++i) if (!hp.trun[(size_t) i].skip) n_computed++;
 	const size_t generic_begin = n_listed;
 	if (!hp.generic.empty()) memcpy(lists + n_listed, hp.generic.data(), hp.generic.size() * sizeof(int32_t));
 	n_listed += hp.generic.size();
@@ -1061,6 +1096,7 @@ inline void build_schedule(HostPlan &hp, const TilePlan *plan, const TileIn *tin
 		/* (the widest ring class of a batch of several one priority notch up; gangs have a knob of their own) */
 		L.prio = kc.gang > 1 ? t.gang_prio : (widest && ring_classes > 1) ? t.wide_prio : 0;
 		widest = false;
+		L.tail_count = tail_split(t, cc, kc.gang, L.count - L.n_direct, n_computed, num_cus);
 		s.launches.push_back(L);
 	}
 	if (!hp.generic.empty()) {
@@ -1090,27 +1126,36 @@ inline void build_schedule(HostPlan &hp, const TilePlan *plan, const TileIn *tin
 	constexpr int kBuckets = 4096;
 	auto bucket = [&](int32_t ti) { const int k = tin[(size_t) ti].H >> 5; return kBuckets - 1 - (k < kBuckets ? k : kBuckets - 1); };
 	std::vector<int32_t> count((size_t) kBuckets + 1);
+	bool any_split = false;
 	for (size_t i = 0; i < s.launches.size(); ++i) {
 		FillLaunch &L = s.launches[i];
 		L.stream = order[i % (size_t) n_order];
 		memset(&L.info, 0, sizeof(L.info));
 		L.info.slots_per_lane = L.m; L.info.wrap16 = L.wrap; L.info.n_tiles = (int) L.tiles->size(); L.info.kind = L.kind;
 		L.info.waves = L.kind == CVX_LAUNCH_CHAINED ? L.count : L.gang;      /* row-block tasks / waves per tile (a gang's size) */
-		std::fill(count.begin(), count.end(), 0);
 		for (int32_t ti : *L.tiles) {
 			const TilePlan &p = plan[(size_t) ti];
 			const TileIn &in = tin[(size_t) ti];
 			L.info.cells += p.cells; L.info.active_cells += p.active;
 			L.info.alg_bytes += p.cells + 6ull * (uint64_t) in.H + 2ull * (uint64_t) in.W;
 			L.info.read_bases += (uint64_t) in.H;
-			if (!hp.trun[(size_t) ti].skip) count[(size_t) bucket(ti) + 1]++;
 		}
-		for (int k = 0; k < kBuckets; ++k) count[(size_t) k + 1] += count[(size_t) k];
 		L.bt_off = n_listed;
-		L.bt_count = count[(size_t) kBuckets];
-		/* (stable: inside a bucket of equally long reads the class's own order, most cells first) */
-		for (int32_t ti : *L.tiles) if (!hp.trun[(size_t) ti].skip) lists[n_listed + (size_t) count[(size_t) bucket(ti)]++] = ti;
-		n_listed += (size_t) L.bt_count;
+		/* (a split launch: the head's tiles, then the tail's -- the two parts are walked one after the other) */
+		const size_t n_head = L.tiles->size() - (size_t) L.tail_count;
+		for (int part = 0; part < (L.tail_count > 0 ? 2 : 1); ++part) {
+			const int32_t *tb = L.tiles->data() + (part ? n_head : 0), *te = L.tiles->data() + (part ? L.tiles->size() : n_head);
+			std::fill(count.begin(), count.end(), 0);
+			for (const int32_t *q = tb; q < te; ++q) if (!hp.trun[(size_t) *q].skip) count[(size_t) bucket(*q) + 1]++;
+			for (int k = 0; k < kBuckets; ++k) count[(size_t) k + 1] += count[(size_t) k];
+			const int part_count = count[(size_t) kBuckets];
+			/* (stable: inside a bucket of equally long reads the class's own order, most cells first) */
+			for (const int32_t *q = tb; q < te; ++q) if (!hp.trun[(size_t) *q].skip) lists[n_listed + (size_t) count[(size_t) bucket(*q)]++] = *q;
+			n_listed += (size_t) part_count;
+			if (part) L.bt_tail_count = part_count;
+		}
+		L.bt_count = (int) (n_listed - L.bt_off);
+		any_split = any_split || L.tail_count > 0;
 	}
 	s.n_listed = n_listed;
 	s.n_walk = (int) (n_listed - s.bt_begin);
@@ -1122,9 +1167,15 @@ inline void build_schedule(HostPlan &hp, const TilePlan *plan, const TileIn *tin
 	/* Only where the walk is issue-bound (>= 4096 tiles; measured, r04c: ONT mix 60 000 tiles 57.2 -> 56.0 ms, 24 000 tiles
 	 * 35.3 -> 34.2, C5 mix 6 144 tiles 397 -> 369 ms); a small batch's one-wave-per-tile walks are latency-bound chains that
 	 * gain nothing from starting early and cost the fills still running (C5 mix 2 048 tiles: 183.6 -> 187.2 ms). */
-	s.per_class = t.bt_per_class && s.launches.size() > 1 && !t.overlap_post && s.n_walk >= 4096;
+	/* A schedule with a split launch walks per launch whatever its size: the head of the split class behind the head's fill, the tail
+	 * behind the tail's, each part with the lanes its own count gives it. */
+	s.per_class = (t.bt_per_class && s.launches.size() > 1 && !t.overlap_post && s.n_walk >= 4096) || any_split;
 	const uint64_t mean_h = n_rows / (uint64_t) std::max(n, 1);
-	if (s.per_class) for (FillLaunch &L : s.launches) L.walk = walk_plan(L.bt_count, s.n_walk, t.bt_group, mean_h, lists + L.bt_off, tin);
+	if (s.per_class) for (FillLaunch &L : s.launches) {
+		const int n_head = L.bt_count - L.bt_tail_count;
+		L.walk = walk_plan(n_head, s.n_walk, t.bt_group, mean_h, lists + L.bt_off, tin);
+		if (L.bt_tail_count > 0) L.walk_tail = walk_plan(L.bt_tail_count, s.n_walk, t.bt_group, mean_h, lists + L.bt_off + (size_t) n_head, tin);
+	}
 	else s.walk = walk_plan(s.n_walk, s.n_walk, t.bt_group, mean_h, lists + s.bt_begin, tin);
 
 	s.chain_blk_off = s.chain_bytes = 0;

@@ -159,8 +159,9 @@ void score_state_free(cvx_score_state *ss);
  * 24 558-tile M = 3 launch instead of beside it. */
 static const int kAuxStreams = 2;      /* (round 5: a batch has up to four fill classes -- chained, gangs, M = 4, M = 3 -- and each wants a stream of its own) */
 
-/* the events of one fill launch: its start, two-phase pass done, exact pass done, the class's own backtrack done */
-enum LaunchEvent { kLevStart = 0, kLevTwoPhase = 1, kLevExact = 2, kLevWalked = 3, kLevPerLaunch = 4 };
+/* the events of one fill launch: its start, two-phase pass done, exact pass done, the class's own backtrack done; and of the tail of a
+ * split launch (FillLaunch::tail_count, recorded on the handle's low-priority stream): its start, two-phase pass done, exact pass done */
+enum LaunchEvent { kLevStart = 0, kLevTwoPhase = 1, kLevExact = 2, kLevWalked = 3, kLevTailStart = 4, kLevTailTwoPhase = 5, kLevTailExact = 6, kLevPerLaunch = 7 };
 
 enum BatchState { kFailed = -1, kEmpty = 0, kUploaded = 1, kPlanned = 2, kComputed = 3, kFinished = 4 };
 
@@ -245,6 +246,7 @@ struct cvx_batch_s {
 	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* timing: plan begin/end, fills done, all done, fills may start */
 	std::vector<hipEvent_t> lev;     /* kLevPerLaunch events per fill launch (LaunchEvent) */
 	std::vector<cvx_launch_info> launches;
+	std::vector<int> launch_tail;    /* per fill launch: tiles of its tail (0: not split, its tail events were not recorded) */
 	cvx_timing timing;
 
 	const TileIn *tin() const { return h_tin.as<TileIn>(); }
@@ -313,6 +315,9 @@ struct cvx_context {
 	                                  * fills of the batches that follow */
 	hipStream_t s_post = nullptr;    /* backtrack, finalize, compaction, result download: runs beside the NEXT batch's fill */
 	hipStream_t aux[kAuxStreams] = {nullptr};  /* concurrent fill classes */
+	hipStream_t s_tail = nullptr;    /* the tails of split fill classes and nothing else (stage_compute): the device's lowest queue priority, so that a tail
+	                                  * is dispatched where its head leaves wave slots free.  Stays null, and no class is split, when the device has no
+	                                  * priority below the default */
 	bool service = false;                      /* cvx_create_ex(CVX_CREATE_SERVICE): short search / scoring / decode calls only */
 	bool owns_main = true;                     /* false: s_main is one of the process's shared service streams */
 	std::mutex streams_mtx;                    /* ensure_streams */
@@ -353,6 +358,13 @@ struct cvx_context {
 	int bt_group = 0;          /* lanes per tile in the backtrack: 0 = auto (by the number of tiles walked together: 64 / 32 / 16 / 8, and 32 for
 	                            * the much-longer-than-average reads of a bulk walked at 8 or 16), 8 / 16 / 32 = that many for all, 64 = the
 	                            * one-wave-per-tile walk, -1 = round 4's rule (64 below 4 096 tiles, else 8 + 32) (env CVX_TUNE_BT_GROUP) */
+	int tail_split = cvx::kTailAuto;   /* tuning knob (env CVX_TUNE_TAIL_SPLIT): 0 = no fill class is split, N > 0 = every whole-tile class with more than N
+	                            * two-phase tiles gets a tail of N (test knob), unset = by the class's resident waves (tail_split, cvx_host_logic.h) */
+	float tail_rounds = 1.0f;  /* the automatic rule's tail in resident rounds of the class (env CVX_TUNE_TAIL_ROUNDS) */
+	int tail_gate = 1;         /* experiment (env CVX_TUNE_TAIL_GATE): 1 = the tail waits for the head's start event, 0 = for the batch's inputs only */
+	int tail_trace = 0;        /* env CVX_TUNE_TAIL_TRACE = 1: one stderr line per split launch of a finished batch, from its events */
+	int fill_waves[cvx::kNumClasses * 2] = {0};   /* resident waves per SIMD of each whole-tile class's two-phase fill as the runtime reports the kernel's
+	                            * occupancy (0: not asked yet, -1: unknown); filled by stage_compute for the classes a batch uses */
 	bool bt_per_class = true;  /* tuning knob (env CVX_TUNE_BT_PER_CLASS = 0 clears it): a batch of several fill classes walks each class behind its own fill (build_schedule) */
 	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
 	bool scalar_twin = false; /* cvx_create_ex(CVX_CREATE_SCALAR_TWIN): the semantics of Convex::ConvexAlign (cvx_host_logic.h, fill_semantics) */

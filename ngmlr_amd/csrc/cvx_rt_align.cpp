@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "cvx_fill_occupancy.h"
 #include "cvx_qry_stage.h"
 #include "cvx_rt.h"
 
@@ -363,6 +364,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	hipStream_t st = S_main;
 	HIP_TRY(hipEventSynchronize(b->ev_in));        /* queued a whole batch ago in the streaming case */
 	b->launches.clear();
+	b->launch_tail.clear();
 	b->ops_total = 0;
 	b->have_ops = false;
 	if (n == 0) {
@@ -406,6 +408,17 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	ScheduleTuning stune;
 	stune.exact_steps = h->tune_exact_steps; stune.bt_group = h->bt_group; stune.bt_per_class = h->bt_per_class; stune.overlap_post = h->overlap_post;
 	stune.wide_prio = h->tune_wide_prio; stune.gang_prio = h->tune_gang_prio; stune.chain_prio = h->tune_chain_prio; stune.chain_lds_kb = h->tune_chain_lds_kb;
+	/* the tail split: only with the low-priority stream to put the tails on; the automatic rule sizes a class's tail by the occupancy of
+	 * the kernel its two-phase pass will launch, asked once per class and handle */
+	stune.tail_tiles = h->s_tail ? h->tail_split : 0;
+	stune.tail_rounds = h->tail_rounds;
+	if (stune.tail_tiles == kTailAuto) {
+		for (size_t c = 0; c < hp.cls.size(); ++c) {
+			if (hp.cls[c].empty() || kClasses[c / 2].gang > 1) continue;
+			if (h->fill_waves[c] == 0) h->fill_waves[c] = fill_two_phase_waves_per_simd(kClasses[c / 2].m, (c & 1) != 0, h->tune_pen_table != 0, h->scalar_twin);
+			stune.tail_waves_per_simd[c] = std::max(0, h->fill_waves[c]);
+		}
+	}
 	ComputeSchedule sch;
 	build_schedule(hp, b->plan(), b->tin(), n, b->n_rows, h->num_cus, stune, b->h_lists.as<int32_t>(), sch);
 	memcpy(b->h_trun.p, hp.trun.data(), (size_t) n * sizeof(TileRun));
@@ -448,6 +461,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
 		const bool wrap = L.wrap != 0;
 		b->launches.push_back(L.info);
+		b->launch_tail.push_back(L.tail_count);
 		HIP_TRY(hipStreamWaitEvent(ls, b->ev[4], 0));
 		HIP_TRY(hipEventRecord(le[kLevStart], ls));
 		FillArgs a = fa;
@@ -474,14 +488,46 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 			a.list_n = L.n_direct;
 			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
 			a.list += L.n_direct;
-			a.list_n = L.count - L.n_direct;
+			a.list_n = L.count - L.n_direct - L.tail_count;      /* (a split class: the head; its tail follows below) */
 			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, a, 0, ls));
 			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
 			/* exact-tracking pass over the tiles the two-phase pass flagged (usually none) */
 			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
+			if (L.tail_count > 0) {
+				/* The tail of a split class: the same two passes over the last tail_count entries of the class's list, on the low-priority
+				 * stream behind the input copies.  The device takes its workgroups where the head's launch leaves wave slots free -- from
+				 * the moment the head has nothing left to dispatch -- and while the tail drains, the head's walk (below, on `ls`) has
+				 * the issue slots the tail no longer uses.  Streams, events and queue priority order all of it; the kernels are the
+				 * head's and know nothing of the split.  (The flag the exact pass reads is per tile and redo_count is a statistic: the
+				 * head's exact pass may run beside the tail's two-phase pass.)
+				 * The tail waits for the head's START event, not just for the inputs: both streams would otherwise leave the same
+				 * barrier at the same moment, and in most batches the tail's workgroups -- exactly one resident round -- were then
+				 * dispatched first and the head filled in behind them (the tail's start event 0.02 ms BEFORE the head's in two batches
+				 * of three, the step 116.3 ms instead of 114.6; profiles/r16_tail_split.txt).  Behind the start event the head's
+				 * dispatch is already under way when the low-priority queue is looked at, and the tail begins one tile's duration
+				 * before the head ends, every time.  CVX_TUNE_TAIL_GATE=0: the inputs only. */
+				FillArgs ta = a;
+				ta.list = a.list + a.list_n;
+				ta.list_n = L.tail_count;
+				HIP_TRY(hipStreamWaitEvent(h->s_tail, h->tail_gate ? le[kLevStart] : b->ev[4], 0));
+				HIP_TRY(hipEventRecord(le[kLevTailStart], h->s_tail));
+				HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, ta, 0, h->s_tail));
+				HIP_TRY(hipEventRecord(le[kLevTailTwoPhase], h->s_tail));
+				HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, ta, 0, h->s_tail));
+				HIP_TRY(hipEventRecord(le[kLevTailExact], h->s_tail));
+			}
 		}
 		HIP_TRY(hipEventRecord(le[kLevExact], ls));
-		if (sch.per_class) RC_TRY(issue_walk(b, ba, L.walk, L.bt_off, L.bt_count, ls, nullptr));
+		if (sch.per_class) {
+			const int n_head = L.bt_count - L.bt_tail_count;
+			RC_TRY(issue_walk(b, ba, L.walk, L.bt_off, n_head, ls, nullptr));
+			if (L.tail_count > 0) {
+				/* the tail's walk behind the tail's fill, on `ls`: whatever is queued on `ls` after this launch -- the next batch's fill --
+				 * stays behind all of this batch's class */
+				HIP_TRY(hipStreamWaitEvent(ls, le[kLevTailExact], 0));
+				RC_TRY(issue_walk(b, ba, L.walk_tail, L.bt_off + (size_t) n_head, L.bt_tail_count, ls, nullptr));
+			}
+		}
 		HIP_TRY(hipEventRecord(le[kLevWalked], ls));      /* what everything after the fills waits for */
 	}
 	/* Everything after the fills CAN run on its own stream, so that `main` goes straight on to the next
@@ -518,19 +564,34 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 
 /* ---- wait for the result records; timing of the batch */
 int stage_results(cvx_context *h, cvx_batch_s *b) {
-	(void) h;
 	if (b->state < kComputed) { set_err("internal: results requested from a batch whose kernels were never queued (state %d)", b->state); return CVX_ERR_ARG; }
 	HIP_TRY(hipEventSynchronize(b->ev_res));
 	if (b->n == 0) { b->ops_total = 0; b->state = kFinished; return CVX_OK; }
 	const BatchSummary *s = b->summary();
 	b->ops_total = s->ops_total;
 	const int launches = b->timing.n_fill_launches;
-	for (int i = 0; i < launches; ++i) b->launches[(size_t) i].ms = ev_ms(b->lev[(size_t) i * kLevPerLaunch + kLevStart], b->lev[(size_t) i * kLevPerLaunch + kLevTwoPhase]);
+	for (int i = 0; i < launches; ++i) {
+		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		b->launches[(size_t) i].ms = ev_ms(le[kLevStart], le[kLevTwoPhase]);
+		/* a split class: one record, from the head's start to the later of the two two-phase ends */
+		if (b->launch_tail[(size_t) i] > 0) b->launches[(size_t) i].ms = std::max(b->launches[(size_t) i].ms, ev_ms(le[kLevStart], le[kLevTailTwoPhase]));
+	}
 	b->timing.plan_ms = ev_ms(b->ev[0], b->ev[1]);
 	/* fill = until the last fill class has finished its exact pass; backtrack = what is left of the compute stage (when every
 	 * class is walked behind its own fill, the walks of the early classes lie inside `fill`: the two still add up) */
 	float fill_end = 0.0f;
-	for (int i = 0; i < launches; ++i) fill_end = std::max(fill_end, ev_ms(b->ev[4], b->lev[(size_t) i * kLevPerLaunch + kLevExact]));
+	for (int i = 0; i < launches; ++i) {
+		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		fill_end = std::max(fill_end, ev_ms(b->ev[4], le[kLevExact]));
+		if (b->launch_tail[(size_t) i] > 0) {      /* (the head's walk then lies inside `fill`: it runs while the tail still fills) */
+			fill_end = std::max(fill_end, ev_ms(b->ev[4], le[kLevTailExact]));
+			if (h->tail_trace)
+				fprintf(stderr, "cvx tail split: launch %d m=%d tiles=%d tail=%d  head two-phase end %.3f exact end %.3f  tail start %.3f two-phase end %.3f exact end %.3f  walked %.3f ms after the launch's start\n",
+						i, b->launches[(size_t) i].slots_per_lane, b->launches[(size_t) i].n_tiles, b->launch_tail[(size_t) i],
+						ev_ms(le[kLevStart], le[kLevTwoPhase]), ev_ms(le[kLevStart], le[kLevExact]), ev_ms(le[kLevStart], le[kLevTailStart]),
+						ev_ms(le[kLevStart], le[kLevTailTwoPhase]), ev_ms(le[kLevStart], le[kLevTailExact]), ev_ms(le[kLevStart], le[kLevWalked]));
+		}
+	}
 	if (launches == 0) fill_end = ev_ms(b->ev[4], b->ev[2]);
 	b->timing.fill_ms = fill_end;
 	b->timing.backtrack_ms = std::max(0.0f, ev_ms(b->ev[4], b->ev[3]) - fill_end);

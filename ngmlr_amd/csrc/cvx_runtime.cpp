@@ -106,6 +106,9 @@ int ensure_streams(cvx_context *c) {
 	make(&c->s_main2);
 	make(&c->s_post2);
 	for (int i = 0; i < kAuxStreams; ++i) make(&c->aux2[i]);
+	/* the tails of split fill classes (cvx_context::s_tail): one stream at the lowest priority the device has.  Default priority is 0
+	 * and numerically greater is lower: a device that reports no such level gets no stream, and no class of the handle is split */
+	if (e == hipSuccess && c->s_tail == nullptr && c->tail_split != 0 && prio_lo > 0) e = hipStreamCreateWithPriority(&c->s_tail, hipStreamNonBlocking, prio_lo);
 	if (e == hipSuccess) e = hipStreamCreateWithPriority(&c->s_io, hipStreamNonBlocking, prio_hi);
 	if (e != hipSuccess) { set_err("hipStreamCreate failed: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
 	c->streams_ready.store(true, std::memory_order_release);      /* last: the whole set exists */
@@ -290,6 +293,10 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	if (const char *e = getenv("CVX_TUNE_BT_GROUP")) c->bt_group = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_BT_PER_CLASS")) c->bt_per_class = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_OVERLAP_POST")) c->overlap_post = atoi(e) != 0;
+	if (const char *e = getenv("CVX_TUNE_TAIL_SPLIT")) c->tail_split = std::max(0, atoi(e));
+	if (const char *e = getenv("CVX_TUNE_TAIL_ROUNDS")) c->tail_rounds = (float) std::max(0.0, atof(e));
+	if (const char *e = getenv("CVX_TUNE_TAIL_TRACE")) c->tail_trace = atoi(e);
+	if (const char *e = getenv("CVX_TUNE_TAIL_GATE")) c->tail_gate = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_SSE_VARIANT")) c->sse_variant = c->sse_variant || (atoi(e) != 0 && !scalar_twin);   /* test knob */
 	c->force_generic = sem.force_generic || c->sse_variant;
 	c->pack_threads = PackPool::get().size();      /* the process's shared pack threads (CVX_PACK_THREADS) */
@@ -378,6 +385,7 @@ void cvx_destroy(cvx_handle h) {
 	if (h->s_main2) (void) hipStreamDestroy(h->s_main2);
 	if (h->s_post2) (void) hipStreamDestroy(h->s_post2);
 	for (auto &a : h->aux2) if (a) (void) hipStreamDestroy(a);
+	if (h->s_tail) (void) hipStreamDestroy(h->s_tail);
 	for (cvx_batch_s *b : h->pool) { b->release(); delete b; }
 	h->pool.clear();
 	/* jobs the caller never released (submitted, maybe waited for): the device is idle, free them too --
