@@ -30,7 +30,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	constexpr bool GANG = G > 1;
 	static_assert(!GANG || (!WRAP && !CHAIN), "gangs serve whole tiles with float runs");
 	static_assert(!TAB || (!WRAP && MODE == kFillTwoPhase), "the penalty table serves the two-phase float-score instantiation only");
-	/* gap run: float (exact small ints), int16-emulating int, or (TAB) the byte address 4 * run of the run's penalty in s_pen */
+	/* gap run: float (exact small ints), int16-emulating int, or (TAB) the byte address of the run's entry in the penalty table */
 	typedef typename RunT<WRAP || TAB>::type run_t;
 	const int tid = threadIdx.x;           /* = ring slot / M of the thread's first slot */
 	const int lane = GANG ? (tid & 63) : tid;
@@ -67,7 +67,15 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	 * the table has kPenClamp + kPenClampSteps + 1 entries or more whatever the corridor (gap runs through zero-score
 	 * cells are as long as a row is wide).  A gang's wave clamps what it takes from its neighbour's record as well (a
 	 * scalar min): that register was offered one step before the neighbour's own clamp. */
-	__shared__ float s_pen[TAB ? kPenEntries : 1];
+	/* FAST = TAB without a gang (the ring classes of every default handle): the table holds {pen, next} pairs,
+	 * next(e) = kPenPairStride * min(e + 1, kPenClamp), and the run register of the new cell is the second dword of the same
+	 * ds_read_b64 that fetches its penalty, consumed one step later like the penalty.  No add per cell, no periodic clamp, no
+	 * slack entries: an address is always one of kPenPairStride * (1 ... kPenClamp).  The host's condition (penalty constant
+	 * from run kPenClamp on) is what makes the saturating next exact.  The gang form keeps the table above, its clamp and the
+	 * 16-bit run of its boundary record. */
+	constexpr bool FAST = TAB && !GANG;
+	__shared__ float s_pen[TAB && !FAST ? kPenEntries : 1];
+	__shared__ float2 s_pen2[FAST ? kPenPairs : 1];
 
 	int t;                          /* tile */
 	int task_id = 0, y0 = 0;        /* chain: task index, first read row of the block */
@@ -203,7 +211,13 @@ CVX_FILL_KERNEL(const FillArgs a) {
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");      /* one wave: LDS write -> read order across lanes */
 	};
 
-	if (TAB) {
+	if (FAST) {
+		if (lane < kPenPairs) {
+			const int nx = lane + 1 < kPenClamp ? lane + 1 : kPenClamp;
+			s_pen2[lane] = make_float2(fminf(gem, gext + (float) lane * decay), __int_as_float(kPenPairStride * nx));
+		}
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+	} else if (TAB) {
 		for (int i = lane; i < kPenEntries; i += 64) s_pen[i] = fminf(gem, gext + (float) i * decay);
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 	}
@@ -327,7 +341,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 			const unsigned dl = (unsigned) tid * (M * 2);
 #pragma unroll
 			for (int j = 0; j < M; ++j) { d[dl + 2 * j] = accA[j]; d[dl + 2 * j + 1] = accB[j]; }
-			if (TAB) {
+			if (TAB && !FAST) {
 				/* the clamp of the run registers, once per kPenClampSteps steps (one register per slot: the deletion and the
 				 * insertion run of a cell share it in this form) */
 				static_assert(kPenClampSteps == 32, "the run registers are clamped where the direction words are flushed");
@@ -467,7 +481,19 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				run_t nd, ni;
 				float runf = 0.0f;
 				float E;
-				if (TAB) {
+				if (FAST) {
+					/* the registers hold the table address of entry run + 1 -- the {penalty, next address} pair of a cell that
+					 * extends this one -- and the new cell's register comes back with its penalty; as in the float form they are
+					 * only ever read through the masks (isDl, isIu) */
+					const u64 extD = nD & isDl, extI = nI & isIu;
+					const int t1 = lanes(extI) ? (int) uI : kPenPairStride;
+					const int ra = lanes(extD) ? (int) drun[j] : t1;
+					const float2 pn = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(s_pen2) + ra);
+					nd = (run_t) __float_as_int(pn.y);
+					ni = nd;
+					if (LAZY) penp[j] = pn.x;
+					E = fmaxf(sc + pn.x, sc * -0x1p100f);      /* (dead code in the lazy form) */
+				} else if (TAB) {
 					/* the registers hold 4 * (run + 1), the table address of the penalty a cell that extends this one pays
 					 * for; as in the float form they are only ever read through the masks (isDl, isIu) */
 					const u64 extD = nD & isDl, extI = nI & isIu;

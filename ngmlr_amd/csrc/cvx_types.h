@@ -63,6 +63,13 @@ static const int kPenClampSteps = 32;
 static const int kPenEntries = 96;
 static_assert(kPenEntries >= kPenClamp + kPenClampSteps + 1, "the penalty table must cover every run reachable between two clamps");
 static_assert(kPenClamp + kPenClampSteps < 65536, "a gang's boundary record keeps the run in 16 bits");
+/* the same table without a gang (FAST, cvx_fill_ring.inc): entry e holds {penalty of run e, byte address of entry min(e + 1, kPenClamp)},
+ * the run register of a slot is the address it loaded with its penalty -- nothing to clamp, so no slack entries; one lane writes one
+ * entry, and the opening address is that of entry 1 */
+static const int kPenPairs = kPenClamp + 1;
+static const int kPenPairStride = 8;
+static_assert(kPenPairs <= 64, "one lane of the wave writes one {penalty, next} pair");
+static_assert(kPenClamp >= 1, "an opening reads entry 1");
 static const int kGangDepth = 8;       /* fill_ring_kernel<.., G > 1>: steps of lane-boundary records a wave keeps for its successor (> G) */
 static const int kChainChunk = 16;     /* chained row blocks: steps per boundary hand-off (multiple of 4, power of two, <= 64) */
 
