@@ -280,6 +280,11 @@ typedef struct {
 } cvx_regime;
 int cvx_runtime_regime(int device_id, cvx_regime *out);
 int cvx_create_ex(int device_id, const cvx_params *params, uint64_t max_matrix_mb, uint32_t flags, cvx_handle *out);
+/* (additive, ABI 9) Which form of the convex gap penalty the handle's two-phase float-score fills use, decided by cvx_create from
+ * the scoring: 1 = the LDS penalty table (whose one-wave form computes on scores scaled by 2^-64: the scoring's nonzero values and
+ * table penalties have binary exponents in [-20, 20] and the penalty is constant from run 56 on), 0 = the arithmetic form
+ * (any other scoring, or CVX_TUNE_PEN_TABLE=0).  The results are the same either way.  < 0: bad argument. */
+int cvx_handle_pen_table(cvx_handle h);
 void cvx_destroy(cvx_handle h);
 
 /* Synchronous convenience form: upload, run, download.  ops_arena receives the

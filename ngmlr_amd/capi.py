@@ -37,7 +37,8 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_corridor_fit", "cvx_corridor_fit_batch", "cvx_create_ex", "cvx_runtime_regime", "cvx_search_batch_arena",
            "cvx_score_submit", "cvx_score_poll", "cvx_score_wait", "cvx_format_alignment_ex", "cvx_format_batch_ex",
            "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len",
-           "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes")
+           "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes",
+           "cvx_handle_pen_table")
 
 
 class CvxParams(C.Structure):

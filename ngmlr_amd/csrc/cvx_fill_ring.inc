@@ -35,10 +35,20 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	const int tid = threadIdx.x;           /* = ring slot / M of the thread's first slot */
 	const int lane = GANG ? (tid & 63) : tid;
 	const int wv = GANG ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;      /* wave inside the gang */
-	const float go = a.sp.go;
+	/* the forms of the FAST cell update (cvx_kernels.hip has the switches; FAST itself is explained below) */
+	constexpr bool FAST_ = TAB && G == 1;
+	constexpr bool NOMUL = FAST_ && (CVX_CELL_NOMUL != 0);
+	constexpr bool SCALED = FAST_ && (CVX_CELL_CLAMP != 0);
+	/* SCALED: every score of the step loop is the parent form's times kScoreScale = 2^-64, so that the clamp bit of v_max3_f32
+	 * ([0, 1]) is the zero clamp of the cell maximum and nothing else: the largest score, 2^20 a row over 2^31 rows, scales to
+	 * 2^-13.  The scoring values are scaled once, here (the table's penalties below, computed unscaled first); the host admits
+	 * only scorings whose nonzero values have binary exponents in [-20, 20] (score_scale_exact, cvx_host_logic.h), every score
+	 * is then a multiple of 2^-43 and its scaled value is zero or normal, and binary32 +, max, negation and compares commute
+	 * with the scaling.  best[] and lbest are multiplied back before the argmax; kFillExact stays unscaled. */
+	const float go = SCALED ? a.sp.go * kScoreScale : a.sp.go;
 	const float gext = a.sp.ge, gem = a.sp.gem, decay = a.sp.decay;
 	/* keep match / mismatch in VGPRs: v_cndmask cannot take two SGPR values plus a mask */
-	float vmat = a.sp.mat, vmis = a.sp.mis;
+	float vmat = SCALED ? a.sp.mat * kScoreScale : a.sp.mat, vmis = SCALED ? a.sp.mis * kScoreScale : a.sp.mis;
 	asm volatile("" : "+v"(vmat), "+v"(vmis));
 
 	/* The row a slot takes over next is a 16-byte record in LDS, written 16*M rows at a time by the whole
@@ -74,6 +84,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	 * from run kPenClamp on) is what makes the saturating next exact.  The gang form keeps the table above, its clamp and the
 	 * 16-bit run of its boundary record. */
 	constexpr bool FAST = TAB && !GANG;
+	static_assert(FAST == FAST_, "one definition of the FAST form");
 	__shared__ float s_pen[TAB && !FAST ? kPenEntries : 1];
 	__shared__ float2 s_pen2[FAST ? kPenPairs : 1];
 
@@ -214,7 +225,8 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	if (FAST) {
 		if (lane < kPenPairs) {
 			const int nx = lane + 1 < kPenClamp ? lane + 1 : kPenClamp;
-			s_pen2[lane] = make_float2(fminf(gem, gext + (float) lane * decay), __int_as_float(kPenPairStride * nx));
+			const float pen = fminf(gem, gext + (float) lane * decay);
+			s_pen2[lane] = make_float2(SCALED ? pen * kScoreScale : pen, __int_as_float(kPenPairStride * nx));
 		}
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
 	} else if (TAB) {
@@ -325,7 +337,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 		}
 		/* this group's reference characters were fetched one group ago */
 		unsigned cw[M];
-		const float misx = TWIN ? a.sp.misx : 0.0f;      /* (handed to phase1 as an argument: one more capture and hipcc no longer unrolls the step loop) */
+		const float misx = TWIN ? (SCALED ? a.sp.misx * kScoreScale : a.sp.misx) : 0.0f;      /* (handed to phase1 as an argument: one more capture and hipcc no longer unrolls the step loop) */
 #pragma unroll
 		for (int j = 0; j < M; ++j) {
 			cw[j] = cwn[j];
@@ -357,7 +369,9 @@ CVX_FILL_KERNEL(const FillArgs a) {
 			 * step after the cell, from its score, the penalty that has come back from LDS meanwhile and its two masks) */
 			float p_E[M], p_O[M];
 			auto offers = [&](const int j) {
-				p_E[j] = fmaxf(S[j] + penp[j], S[j] * -0x1p100f);
+				/* NOMUL: -S for the product.  Either is +-0 exactly when S is zero and negative otherwise, and an offer is only read
+				 * through the maximum with zero and the equality with that maximum */
+				p_E[j] = NOMUL ? fmaxf(S[j] + penp[j], -S[j]) : fmaxf(S[j] + penp[j], S[j] * -0x1p100f);
 				p_O[j] = S[j] + go;
 			};
 			if (LAZY) offers(M - 1);
@@ -448,7 +462,9 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				if (TWIN) mv = lanes(ballot(refc == 'x')) ? misx_ : vmis;
 				const float diag_cell = dg[j] + (eq ? vmat : mv);
 				float lc = lcv, dc = diag_cell, uc = uV;
-				const float mx = fmaxf(fmaxf(fmaxf(lc, dc), uc), 0.0f);
+				/* SCALED: one v_max3_f32 with the clamp bit.  The sign of a zero result is the instruction's; it is not observable: a
+				 * zero is never positive and enters compares only as equal to zero */
+				const float mx = SCALED ? __builtin_amdgcn_fmed3f(fmaxf(fmaxf(lc, dc), uc), 0.0f, 1.0f) : fmaxf(fmaxf(fmaxf(lc, dc), uc), 0.0f);
 				p_lc[j] = lc; p_dc[j] = dc; p_uc[j] = uc; p_mx[j] = mx;
 				p_eL[j] = ballot(mx == lc);
 				p_eU[j] = ballot(mx == uc);
@@ -633,13 +649,13 @@ CVX_FILL_KERNEL(const FillArgs a) {
 		int vy = s_besty[j][tid];
 		const int ycur = (int) (ref_base - (xa[j] - (unsigned) r - 4u));      /* the row the slot holds now */
 		if (ycur < H && best_r[j] >= r - cnt[j]) vy = ycur;
-		const float v = best[j];
+		const float v = SCALED ? best[j] * kScoreUnscale : best[j];      /* (best[] is +0 or positive) */
 		const int vx = best_r[j] - vy;
 		if (v > 0.0f) {     /* best[] starts at 0: a slot that never saw a positive score has no candidate */
 			if (v > b || (v == b && (vy < by || (vy == by && vx < bx)))) { b = v; by = vy; bx = vx; }
 		}
 	}
-	float be = lbest;       /* maximum over the cells that were not tracked exactly */
+	float be = SCALED ? lbest * kScoreUnscale : lbest;       /* maximum over the cells that were not tracked exactly */
 #pragma unroll
 	for (int off = 32; off >= 1; off >>= 1) {
 		const float ob = __shfl_xor(b, off, 64);

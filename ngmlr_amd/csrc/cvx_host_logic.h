@@ -770,6 +770,32 @@ inline float twin_mismatch_x(const float mismatch) {
 	return r;
 }
 
+/* The FAST ring fill (cvx_fill_ring.inc) runs on scores scaled by kScoreScale = 2^-64 so that the clamp bit of v_max3_f32 is the
+ * zero clamp of a cell's maximum.  Scaling by a power of two commutes with binary32 +, max, negation and compares as long as
+ * nothing overflows, underflows or goes subnormal.  That holds when every nonzero value the fill adds -- match, mismatch, the
+ * twin's 'x' mismatch (pass 0 for a default handle), gap open and the kPenPairs penalties of the table -- is finite with a binary
+ * exponent in [-kScoreExpMax, kScoreExpMax]: every score is then a multiple of 2^-43 (induction over the adds; rounding only
+ * coarsens the grid), so a nonzero scaled score is at least 2^-107 in magnitude, which is normal, and the largest score, 2^20 a row
+ * over 2^31 rows, scales to 2^-13 <= 1.  The penalties are computed with the operations of cvx_create's table check.  A scoring
+ * that fails runs the arithmetic form (tune_pen_table = 0), which is unscaled. */
+inline bool score_scale_value_ok(const float v) {
+	if (v == 0.0f) return true;
+	if (!std::isfinite(v)) return false;
+	const int e = std::ilogb(v);      /* (a subnormal's is below -126) */
+	return e >= -kScoreExpMax && e <= kScoreExpMax;
+}
+inline bool score_scale_exact(const float match, const float mismatch, const float mismatch_x, const float gap_open,
+                              const float gap_extend, const float gap_extend_min, const float gap_decay) {
+	if (!score_scale_value_ok(match) || !score_scale_value_ok(mismatch) || !score_scale_value_ok(mismatch_x) || !score_scale_value_ok(gap_open)) return false;
+	for (int run = 0; run < kPenPairs; ++run) {
+		volatile float prod = (float) run * gap_decay;
+		volatile float sum = gap_extend + prod;
+		volatile float pen = std::fmin(gap_extend_min, (float) sum);
+		if (!score_scale_value_ok(pen)) return false;
+	}
+	return true;
+}
+
 /* Kernel class, arena offsets and (sorted) work lists of every tile from its corridor plan.
  * tune: the CVX_TUNE_* knobs of the runtime. */
 /* tuning / test knobs of the runtime (CVX_TUNE_* environment variables; all 0 = off) */

@@ -465,6 +465,17 @@ template <bool B> struct BoolTag { static constexpr bool value = B; };
 #define CVX_FILL_PRIO 1
 #endif
 
+/* The cell update of the FAST form (TAB without a gang: cvx_fill_ring.inc), two switches for A/B builds (tools/build_variant.sh):
+ *   CVX_CELL_NOMUL   the gap-extension offer as max(S + pen, -S) instead of max(S + pen, S * -2^100): no multiply
+ *   CVX_CELL_CLAMP   the zero clamp of a cell's maximum as the clamp bit of v_max3_f32, on scores scaled by kScoreScale
+ * DESIGN.md 5 has what each is worth, and the two forms of folding a lane rotate into its consumer that were measured and left out. */
+#ifndef CVX_CELL_NOMUL
+#define CVX_CELL_NOMUL 1
+#endif
+#ifndef CVX_CELL_CLAMP
+#define CVX_CELL_CLAMP 1
+#endif
+
 /* What a cell that extends a gap offers: src/ConvexAlignFast.cpp:669-675, E = (score == 0) ? 0 : score + pen with
  * pen = min(gap_ext_min, gap_ext + run * decay).  score >= 0 and pen < 0, so this is max(score + pen, score * -2^100):
  * -0 for score 0 (compares equal to the reference's +0 and never reaches an output), score + pen otherwise.  One

@@ -312,6 +312,10 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 		volatile float at_clamp = p->gap_extend + prod;
 		const bool reached = !(at_clamp < p->gap_extend_min);
 		if (!(p->gap_decay >= 0.0f) || !(reached || p->gap_decay == 0.0f)) c->tune_pen_table = 0;
+		/* the table form without a gang computes on scores scaled by 2^-64 (the clamp bit of its v_max3_f32 is the cell's zero
+		 * clamp); a scoring whose values could leave the range in which that is exact keeps the arithmetic form as well */
+		if (!score_scale_exact(p->match, p->mismatch, scalar_twin ? c->sp.misx : 0.0f, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay))
+			c->tune_pen_table = 0;
 	}
 	if (const char *e = getenv("CVX_TUNE_FAIL_COMPUTE")) c->test_fail_compute = atoi(e);
 	if (const char *e = getenv("CVX_TUNE_SCORE_NO_DIAG")) c->score_no_diag = atoi(e) != 0;
@@ -368,6 +372,13 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	}
 	*out = c;
 	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_handle_pen_table(cvx_handle h) {
+	ABI_GUARD_BEGIN
+	if (!h) { set_err("cvx_handle_pen_table: NULL handle"); return CVX_ERR_ARG; }
+	return h->tune_pen_table ? 1 : 0;
 	ABI_GUARD_END
 }
 

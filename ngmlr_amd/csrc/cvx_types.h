@@ -70,7 +70,13 @@ static const int kPenPairs = kPenClamp + 1;
 static const int kPenPairStride = 8;
 static_assert(kPenPairs <= 64, "one lane of the wave writes one {penalty, next} pair");
 static_assert(kPenClamp >= 1, "an opening reads entry 1");
-static const int kGangDepth = 8;       /* fill_ring_kernel<.., G > 1>: steps of lane-boundary records a wave keeps for its successor (> G) */
+/* FAST with the zero clamp of the cell maximum as the clamp bit of v_max3_f32 (clamps to [0, 1]): the fill runs on scores scaled
+ * by kScoreScale, a power of two, and multiplies its results back (cvx_fill_ring.inc; the host's condition is
+ * score_scale_exact(), cvx_host_logic.h).  kScoreExpMax: the binary exponents the nonzero scoring values may have. */
+static const float kScoreScale = 0x1p-64f;
+static const float kScoreUnscale = 0x1p64f;
+static const int kScoreExpMax = 20;
+static const int kGangDepth = 8;      /* fill_ring_kernel<.., G > 1>: steps of lane-boundary records a wave keeps for its successor (> G) */
 static const int kChainChunk = 16;     /* chained row blocks: steps per boundary hand-off (multiple of 4, power of two, <= 64) */
 
 struct ScoreParams {
