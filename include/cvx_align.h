@@ -35,6 +35,7 @@
  * cvx_job_nm_profile          addPosition / nmPerPosition    src/ConvexAlignFast.cpp:76-98,186-269, on the device
  * cvx_job_nm_regions / cvx_nm_regions_ops / cvx_nm_regions_host  the peak finder over that profile at the top of
  *                             detectMisalignment  src/AlignmentBuffer.cpp:1143-1148,1316-1395 (device: no profile leaves HBM)
+ * CVX_CREATE_NM_REGIONS / cvx_job_regions  the same regions delivered with a job's results: no text stage, no round trip
  * cvx_sam_record_text / cvx_sam_batch  SAMWriter::DoWriteReadGeneric  src/SAMWriter.cpp:87-224 (f3: SAM record assembly)
  * cvx_sam_unmapped_text       SAMWriter::DoWriteUnmappedReadGeneric  src/SAMWriter.cpp:308-357
  * cvx_score_batch             StrippedSW::BatchScore/SingleScore  src/StrippedSW.cpp:118-203 (next-row f2)
@@ -245,7 +246,12 @@ int cvx_create(int device_id, const cvx_params *params, uint64_t max_matrix_mb, 
  * cvx_genome_decode) from a thread that blocks in them -- its stream gets the device's highest priority, so that a 0.3 ms scoring
  * kernel does not queue behind a 10 ms fill of an aligning handle in the same process.  MEASURED AND OFF: inside ngmlr the run got
  * slower with it (profiles/r06_e2e_service_prio.txt); the flag is recorded in the handle, the priority applies only with CVX_SERVICE_PRIO=1. */
-enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2 };
+enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2, CVX_CREATE_NM_REGIONS = 4 };
+/* CVX_CREATE_NM_REGIONS (additive, ABI 9): every job of the handle finds the low-identity regions of its tiles' NM profile
+ * (cvx_nm_region below) on the device, behind its op compaction on the job's own stream, and delivers them with its results:
+ * cvx_job_regions after cvx_wait, no text stage, no extra round trip, no profile anywhere.  Combines with CVX_CREATE_SCALAR_TWIN;
+ * refused (CVX_ERR_ARG) together with CVX_CREATE_SERVICE.  A handle without the flag launches, allocates and returns what it
+ * always did. */
 /* CVX_CREATE_SCALAR_TWIN (additive, ABI 9): the handle reproduces Convex::ConvexAlign, the scalar aligner ngmlr's --nosse selects
  * (src/ConvexAlign.cpp:418-610, bound at src/AlignmentBuffer.h:345-353), instead of Convex::ConvexAlignFast:
  *   - the scalar recurrence for ANY scoring (a default handle reproduces the SSE path, which differs from it outside
@@ -753,9 +759,21 @@ typedef struct {
  * job).  region_off[count + 1]: tile first + i owns (*regions)[region_off[i] .. region_off[i + 1]); a tile without a
  * valid alignment owns none.  *regions points at page-locked memory owned by the job, valid until the next call of this
  * entry on the job or cvx_job_release.  open (may be NULL): count records, the end state of every tile's scan.
- * *kernel_ms (may be NULL): the kernels' own duration (both passes and the offset scan). */
+ * *kernel_ms (may be NULL): the kernels' own duration (both passes and the offset scan).
+ * (Two synchronous round trips on the text stream, and only behind the device text stage.  A pipeline that formats its text on
+ * the host takes the job form instead: CVX_CREATE_NM_REGIONS + cvx_job_regions below.) */
 int cvx_job_nm_regions(cvx_handle h, cvx_job job, int32_t first, int32_t count, uint64_t *region_off,
 		const cvx_nm_region **regions, cvx_nm_open *open, double *kernel_ms);
+/* The job form (additive, ABI 9): the regions of ALL tiles of a job of a CVX_CREATE_NM_REGIONS handle, as they came back with the
+ * job's results -- valid after cvx_wait and before cvx_job_release, no device call of its own.  (*region_off)[n_tiles + 1], tile i
+ * owns (*regions)[(*region_off)[i] .. (*region_off)[i + 1]); a tile without a valid alignment owns none.  (*open)[n_tiles]: the end
+ * state of every tile's scan.  All three point at page-locked memory the job owns (any of the three arguments may be NULL).
+ * CVX_ERR_ARG, with a message, on a handle created without the flag and on a job cvx_wait has not returned for.
+ * The device writes the regions into an arena sized by an estimate (eight regions per tile); a job with more runs the write again
+ * over a larger arena while its ops are downloaded -- cvx_job_regions_info tells: *total the regions of the job, *first_capacity
+ * the regions the arena held when the write first ran, *rewrites how often it ran again (each may be NULL). */
+int cvx_job_regions(cvx_handle h, cvx_job job, const uint64_t **region_off, const cvx_nm_region **regions, const cvx_nm_open **open);
+int cvx_job_regions_info(cvx_handle h, cvx_job job, uint64_t *total, uint64_t *first_capacity, int32_t *rewrites);
 /* The same kernel over op lists the caller holds (the twin of cvx_nm_profile_ops).  regions: room for cap_regions
  * (CVX_ERR_CAPACITY, with region_off and open filled in, when that is too little) -- or NULL: sizes (and open) only.
  * CVX_ERR_ARG for ops outside the arena. */

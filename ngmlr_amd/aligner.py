@@ -23,18 +23,23 @@ DEFAULT_SCORING = dict(match=2.0, mismatch=-5.0, gap_open=-5.0, gap_extend=-5.0,
 
 
 class ConvexAlignHip:
-    def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, scalar_twin: bool = False, **scoring):
+    def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, scalar_twin: bool = False,
+                 nm_regions: bool = False, **scoring):
         """scalar_twin: the handle reproduces Convex::ConvexAlign (ngmlr --nosse) instead of Convex::ConvexAlignFast
-        (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h); the host text helpers of its batches follow."""
+        (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h); the host text helpers of its batches follow.
+        nm_regions: every job delivers the low-identity regions of its tiles with its results (CVX_CREATE_NM_REGIONS,
+        Job.regions)."""
         self.lib = capi.load(lib_path)
         self.scalar_twin = bool(scalar_twin)
+        self.nm_regions = bool(nm_regions)
         sc = dict(DEFAULT_SCORING)
         sc.update(scoring)
         self.params = capi.CvxParams(sc["match"], sc["mismatch"], sc["gap_open"], sc["gap_extend"],
                                      sc["gap_extend_min"], sc["gap_decay"])
         self.h = C.c_void_p()
-        if self.scalar_twin:
-            capi.check(self.lib.cvx_create_ex(device, C.byref(self.params), max_matrix_mb, capi.CREATE_SCALAR_TWIN, C.byref(self.h)))
+        flags = (capi.CREATE_SCALAR_TWIN if self.scalar_twin else 0) | (capi.CREATE_NM_REGIONS if self.nm_regions else 0)
+        if flags:
+            capi.check(self.lib.cvx_create_ex(device, C.byref(self.params), max_matrix_mb, flags, C.byref(self.h)))
         else:
             capi.check(self.lib.cvx_create(device, C.byref(self.params), max_matrix_mb, C.byref(self.h)))
 
@@ -366,6 +371,27 @@ class Job:
         n = int(off[count]) if count > 0 else 0
         reg = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_int32)), shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), dtype=np.int32)
         return off, reg, opn, ms.value
+
+    def regions(self):
+        """cvx_job_regions (a ConvexAlignHip(nm_regions=True) job, after wait()): the same regions of every tile as they came
+        back with the job's results -- no text stage and no device call.
+        -> (offsets uint64[n + 1], regions int32[r, 4], open records NM_OPEN_DTYPE[n]), copied out of the job's memory"""
+        po, pr, pn = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        capi.check(self.al.lib.cvx_job_regions(self.al.h, self.j, C.byref(po), C.byref(pr), C.byref(pn)))
+        n = self.n
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        r = int(off[n])
+        reg = np.ctypeslib.as_array(C.cast(pr, C.POINTER(C.c_int32)), shape=(r * 4,)).reshape(r, 4).copy() if r else np.zeros((0, 4), dtype=np.int32)
+        opn = (np.ctypeslib.as_array(C.cast(pn, C.POINTER(C.c_uint8)), shape=(n * NM_OPEN_DTYPE.itemsize,)).view(NM_OPEN_DTYPE).copy()
+               if n else np.zeros(0, dtype=NM_OPEN_DTYPE))
+        return off, reg, opn
+
+    def regions_info(self) -> dict:
+        """cvx_job_regions_info: regions of the job, regions the arena held when the device first wrote them, and how often
+        the write ran again over a larger arena."""
+        total, cap, again = C.c_uint64(), C.c_uint64(), C.c_int32()
+        capi.check(self.al.lib.cvx_job_regions_info(self.al.h, self.j, C.byref(total), C.byref(cap), C.byref(again)))
+        return {"total": int(total.value), "first_capacity": int(cap.value), "rewrites": int(again.value)}
 
     def release(self) -> None:
         if self.j:

@@ -222,7 +222,7 @@ void BatchingAligner::dispatchLoop() {
 		bool const canSubmit = (int) inFlight.size() < maxFlight && textPending < maxTextAhead;
 		if (canSubmit && shouldCut(inFlight.empty())) {
 			Launch * l = new Launch();
-			l->job = 0; l->results = 0; l->ops = 0; l->failed = false; l->text = 0; l->submitMs = l->waitMs = 0.0;
+			l->job = 0; l->results = 0; l->ops = 0; l->failed = false; l->text = 0; l->haveRegions = false; l->submitMs = l->waitMs = 0.0;
 			size_t const take = std::min(queue.size(), (size_t) maxBatch);
 			l->oldestAt = oldest;
 			l->cutAt = std::chrono::steady_clock::now();
@@ -269,6 +269,7 @@ void BatchingAligner::dispatchLoop() {
 				try {
 					std::chrono::steady_clock::time_point const tw = std::chrono::steady_clock::now();
 					backend->Wait(l->job, &l->results, &l->ops);
+					l->haveRegions = !deviceText && backend->Regions(l->job, l->regions);      /* (they came back inside that wait) */
 					if (launchTrace) {
 						std::chrono::steady_clock::time_point const t = std::chrono::steady_clock::now();
 						l->waitMs = std::chrono::duration<double, std::milli>(t - tw).count();
@@ -364,7 +365,7 @@ int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int co
 	if (!failed) {
 		try {
 			if (l->text) backend->FinishText(req.tile, *r, *l->text, (int) (r - l->results));
-			else backend->Finish(req.tile, *r, ops);
+			else backend->Finish(req.tile, *r, ops, l->haveRegions ? &l->regions : 0, (int) (r - l->results));
 		} catch (...) {
 			threw = true;
 		}
@@ -441,7 +442,8 @@ SharedAligner::SharedAligner(int const stdOutMode, float const match, float cons
 		int maxBatch = 4096, timeoutUs = 2000;
 		if (const char * e = getenv("CVX_BATCH_MAX")) maxBatch = atoi(e);
 		if (const char * e = getenv("CVX_BATCH_TIMEOUT_US")) timeoutUs = atoi(e);
-		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device, 0, scalarTwin);   /* throws without a usable device */
+		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device, 0, scalarTwin,
+				DeviceRegions::Enabled());   /* throws without a usable device; the regions of every launch come back with its results where a binding reads them */
 		g_shared[device] = new BatchingAligner(g_backend[device], 0, maxBatch, timeoutUs);   /* workers join one by one */
 		/* with alignment contexts off the CS threads (align_pool.h) a launch waits for 256 tiles, 30 ms at most: hundreds of
 		 * contexts hide that wait, and the device sees a few large launches instead of many small ones (CVX_BATCH_TARGET /
@@ -495,6 +497,11 @@ SharedAligner::~SharedAligner() {
 			long rl = 0, rt = 0, rm = 0;
 			ConvexAlignHip::ReadStats(rl, rt, rm);
 			if (rl + rm > 0) fprintf(stderr, "SharedAligner: %ld tiles in %ld launches took their query as a segment of the launch's read block (cvx_submit_segments; CVX_DEVICE_READS=0 turns that off), %ld mixed launches materialised theirs\n", rt, rl, rm);
+		}
+		{
+			long na = 0, nr = 0, np = 0;
+			DeviceRegions::Stats(na, nr, np);
+			if (na + np > 0) fprintf(stderr, "SharedAligner: %ld alignments handed detectMisalignment %ld regions from the device, %ld their profile (CVX_DEVICE_REGIONS=0 turns that off)\n", na, nr, np);
 		}
 		if (g_lastTextLaunches > 0) fprintf(stderr, "SharedAligner: text stage on the device for %ld launches (cvx_job_text + cvx_job_nm_profile), %.3f s of the dispatchers' time\n", g_lastTextLaunches, g_lastTextSeconds);
 		fprintf(stderr, "SharedAligner: library loaded at 0, first worker joined at %.2f s, last one left at %.2f s\n",

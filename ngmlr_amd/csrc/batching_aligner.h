@@ -116,6 +116,8 @@ private:
 		int unfinished;                    /* workers still writing their text out of this launch's buffers */
 		bool failed;
 		ConvexAlignHip::JobText * text;    /* CVX_DEVICE_TEXT=1: the launch's text stage ran on the device (else 0) */
+		ConvexAlignHip::JobRegions regions; /* a backend with NmRegions(): the launch's regions, for the requests among its tiles (Finish) */
+		bool haveRegions;
 	};
 	ConvexAlignHip * backend;
 	std::mutex mtx;

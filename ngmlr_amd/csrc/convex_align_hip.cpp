@@ -5,6 +5,7 @@
  */
 #include "convex_align_hip.h"
 #include "cvx_fiber.h"
+#include "nm_regions_note.h"
 
 #include <atomic>
 #include <cstdio>
@@ -150,6 +151,26 @@ void DeviceReads::CopyOut(char * dst, char const * src, int offset, int n) {
 	}
 }
 
+/* ------------------------------------------------------------------ DeviceRegions */
+namespace {
+std::atomic<bool> g_regionsAnnounced(false);
+std::atomic<long> g_noteAlignments(0), g_noteRegions(0), g_profileAlignments(0);
+bool const g_deviceRegions = [] { const char * e = getenv("CVX_DEVICE_REGIONS"); return !(e && atoi(e) == 0); }();
+}
+
+void DeviceRegions::Announce() { g_regionsAnnounced.store(true); }
+bool DeviceRegions::Enabled() { return g_deviceRegions && g_regionsAnnounced.load(); }
+void DeviceRegions::CountNote(int regions) {
+	g_noteAlignments.fetch_add(1, std::memory_order_relaxed);
+	g_noteRegions.fetch_add(regions, std::memory_order_relaxed);
+}
+void DeviceRegions::CountProfile() { g_profileAlignments.fetch_add(1, std::memory_order_relaxed); }
+void DeviceRegions::Stats(long & noteAlignments, long & noteRegions, long & profileAlignments) {
+	noteAlignments = g_noteAlignments.load();
+	noteRegions = g_noteRegions.load();
+	profileAlignments = g_profileAlignments.load();
+}
+
 void ConvexAlignHip::ReadStats(long & notedLaunches, long & notedTiles, long & mixedLaunches) {
 	notedLaunches = g_notedLaunches.load();
 	notedTiles = g_notedTiles.load();
@@ -169,7 +190,7 @@ void ConvexAlignHip::CorridorStats(long & prepared, long & closedForm) {
 
 ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float const mismatch,
 		float const gapOpen, float const gapExtend, float const gapExtendMin, float const gapDecay,
-		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin) : handle(0), twin(scalarTwin), genome(0) {
+		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin, bool const nmRegions) : handle(0), twin(scalarTwin), regions(nmRegions), genome(0) {
 	(void) stdOutMode;
 	cvx_params p;
 	p.match = match; p.mismatch = mismatch; p.gap_open = gapOpen;
@@ -179,7 +200,8 @@ ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float co
 	if (maxMatrixMB == 0) maxMatrixMB = (unsigned long) Config.getMaxMatrixSizeMB();
 #endif
 	if (maxMatrixMB == 0) maxMatrixMB = 10000;      /* IConfig's default (src/IConfig.h:47) */
-	if (cvx_create_ex(deviceId, &p, (uint64_t) maxMatrixMB, twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u, &handle) != CVX_OK) {
+	uint32_t const flags = (twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u) | (regions ? (uint32_t) CVX_CREATE_NM_REGIONS : 0u);
+	if (cvx_create_ex(deviceId, &p, (uint64_t) maxMatrixMB, flags, &handle) != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
 		throw "ConvexAlignHip: no usable MI355X / unsupported scoring";
 	}
@@ -408,6 +430,17 @@ void ConvexAlignHip::Wait(cvx_job job, cvx_result const ** results, uint32_t con
 	}
 }
 
+bool ConvexAlignHip::Regions(cvx_job job, JobRegions & jr) {
+	jr.off = 0; jr.regions = 0;
+	if (!regions) return false;
+	if (cvx_job_regions(handle, job, &jr.off, &jr.regions, 0) != CVX_OK) {
+		/* a request must never be answered with nothing: fail the launch like any other error of it */
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	return true;
+}
+
 bool ConvexAlignHip::WindowRefs(cvx_job job, Tile * const * tiles, int n) {
 	int nWindows = 0;
 	for (int i = 0; i < n; ++i) nWindows += tiles[i]->window ? 1 : 0;
@@ -458,15 +491,18 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 	std::vector<char const *> callers((size_t) n);
 	std::vector<Tile *> ptrs((size_t) n);
 	for (int i = 0; i < n; ++i) { callers[(size_t) i] = tiles[i].refSeq; ptrs[(size_t) i] = &tiles[i]; }
+	JobRegions jr;
+	bool haveRegions = false;
 	try {
 		(void) WindowRefs(job, ptrs.data(), n);
+		haveRegions = Regions(job, jr);
 	} catch (...) {
 		Release(job);
 		throw;
 	}
 	for (int i = 0; i < n; ++i) {
 		try {
-			Finish(tiles[i], res[i], ops);
+			Finish(tiles[i], res[i], ops, haveRegions ? &jr : 0, i);
 		} catch (...) {
 			/* this tile's own hard error: the caller drops this alignment and no other (src/AlignmentBuffer.cpp:454-463) */
 			tiles[i].failed = true;
@@ -479,15 +515,22 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 }
 
 /* convertCigar + flags into the caller's Align (src/ConvexAlignFast.cpp:488-539) */
-void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops) const {
+void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr, int index) const {
 	Align & a = *t.result;
 	int const refLen = t.refLen, qryLen = t.qryLen;
-	if (noAlignment(t, r)) return;
+	if (noAlignment(t, r)) return;      /* (a request stays where it is for the caller's retry) */
+	/* nm_regions_note.h: the caller asked for regions.  With the job's regions at hand the text is formatted without a profile
+	 * (nm_triples = NULL counts the entries and writes none) and the note goes where the profile would have gone; without them
+	 * the request -- or the note an earlier call left -- is cleared and the profile is written as always */
+	bool const asNote = jr != 0 && jr->off != 0 && NmRegionsNote::Begin(a.nmPerPosition, a.nmPerPostionLength, true);
+	/* (the request's buffer is a few dozen rows, and the finder's loop scans alignmentLength rows of a profile: the buffer becomes
+	 * the one the caller allocates when it does not ask, and covers alignmentLength below) */
+	bool const fromRequest = !asNote && NmRegionsNote::BeginProfile(a.nmPerPosition, a.nmPerPostionLength, qryLen);
 	cvx_alignment_text txt;
 	for (;;) {
 		int rc = cvx_format_alignment_ex(&r, ops, t.refSeq, refLen, qryLen, t.externalQStart,
 				t.externalQEnd, a.pBuffer1, a.maxBufferLength, a.pBuffer2, a.maxMdBufferLength,
-				(int32_t *) a.nmPerPosition, a.nmPerPostionLength, twin ? (uint32_t) CVX_FORMAT_SCALAR_TWIN : 0u, &txt);
+				asNote ? (int32_t *) 0 : (int32_t *) a.nmPerPosition, asNote ? 0 : a.nmPerPostionLength, twin ? (uint32_t) CVX_FORMAT_SCALAR_TWIN : 0u, &txt);
 		if (rc != CVX_OK) throw 1;
 		bool again = false;
 		if (txt.md_len >= a.maxMdBufferLength) {       /* checkMdBufferLength: grow with new[] */
@@ -498,7 +541,7 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 			a.maxMdBufferLength = cap;
 			again = true;
 		}
-		if (txt.nm_count > a.nmPerPostionLength) {      /* addPosition: grow with new[] */
+		if (!asNote && txt.nm_count > a.nmPerPostionLength) {      /* addPosition: grow with new[] */
 			int cap = a.nmPerPostionLength > 0 ? a.nmPerPostionLength : 64;
 			while (cap < txt.nm_count) cap *= 2;
 			delete[] a.nmPerPosition;
@@ -507,6 +550,13 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 			again = true;
 		}
 		if (!again) break;
+	}
+	if (fromRequest) NmRegionsNote::CoverScan(a.nmPerPosition, a.nmPerPostionLength, txt.nm_count, txt.alignment_length);
+	if (asNote) {
+		static_assert(sizeof(NmRegionsNote::Region) == sizeof(cvx_nm_region), "a note holds cvx_nm_region records");
+		int const count = (int) (jr->off[index + 1] - jr->off[index]);
+		NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr->regions + jr->off[index]) : 0;
+		NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
 	}
 	if (txt.cigar_len > a.maxBufferLength) {
 		fprintf(stderr, "CIGAR/MD buffer not long enough (%d %d > %d %d). Please report this!\n",
@@ -579,6 +629,8 @@ void ConvexAlignHip::Text(cvx_job job, Tile const * const * tiles, int n, JobTex
 void ConvexAlignHip::FinishText(Tile & t, cvx_result const & r, JobText const & jt, int index) const {
 	if (noAlignment(t, r)) return;
 	Align & a = *t.result;
+	/* this path has no regions: a request ends as the profile, in a buffer as long as the caller's own would have been */
+	bool const fromRequest = NmRegionsNote::BeginProfile(a.nmPerPosition, a.nmPerPostionLength, t.qryLen);
 	cvx_alignment_text const & txt = jt.out[(size_t) index];
 	if (txt.md_len >= a.maxMdBufferLength) {       /* checkMdBufferLength: grow with new[] */
 		int cap = a.maxMdBufferLength > 0 ? a.maxMdBufferLength : 64;
@@ -608,6 +660,7 @@ void ConvexAlignHip::FinishText(Tile & t, cvx_result const & r, JobText const & 
 		throw 1;
 	}
 	if (e1 > e0) memcpy((void *) a.nmPerPosition, jt.nm + 3 * e0, (size_t) (e1 - e0) * 3 * sizeof(int32_t));
+	if (fromRequest) NmRegionsNote::CoverScan(a.nmPerPosition, a.nmPerPostionLength, txt.nm_count, txt.alignment_length);
 	fillAlign(t, txt);
 }
 

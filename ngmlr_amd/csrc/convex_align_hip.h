@@ -32,7 +32,11 @@ public:
 	ConvexAlignHip(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = 0,
 			unsigned long const maxMatrixSizeMB = 0 /* Config.getMaxMatrixSizeMB(); 0 = the reference's default 10000 */,
-			bool const scalarTwin = false);
+			bool const scalarTwin = false, bool const nmRegions = false);
+	/* nmRegions: the handle is created with CVX_CREATE_NM_REGIONS -- every launch brings the low-identity regions of its tiles back
+	 * with its results, and Finish answers a request in Align::nmPerPosition (nm_regions_note.h) with a note of them instead of
+	 * the profile.  Without it (and on the CVX_DEVICE_TEXT=1 path) a request ends as the full profile. */
+	bool NmRegions() const { return regions; }
 	/* scalarTwin: the drop-in takes the place of Convex::ConvexAlign, the scalar aligner ngmlr's --nosse binds at
 	 * src/AlignmentBuffer.h:345-353, instead of ConvexAlignFast's (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h).  In that mode
 	 * SingleAlign / AlignTiles leave Align::svType and Align::cigarOpCount exactly as the caller passed them -- no clear at entry,
@@ -101,7 +105,16 @@ public:
 	cvx_job Submit(Tile const * tiles, int n);
 	bool Poll(cvx_job job);       /* true: Wait would not block (also keeps queued launches moving) */
 	void Wait(cvx_job job, cvx_result const ** results, uint32_t const ** ops);
-	void Finish(Tile & t, cvx_result const & r, uint32_t const * ops) const;
+	/* the regions of a finished job (cvx_job_regions: the job's page-locked memory, valid until Release); tile i owns
+	 * regions[off[i] .. off[i + 1]) */
+	struct JobRegions {
+		uint64_t const * off;
+		cvx_nm_region const * regions;
+	};
+	bool Regions(cvx_job job, JobRegions & jr);      /* after Wait.  false: the handle delivers none (throws 1 when one that should cannot) */
+	/* jr / index: the launch's regions and the tile's place in it.  With them a request (or an earlier note) in
+	 * Align::nmPerPosition is answered with a note and no profile is written; without them it ends as the profile */
+	void Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr = 0, int index = 0) const;
 	void Release(cvx_job job);
 	/* one line on stderr about a finished job: tiles, device stages, fill classes (CVX_LAUNCH_TRACE=1 in the dispatcher) */
 	void Trace(cvx_job job, int nTiles, double serviceMs, double waitedMs) const;
@@ -136,6 +149,7 @@ private:
 	bool noAlignment(Tile & t, cvx_result const & r) const;
 	cvx_handle handle;
 	bool twin;
+	bool regions;
 	unsigned long maxMatrixMB;
 	std::vector<cvx_tile> packed;
 	cvx_genome genome;                     /* DeviceWindows' genome on this aligner's device (uploaded by the first launch that carries a window) */
@@ -201,6 +215,24 @@ struct DeviceReads {
 	/* strncpy(dst, src + offset, n) for a caller that reads characters of a query after all (checkForSV,
 	 * src/AlignmentBuffer.cpp:1202): from a placeholder, those n characters of the string it stands for, built on the host */
 	static void CopyOut(char * dst, char const * src, int offset, int n);
+};
+
+/*
+ * detectMisalignment on regions found by the device (nm_regions_note.h; CVX_CREATE_NM_REGIONS, include/cvx_align.h).
+ *
+ * Every alignment writes Align::nmPerPosition, 12 bytes per alignment column, for one reader: the peak finder at the top of
+ * AlignmentBuffer::detectMisalignment (reference src/AlignmentBuffer.cpp:1316-1395), which keeps four or five regions.  A
+ * binding that walks a note there announces itself (Announce) before the aligners are built; SharedAligner then creates its
+ * handles with the flag, the binding's allocation site writes a request instead of allocating the profile, and Finish answers
+ * it.  CVX_DEVICE_REGIONS=0 turns all of it off inside the same binary: plain handles, no requests, the reference's loop.
+ */
+struct DeviceRegions {
+	static void Announce();                /* the binding's finder site is compiled in */
+	static bool Enabled();                 /* announced, unless CVX_DEVICE_REGIONS=0 */
+	/* the binding's finder site: an alignment walked `regions` regions of a note / scanned its profile */
+	static void CountNote(int regions);
+	static void CountProfile();
+	static void Stats(long & noteAlignments, long & noteRegions, long & profileAlignments);
 };
 
 }  // namespace Convex

@@ -38,6 +38,12 @@ hipError_t launch_nm_regions_count(const TextArgs &a, int first, int count, unsi
 hipError_t launch_nm_regions_write(const TextArgs &a, int first, int count, const unsigned long long *len, const unsigned long long *off,
 		const NmRegion *stage, NmRegion *regions, hipStream_t st);
 
+/* pass 2 of a job that finds its regions with its results (CVX_CREATE_NM_REGIONS), over all `count` tiles of the job: the same
+ * write into an arena of `cap` regions sized before the total was known -- what lies past cap is dropped, total[0] (the scan's)
+ * says how many there are, total[1] receives cap */
+hipError_t launch_nm_regions_bounded(const TextArgs &a, int count, const unsigned long long *len, const unsigned long long *off,
+		unsigned long long *total, const NmRegion *stage, NmRegion *regions, unsigned long long cap, hipStream_t st);
+
 }  // namespace cvx
 
 #endif

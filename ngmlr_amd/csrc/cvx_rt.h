@@ -226,6 +226,15 @@ struct cvx_batch_s {
 	DevBuf<NmRegion> d_nmreg;        /* ... and the regions, dense */
 	PinBuf h_nmroff, h_nmopen;
 	PinBuf h_nmreg;                  /* the regions on the host: what cvx_job_nm_regions hands out */
+	/* the same regions found with the job's results (a CVX_CREATE_NM_REGIONS handle: queue_job_regions in stage_compute, cvx_job_regions);
+	 * buffers of their own, so that a cvx_job_nm_regions call on the text stream never meets them */
+	DevBuf<unsigned long long> d_jroff;  /* counts[n], offsets[n], the total, the capacity the write ran with */
+	DevBuf<NmOpen> d_jropen;
+	DevBuf<NmRegion> d_jrstage, d_jrreg;
+	PinBuf h_jroff, h_jropen, h_jrreg;   /* offsets[n] + total + capacity and the end states arrive with the result records, the regions with the dense ops */
+	bool jr_on = false;              /* this run of the compute stage queued the finder */
+	uint64_t jr_cap = 0, jr_total = 0;      /* regions the arena holds; regions of the job (after stage_results) */
+	int jr_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
 	PinBuf h_win;                    /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
 	PinBuf h_refs;                   /* ... and the decoded windows back on the host (cvx_job_window_refs): the reference part of d_seq */
 	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
@@ -293,6 +302,7 @@ struct cvx_batch_s {
 		d_ext.release(); d_trec.release(); d_tlen.release(); d_text.release();
 		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
 		d_nmroff.release(); d_nmopen.release(); d_nmstage.release(); d_nmreg.release(); h_nmroff.release(); h_nmopen.release(); h_nmreg.release();
+		d_jroff.release(); d_jropen.release(); d_jrstage.release(); d_jrreg.release(); h_jroff.release(); h_jropen.release(); h_jrreg.release();
 		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
 		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
 		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();
@@ -367,6 +377,7 @@ struct cvx_context {
 	                            * occupancy (0: not asked yet, -1: unknown); filled by stage_compute for the classes a batch uses */
 	bool bt_per_class = true;  /* tuning knob (env CVX_TUNE_BT_PER_CLASS = 0 clears it): a batch of several fill classes walks each class behind its own fill (build_schedule) */
 	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
+	bool nm_regions = false;  /* cvx_create_ex(CVX_CREATE_NM_REGIONS): every job finds the low-identity regions of its tiles behind its compaction (cvx_job_regions) */
 	bool scalar_twin = false; /* cvx_create_ex(CVX_CREATE_SCALAR_TWIN): the semantics of Convex::ConvexAlign (cvx_host_logic.h, fill_semantics) */
 	bool force_generic = false; /* every tile to the catch-all kernel: sse_variant, or a twin handle whose scoring lacks the rings' sign structure */
 	bool sse_variant = false; /* scoring outside the regime where the reference's SSE path equals the scalar recurrence:

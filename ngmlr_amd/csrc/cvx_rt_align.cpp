@@ -62,6 +62,7 @@ void recycle_batch(cvx_context *h, cvx_batch_s *b) {
 	b->have_ops = false;
 	b->have_refs = false;
 	b->text_done = false;
+	b->jr_on = false;
 	b->fail_rc = CVX_OK;
 	b->fail_msg.clear();
 	if (h) {
@@ -117,6 +118,7 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	b->have_ops = false;
 	b->have_refs = false;
 	b->text_done = false;
+	b->jr_on = false;
 	b->ops_total = 0;
 	b->seq_total = L.seq_total;
 	b->n_rows = L.n_rows;
@@ -348,6 +350,41 @@ int upload_chain(cvx_batch_s *b, const HostPlan &hp, const ComputeSchedule &sch,
 	return CVX_OK;
 }
 
+/* regions the dense arena of a job's low-identity regions is first sized for: a 10 kb PacBio tile has four or five */
+static const uint64_t kJobRegionsPerTile = 8;
+
+/* A CVX_CREATE_NM_REGIONS handle: the peak finder of detectMisalignment over the batch's op lists (cvx_text.hip), queued on `st`
+ * behind the compaction with no host step in between -- count + stage per tile, the offset scan, then the write into an arena
+ * sized by an estimate, the way finalize and compact treat the dense ops.  Offsets, total, the capacity the write ran with and
+ * the end states travel in the copies queued here, in front of the event stage_results waits for; the regions themselves with
+ * the dense ops (stage_ops).  rewrite: the arena has grown, only the write runs again. */
+int queue_job_regions(cvx_batch_s *b, hipStream_t st, bool rewrite) {
+	const int n = b->n;
+	const size_t n1 = (size_t) n;
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
+	a.n_tiles = n;
+	if (!rewrite) {
+		RC_TRY(b->d_jroff.ensure(2 * n1 + 8));
+		RC_TRY(b->d_jropen.ensure(n1));
+		RC_TRY(b->d_jrstage.ensure(n1 * (size_t) kNmStage));
+		RC_TRY(b->d_jrreg.ensure((size_t) (kJobRegionsPerTile * n1) + 64));
+		RC_TRY(b->h_jroff.ensure((n1 + 2) * sizeof(unsigned long long)));
+		RC_TRY(b->h_jropen.ensure(n1 * sizeof(NmOpen)));
+		b->jr_cap = b->d_jrreg.cap;
+		b->jr_rewrites = 0;
+	}
+	unsigned long long *d_len = b->d_jroff.p, *d_off = b->d_jroff.p + n1, *d_total = d_off + n1;
+	if (!rewrite) HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_off, d_total, b->d_jropen.p, b->d_jrstage.p, st));
+	HIP_TRY(launch_nm_regions_bounded(a, n, d_len, d_off, d_total, b->d_jrstage.p, b->d_jrreg.p, b->jr_cap, st));
+	if (!rewrite) {
+		HIP_TRY(hipMemcpyAsync(b->h_jroff.p, d_off, (n1 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(b->h_jropen.p, b->d_jropen.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
+	}
+	return CVX_OK;
+}
+
 /* ---- stage 3: host planning, then every kernel of the batch on `main` (+ aux); nothing waits */
 int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	const int n = b->n;
@@ -367,7 +404,13 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	b->launch_tail.clear();
 	b->ops_total = 0;
 	b->have_ops = false;
+	b->jr_on = h->nm_regions;
+	b->jr_total = 0;
 	if (n == 0) {
+		if (b->jr_on) {      /* cvx_job_regions of an empty job: one offset, 0 */
+			RC_TRY(b->h_jroff.ensure(2 * sizeof(unsigned long long)));
+			memset(b->h_jroff.p, 0, 2 * sizeof(unsigned long long));
+		}
 		HIP_TRY(hipEventRecord(b->ev[4], st));
 		hipStream_t ps = h->overlap_post ? S_post : S_main;
 		HIP_TRY(hipStreamWaitEvent(ps, b->ev[4], 0));
@@ -548,6 +591,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	BatchSummary *d_sum = reinterpret_cast<BatchSummary *>(b->d_res.p + (size_t) n * sizeof(ResultRec));
 	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, b->d_dstoff.p + n, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
 	HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, n, b->dense_cap, st));
+	if (b->jr_on) RC_TRY(queue_job_regions(b, st, false));      /* (inside the compute stage's timing: ev[3] below) */
 	HIP_TRY(hipEventRecord(b->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(b->h_res.p, b->d_res.p, (size_t) n * sizeof(ResultRec) + sizeof(BatchSummary), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(b->ev_res, st));
@@ -569,6 +613,7 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	if (b->n == 0) { b->ops_total = 0; b->state = kFinished; return CVX_OK; }
 	const BatchSummary *s = b->summary();
 	b->ops_total = s->ops_total;
+	if (b->jr_on) b->jr_total = b->h_jroff.as<unsigned long long>()[(size_t) b->n];      /* (the total sits behind the n offsets) */
 	const int launches = b->timing.n_fill_launches;
 	for (int i = 0; i < launches; ++i) {
 		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
@@ -614,6 +659,22 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 		hipStream_t ps = b->s_run ? b->s_run : h->s_main;      /* the batch's own stream set: behind everything it queued */
 		HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, b->n, b->dense_cap, ps));
 		HIP_TRY(hipStreamSynchronize(ps));
+	}
+	if (b->jr_on && b->jr_total > b->jr_cap) {
+		/* as rare: more regions than eight per tile -- a larger arena, and the write alone runs again (counts, offsets and the
+		 * staged regions are still the job's) */
+		RC_TRY(b->d_jrreg.ensure((size_t) b->jr_total + 64));
+		b->jr_cap = b->d_jrreg.cap;
+		b->jr_rewrites += 1;
+		hipStream_t ps = b->s_run ? b->s_run : h->s_main;
+		RC_TRY(queue_job_regions(b, ps, true));
+		HIP_TRY(hipStreamSynchronize(ps));
+	}
+	if (b->jr_on && b->jr_total) {
+		/* the regions ride in front of the dense ops, under the one wait below (a job with regions has ops) */
+		RC_TRY(b->h_jrreg.ensure((size_t) b->jr_total * sizeof(NmRegion)));
+		HIP_TRY(hipMemcpyAsync(b->h_jrreg.p, b->d_jrreg.p, (size_t) b->jr_total * sizeof(NmRegion), hipMemcpyDeviceToHost, h->s_io));
+		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
 	}
 	if (b->ops_total) {
 		RC_TRY(b->h_ops.ensure((size_t) b->ops_total * sizeof(uint32_t)));

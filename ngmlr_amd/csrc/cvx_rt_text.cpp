@@ -333,6 +333,39 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 	ABI_GUARD_END
 }
 
+/* the job form: what queue_job_regions (cvx_rt_align.cpp) queued behind the job's compaction and stage_results / stage_ops
+ * brought back in their own waits -- nothing is launched, copied or waited for here */
+static int job_regions_ready(const char *who, cvx_handle h, cvx_job j) {
+	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
+	if (!h->nm_regions) { set_err("%s: the handle was created without CVX_CREATE_NM_REGIONS", who); return CVX_ERR_ARG; }
+	if (j->state < kFinished || !j->have_ops || !j->jr_on) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
+	return CVX_OK;
+}
+
+int cvx_job_regions(cvx_handle h, cvx_job j, const uint64_t **region_off, const cvx_nm_region **regions, const cvx_nm_open **open) {
+	ABI_GUARD_BEGIN
+	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the offsets leave as the scan wrote them");
+	if (region_off) *region_off = nullptr;
+	if (regions) *regions = nullptr;
+	if (open) *open = nullptr;
+	RC_TRY(job_regions_ready("cvx_job_regions", h, j));
+	if (region_off) *region_off = j->h_jroff.as<uint64_t>();
+	if (regions) *regions = j->h_jrreg.as<cvx_nm_region>();      /* (NULL for a job that never had a region: nothing to point at) */
+	if (open) *open = j->n > 0 ? j->h_jropen.as<cvx_nm_open>() : nullptr;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_job_regions_info(cvx_handle h, cvx_job j, uint64_t *total, uint64_t *first_capacity, int32_t *rewrites) {
+	ABI_GUARD_BEGIN
+	RC_TRY(job_regions_ready("cvx_job_regions_info", h, j));
+	if (total) *total = j->jr_total;
+	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jroff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
+	if (rewrites) *rewrites = j->jr_rewrites;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
 int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
 		uint64_t *region_off, cvx_nm_region *regions, uint64_t cap_regions, cvx_nm_open *open) {
 	ABI_GUARD_BEGIN

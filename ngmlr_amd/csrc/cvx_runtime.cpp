@@ -232,7 +232,11 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 				p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay);
 		return CVX_ERR_PARAMS;
 	}
-	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN | CVX_CREATE_NM_REGIONS)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	if ((flags & CVX_CREATE_NM_REGIONS) && (flags & CVX_CREATE_SERVICE)) {
+		set_err("cvx_create_ex: CVX_CREATE_NM_REGIONS on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
+		return CVX_ERR_ARG;
+	}
 	/* (a scalar-twin handle runs the scalar recurrence for any scoring: rings where their sign structure holds, else the
 	 * catch-all kernel with scalar rules, never the SSE variant -- fill_semantics, cvx_host_logic.h) */
 	const bool scalar_twin = (flags & CVX_CREATE_SCALAR_TWIN) != 0;
@@ -343,6 +347,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	 * fill classes behind each other and scoring kernels behind 10 ms fills (profiles/r06_e2e_launch_trace.txt). */
 	hipError_t e = hipSuccess;
 	c->service = (flags & CVX_CREATE_SERVICE) != 0;
+	c->nm_regions = (flags & CVX_CREATE_NM_REGIONS) != 0;
 	const char *sp = getenv("CVX_SERVICE_PRIO");
 	int shared = 4;      /* CVX_SERVICE_STREAMS: streams per device the service handles of a process share (0 = one of its own per handle) */
 	if (const char *e2 = getenv("CVX_SERVICE_STREAMS")) shared = atoi(e2) > 0 ? std::min(atoi(e2), kServiceStreamsMax) : 0;

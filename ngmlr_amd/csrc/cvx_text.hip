@@ -576,6 +576,37 @@ nm_regions_kernel(const TextArgs a, const int first, unsigned long long *len, co
 	if (lane == 0) { len[b] = (unsigned long long) n_closed; open[b] = st; }
 }
 
+/* The job form of nm_regions_kernel<false> (stage_compute on a CVX_CREATE_NM_REGIONS handle): the arena was sized by an estimate
+ * before anybody knew the total, so tile b writes only the part of its regions that lies below `cap` -- the way compact_ops_kernel
+ * treats the dense op arena.  total[0] is the scan's true total; total[1] = cap, the capacity this write ran with, travels to the
+ * host beside it, and a job that needs more runs the write again over a larger arena (stage_ops). */
+__global__ void __launch_bounds__(64)
+nm_regions_bounded_kernel(const TextArgs a, const unsigned long long *len, const unsigned long long *off, unsigned long long *total,
+		const NmRegion *stage, NmRegion *regions, const unsigned long long cap) {
+	const int b = (int) blockIdx.x;
+	const int lane = (int) threadIdx.x;
+	if (b == 0 && lane == 0) total[1] = cap;
+	const int n_closed = (int) len[b];
+	const unsigned long long at = off[b];
+	if (n_closed <= 0 || at >= cap) return;
+	const int room = cap - at < (unsigned long long) n_closed ? (int) (cap - at) : n_closed;
+	NmRegion *dst = regions + at;
+	if (n_closed <= kNmStage) {
+		if (lane < room) dst[lane] = stage[(size_t) b * kNmStage + lane];
+		return;
+	}
+	const TileOut o = a.tout[b];
+	const NmScanEnd s = nm_regions_tile(lane, o, a.ops + a.trun[b].ops_off + o.ops_first, room, dst);
+	if (lane == 0 && s.heads == n_closed && room == n_closed) { dst[n_closed - 1].ref_stop = s.last_ref; dst[n_closed - 1].read_stop = s.last_read; }
+}
+
+hipError_t launch_nm_regions_bounded(const TextArgs &a, int count, const unsigned long long *len, const unsigned long long *off,
+		unsigned long long *total, const NmRegion *stage, NmRegion *regions, unsigned long long cap, hipStream_t st) {
+	if (count <= 0) return hipSuccess;
+	hipLaunchKernelGGL(nm_regions_bounded_kernel, dim3(count), dim3(64), 0, st, a, len, off, total, stage, regions, cap);
+	return hipGetLastError();
+}
+
 hipError_t launch_nm_regions_count(const TextArgs &a, int first, int count, unsigned long long *len, unsigned long long *off,
 		unsigned long long *total, NmOpen *open, NmRegion *stage, hipStream_t st) {
 	if (count <= 0) return hipSuccess;

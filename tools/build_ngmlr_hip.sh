@@ -46,20 +46,25 @@ mkdir -p "$REPO/oracle/_ref"
 #   ngmlr_index_cpu    the reference's CPU code with only that table builder bound: the table file it writes against the unmodified
 #                      binary's, without a GPU (tests/test_index_cpu.py)
 #   ngmlr_pool_cpu     the reference's CPU aligners + the same pool: the pool's own correctness without a GPU (tests/test_pool_cpu.py)
+#   ngmlr_hip_regions  ngmlr_hip_all + detectMisalignment on the regions its job found: a request instead of the nmPerPosition profile where
+#                      computeAlignment allocates it, the peak finder's loop as a walk over the aligner's note (nm_regions_*_binding.inc,
+#                      ngmlr_amd/csrc/nm_regions_note.h; CVX_DEVICE_REGIONS=0 restores the profile inside the same binary)
+#   ngmlr_regions_cpu  the same two insertions around the reference's CPU aligner (tests/cpp/regions_cpu_aligner.h), no GPU
 #   ngmlr_pool_parked  the same with a park / wake of the read's user-level context in front of every SingleAlign
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-} REGIONS=${12:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" "$REGIONS" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 SCOREWIN = sys.argv[10]
 FEED = sys.argv[11]
 READSEG = sys.argv[12]
+REGIONS = sys.argv[13]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -110,6 +115,34 @@ if READSEG:
     s = sub1(s, '\t\tInterval const * interval, MappedRead* read,\n\t\tbool const revComp) {\n', '\t\tInterval const * interval, MappedRead* read,\n\t\tbool const revComp) {\n#include "read_segments_binding.inc"\n', 'extractReadSeq (Interval overload)')
     s = sub1(s, 'strncpy(readSeq, fullReadSeq + inversionMidpointOnRead - readCheckLength, readCheckLength * 2);',
              'Convex::DeviceReads::CopyOut(readSeq, fullReadSeq, inversionMidpointOnRead - readCheckLength, readCheckLength * 2);', 'checkForSV')
+    open(p, 'w').write(s)
+if REGIONS:
+    # detectMisalignment on the regions the aligner found (ngmlr_amd/csrc/nm_regions_note.h, Convex::DeviceRegions in convex_align_hip.h;
+    # CVX_DEVICE_REGIONS=0 turns it off): a request instead of the profile's buffer where computeAlignment allocates it
+    # (nm_regions_alloc_binding.inc, the reference's two lines kept as its else branch), and the peak finder's loop as a walk over the
+    # note (nm_regions_finder_binding.inc) -- what the reference does per region moved, as it stands, into a lambda both forms call
+    assert CLASS != 'cpu'
+    p = T + '/src/AlignmentBuffer.cpp'
+    s = open(p).read()
+    m = re.search(r'^([ \t]*)align->nmPerPostionLength = \(readLength \+ 1\) \* 2;\n[ \t]*align->nmPerPosition = new PositionNM\[align->nmPerPostionLength\];\n', s, re.M)
+    assert m and len(re.findall(r'\balign->nmPerPosition = new PositionNM\[', s)) == 1, 'profile allocation'
+    s = s[:m.start()] + '#include "nm_regions_alloc_binding.inc"\n' + m.group(1) + '{\n' + m.group(0) + m.group(1) + '}\n' + s[m.end():]
+    first, last = 'if (stdoutInversionBed) {\n', 'bestInversionMidpointOnRead = inversionMidpointOnRead;\n'
+    assert s.count(first) == 1 and s.count(last) == 1, 'region body'
+    a = s.rindex('\n', 0, s.index(first)) + 1
+    b = s.index('}\n', s.index(last)) + 2
+    body = s[a:b]
+    s = s[:a] + '\t\t\t\t\tcvxRegionBody();\n' + s[b:]
+    s = sub1(s, '\tfor (int i = 0; i < align->alignmentLength /*&& result == SV_NONE*/; ++i) {\n',
+             '\tauto cvxRegionBody = [&]() {\n' + body + '\t};\n#include "nm_regions_finder_binding.inc"\n'
+             '\tfor (int i = 0; !cvxNote && i < align->alignmentLength /*&& result == SV_NONE*/; ++i) {\n', 'peak finder loop')
+    open(p, 'w').write(s)
+    # (the CPU wrapper stands only in the SSE branch: under --nosse the reference's own scalar aligner is constructed, which knows no
+    # request, so nothing is announced there and the reference's allocation and loop run)
+    p = T + '/src/AlignmentBuffer.h'
+    s = open(p).read()
+    s = sub1(s, '\t\tif (Config.getNoSSE()) {\n', ('\t\tif (%s) Convex::DeviceRegions::Announce();      /* cvx: this binary\'s detectMisalignment walks a note */\n\t\tif (Config.getNoSSE()) {\n'
+             % ('!Config.getNoSSE()' if 'RegionsCpu' in CLASS else 'true')), 'AlignmentBuffer ctor (regions)')
     open(p, 'w').write(s)
 if SEARCH:
     # the k-mer vote of a CS thread's batch on the device (ngmlr_amd/csrc/candidate_search_hip.h, cs_search_binding.inc)
@@ -254,7 +287,7 @@ if SCORER:
 if CLASS != 'cpu':
     p = T + '/src/AlignmentBuffer.h'
     s = open(p).read()
-    s = s.replace('#include "ConvexAlignFast.h"', '#include "ConvexAlignFast.h"\n#include "convex_align_hip.h"\n#include "batching_aligner.h"' + ('\n#include "parking_cpu_aligner.h"' if 'Parking' in CLASS else ''), 1)
+    s = s.replace('#include "ConvexAlignFast.h"', '#include "ConvexAlignFast.h"\n#include "convex_align_hip.h"\n#include "batching_aligner.h"' + ('\n#include "parking_cpu_aligner.h"' if 'Parking' in CLASS else '') + ('\n#include "nm_regions_note.h"' if REGIONS else '') + ('\n#include "regions_cpu_aligner.h"' if 'RegionsCpu' in CLASS else ''), 1)
     pat = re.compile(r'aligner = new Convex::ConvexAlignFast\(', re.S)
     assert len(pat.findall(s)) == 1
     s = pat.sub('aligner = new %s(' % CLASS, s)
@@ -295,10 +328,12 @@ bv ngmlr_hip_checks Convex::SharedAligner StrippedSWHip sam pool search index ch
 bv ngmlr_hip_scorewin Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin
 bv ngmlr_hip_feed Convex::SharedAligner StrippedSWHip sam pool search index "" scorewin feed
 bv ngmlr_hip_readseg Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" readseg
+bv ngmlr_hip_regions Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions
+bv ngmlr_regions_cpu Convex::RegionsCpuAligner "" "" "" "" "" "" "" "" "" regions      # the reference's CPU aligner behind the request / note exchange (tests/cpp/regions_cpu_aligner.h)
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_hip_regions ngmlr_regions_cpu ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
