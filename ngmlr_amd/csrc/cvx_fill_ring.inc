@@ -10,6 +10,20 @@
  * (src/ConvexAlign.cpp:511-513).  That is one compare and one select more per cell, in a loop whose floor is the pipe those
  * two run on (DESIGN.md 5), hence a compile-time switch; and it is a second kernel name instead of a sixth template
  * parameter so that the default forms keep their names and, instruction for instruction, their code.
+ *
+ * The forms of one kernel (which of them are built, and which serves a launch: pick_fill, cvx_kernels.hip):
+ *
+ *   MODE   kFillTwoPhase / kFillExact (whole tiles: best-cell tracking late only / from the first step), kFillChain (row blocks)
+ *   WRAP   gap runs as the reference's int16 instead of floats
+ *   G > 1  a gang of G waves on one ring (M = 3, whole tiles, float runs)
+ *   TAB    the convex penalty from a table in LDS instead of multiply, add, min (two-phase, float runs); a cell's offers to its
+ *          neighbours are then worked out one step after the cell, when the penalty has come back.  Two forms of it:
+ *            a gang    a table of penalties, the run register its byte address, clamped once per 32 steps
+ *            FAST      (no gang) {penalty, next address} pairs, the extension offer without a multiply, scores scaled by 2^-64
+ *          and without TAB the arithmetic form: V[] and Hc[] hold the offers, computed with the cell.
+ *
+ * The text has no preprocessor conditional: every choice is a template parameter.  What was tried and left out is in
+ * docs/history.md ("Retired build switches of the ring fill").
  */
 template <int M, bool WRAP, int MODE, bool TAB = false, int G = 1>
 __global__ void __launch_bounds__(64 * G) CVX_FILL_OCC(M, TAB && G == 1)
@@ -35,16 +49,16 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	const int tid = threadIdx.x;           /* = ring slot / M of the thread's first slot */
 	const int lane = GANG ? (tid & 63) : tid;
 	const int wv = GANG ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;      /* wave inside the gang */
-	/* the forms of the FAST cell update (cvx_kernels.hip has the switches; FAST itself is explained below) */
-	constexpr bool FAST_ = TAB && G == 1;
-	constexpr bool NOMUL = FAST_ && (CVX_CELL_NOMUL != 0);
-	constexpr bool SCALED = FAST_ && (CVX_CELL_CLAMP != 0);
-	/* SCALED: every score of the step loop is the parent form's times kScoreScale = 2^-64, so that the clamp bit of v_max3_f32
-	 * ([0, 1]) is the zero clamp of the cell maximum and nothing else: the largest score, 2^20 a row over 2^31 rows, scales to
-	 * 2^-13.  The scoring values are scaled once, here (the table's penalties below, computed unscaled first); the host admits
-	 * only scorings whose nonzero values have binary exponents in [-20, 20] (score_scale_exact, cvx_host_logic.h), every score
-	 * is then a multiple of 2^-43 and its scaled value is zero or normal, and binary32 +, max, negation and compares commute
-	 * with the scaling.  best[] and lbest are multiplied back before the argmax; kFillExact stays unscaled. */
+	/* FAST = TAB without a gang (the ring classes of every default handle): the penalty table holds {penalty, next run} pairs
+	 * (s_pen2 below), the gap-extension offer has no multiply and the step loop runs on scaled scores */
+	constexpr bool FAST = TAB && !GANG;
+	/* SCALED = FAST, under the name that says why a value is multiplied: every score of the step loop is the unscaled form's times
+	 * kScoreScale = 2^-64, so that the clamp bit of v_max3_f32 ([0, 1]) is the zero clamp of the cell maximum and nothing else:
+	 * the largest score, 2^20 a row over 2^31 rows, scales to 2^-13.  The scoring values are scaled once, here (the table's
+	 * penalties below, computed unscaled first); the host admits only scorings whose nonzero values have binary exponents in [-20, 20] (score_scale_exact, cvx_host_logic.h),
+	 * every score is then a multiple of 2^-43 and its scaled value is zero or normal, and binary32 +, max, negation and
+	 * compares commute with the scaling.  best[] and lbest are multiplied back before the argmax; kFillExact stays unscaled. */
+	constexpr bool SCALED = FAST;
 	const float go = SCALED ? a.sp.go * kScoreScale : a.sp.go;
 	const float gext = a.sp.ge, gem = a.sp.gem, decay = a.sp.decay;
 	/* keep match / mismatch in VGPRs: v_cndmask cannot take two SGPR values plus a mask */
@@ -77,14 +91,12 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	 * the table has kPenClamp + kPenClampSteps + 1 entries or more whatever the corridor (gap runs through zero-score
 	 * cells are as long as a row is wide).  A gang's wave clamps what it takes from its neighbour's record as well (a
 	 * scalar min): that register was offered one step before the neighbour's own clamp. */
-	/* FAST = TAB without a gang (the ring classes of every default handle): the table holds {pen, next} pairs,
+	/* FAST: the table holds {pen, next} pairs,
 	 * next(e) = kPenPairStride * min(e + 1, kPenClamp), and the run register of the new cell is the second dword of the same
 	 * ds_read_b64 that fetches its penalty, consumed one step later like the penalty.  No add per cell, no periodic clamp, no
 	 * slack entries: an address is always one of kPenPairStride * (1 ... kPenClamp).  The host's condition (penalty constant
 	 * from run kPenClamp on) is what makes the saturating next exact.  The gang form keeps the table above, its clamp and the
 	 * 16-bit run of its boundary record. */
-	constexpr bool FAST = TAB && !GANG;
-	static_assert(FAST == FAST_, "one definition of the FAST form");
 	__shared__ float s_pen[TAB && !FAST ? kPenEntries : 1];
 	__shared__ float2 s_pen2[FAST ? kPenPairs : 1];
 
@@ -112,13 +124,11 @@ CVX_FILL_KERNEL(const FillArgs a) {
 		/* the widest ring class of a batch of several (FillArgs::chain_prio, set by the host): its waves pay the most per step, its
 		 * tiles are the launch's long pole beside the narrower classes' -- one notch above those */
 		if (!GANG && a.chain_prio) { if (a.chain_prio >= 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
-#if CVX_FILL_PRIO
 		/* The list is longest-first and a tile is a serial chain of steps: in a batch of uneven tiles (ONT mix: median
 		 * 1.3 kb, up to 20 kb) the launch lasts as long as its longest tiles take at a sixth of a SIMD.  The first
 		 * sixteenth of the list runs at raised wave priority: those waves proceed at nearly a whole SIMD's pace, the short
 		 * tiles fill in behind them.  (A batch of equal tiles -- the PacBio bench -- is unaffected.) */
 		if (blockIdx.x < (unsigned) (a.list_n >> 4)) __builtin_amdgcn_s_setprio(2);
-#endif
 		/* a gang's tiles are the widest corridors of the batch -- the retry loop's second and third attempts, twice and three
 		 * times the steps per row -- and, like the chained blocks, the long pole of a mixed launch: raised priority for all of them
 		 * (FillArgs::chain_prio; CVX_TUNE_GANG_PRIO=0 switches it off) */
@@ -151,8 +161,8 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	 * src/AlignmentMatrixFast.h:49-53), i.e. S = 0, runs = 0, V = Hc = gap_open;
 	 * the update below produces exactly that for inactive lanes by itself. */
 	float S[M];        /* score of the slot's latest cell                            */
-	float Hc[M];       /* left candidate that cell offers to the next column         */
-	float V[M];        /* up candidate it offers to the next row                     */
+	float Hc[M];       /* left candidate that cell offers to the next column (arithmetic forms: TAB has offers() instead) */
+	float V[M];        /* up candidate it offers to the next row (likewise)          */
 	float dg[M];       /* diagonal score for the slot's next cell                    */
 	run_t drun[M];     /* deletion run of the latest cell: the run itself (0 unless D) in the int16   */
 	run_t irun[M];     /* kernels, run + 1 in the float ones (read only through mD / mI); same for I  */
@@ -161,8 +171,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 	int qch[M];        /* read character of the row                                  */
 	unsigned xa[M];    /* seq-arena offset of the next reference dword to prefetch   */
 	unsigned cwn[M];   /* reference characters of the NEXT 4-step group              */
-	float penp[M];     /* TAB (lazy form): the penalty an extension of the slot's latest cell pays, on its way from LDS */
-	constexpr bool LAZY = TAB && (CVX_FILL_TAB_LAZY != 0);
+	float penp[M];     /* TAB: the penalty an extension of the slot's latest cell pays, on its way from LDS */
 	float best[M];
 	int best_r[M];
 	float lbest = 0.0f;          /* early phase: running maximum of this lane's cells */
@@ -365,17 +374,17 @@ CVX_FILL_KERNEL(const FillArgs a) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
 			/* lane boundary: previous lane's last slot, values of step r-1 */
-			/* (lazy TAB form: what a slot's latest cell offers -- E to an extension, O to an opening -- is worked out here, one
+			/* (TAB: what a slot's latest cell offers -- E to an extension, O to an opening -- is worked out here, one
 			 * step after the cell, from its score, the penalty that has come back from LDS meanwhile and its two masks) */
 			float p_E[M], p_O[M];
 			auto offers = [&](const int j) {
-				/* NOMUL: -S for the product.  Either is +-0 exactly when S is zero and negative otherwise, and an offer is only read
+				/* FAST: -S for the product.  Either is +-0 exactly when S is zero and negative otherwise, and an offer is only read
 				 * through the maximum with zero and the equality with that maximum */
-				p_E[j] = NOMUL ? fmaxf(S[j] + penp[j], -S[j]) : fmaxf(S[j] + penp[j], S[j] * -0x1p100f);
+				p_E[j] = FAST ? fmaxf(S[j] + penp[j], -S[j]) : fmaxf(S[j] + penp[j], S[j] * -0x1p100f);
 				p_O[j] = S[j] + go;
 			};
-			if (LAZY) offers(M - 1);
-			float uV0 = LAZY ? rot1_f(lanes(mI[M - 1]) ? p_E[M - 1] : p_O[M - 1]) : rot1_f(V[M - 1]);
+			if (TAB) offers(M - 1);
+			float uV0 = TAB ? rot1_f(lanes(mI[M - 1]) ? p_E[M - 1] : p_O[M - 1]) : rot1_f(V[M - 1]);
 			float uS0 = rot1_f(S[M - 1]);
 			run_t uI0;
 			if (WRAP || TAB) uI0 = (run_t) rot1_i((int) irun[M - 1]);
@@ -394,9 +403,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 					int spins = 0;
 					while (!gang_failed && (((unsigned) __builtin_amdgcn_readfirstlane((int) (gq >> 32))) >> 17) != want_tag) {
 						if (++spins > (1 << 22)) { gang_failed = 1; break; }      /* never hang the device */
-#if CVX_GANG_SLEEP > 0
-						__builtin_amdgcn_s_sleep(CVX_GANG_SLEEP);
-#endif
+						__builtin_amdgcn_s_sleep(kGangWaitSleep);
 						gq = __hip_atomic_load(&s_gx[gang_pred][(r - r0 - 1) & (kGangDepth - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 					}
 					const unsigned meta = (unsigned) __builtin_amdgcn_readfirstlane((int) (gq >> 32));
@@ -447,7 +454,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				const run_t uI = (j > 0) ? irun[j > 0 ? j - 1 : 0] : uI0;
 				const u64 mIu = (j > 0) ? mI[j > 0 ? j - 1 : 0] : mIu0;
 				float lcv = Hc[j];
-				if (LAZY) {
+				if (TAB) {
 					if (j > 0) {
 						offers(j > 0 ? j - 1 : 0);
 						uV = lanes(mIu) ? p_E[j > 0 ? j - 1 : 0] : p_O[j > 0 ? j - 1 : 0];
@@ -496,7 +503,6 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				const float sc = lanes(p_act[j]) ? mx : 0.0f;
 				run_t nd, ni;
 				float runf = 0.0f;
-				float E;
 				if (FAST) {
 					/* the registers hold the table address of entry run + 1 -- the {penalty, next address} pair of a cell that
 					 * extends this one -- and the new cell's register comes back with its penalty; as in the float form they are
@@ -507,8 +513,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 					const float2 pn = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(s_pen2) + ra);
 					nd = (run_t) __float_as_int(pn.y);
 					ni = nd;
-					if (LAZY) penp[j] = pn.x;
-					E = fmaxf(sc + pn.x, sc * -0x1p100f);      /* (dead code in the lazy form) */
+					penp[j] = pn.x;
 				} else if (TAB) {
 					/* the registers hold 4 * (run + 1), the table address of the penalty a cell that extends this one pays
 					 * for; as in the float form they are only ever read through the masks (isDl, isIu) */
@@ -517,9 +522,7 @@ CVX_FILL_KERNEL(const FillArgs a) {
 					const int ra = lanes(extD) ? (int) drun[j] : t1;
 					nd = (run_t) (ra + 4);
 					ni = nd;
-					const float pen = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_pen) + ra);
-					if (LAZY) penp[j] = pen;
-					E = fmaxf(sc + pen, sc * -0x1p100f);      /* gap_extend_value with the penalty looked up (dead code in the lazy form) */
+					penp[j] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(s_pen) + ra);
 				} else if (WRAP) {
 					/* indelRun is a short in the reference (src/AlignmentMatrixFast.h:43) */
 					nd = lanes(nD) ? (lanes(isDl) ? (run_t) (short) ((int) drun[j] + 1) : (run_t) 1) : (run_t) 0;
@@ -538,14 +541,14 @@ CVX_FILL_KERNEL(const FillArgs a) {
 					nd = (run_t) (runf + 1.0f);
 					ni = nd;
 				}
-				if (!TAB) E = gap_extend_value(sc, runf, gem, gext, decay);
-				const float O = sc + go;
-
 				dg[j] = uS;
 				S[j] = sc;
 				drun[j] = nd;
 				irun[j] = ni;
-				if (!LAZY) {
+				if (!TAB) {
+					/* the arithmetic forms work the cell's offers out at once (TAB: one step later, in offers()) */
+					const float E = gap_extend_value(sc, runf, gem, gext, decay);
+					const float O = sc + go;
 					V[j] = lanes(nI) ? E : O;
 					Hc[j] = lanes(nD) ? E : O;
 				}
@@ -567,34 +570,12 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				accA[j] = shl1_in(accA[j], p_gap[j]);       /* plane 0: I or D */
 				accB[j] = shl1_in(accB[j], p_cread[j]);     /* plane 1: I or diagonal */
 			};
-#if CVX_FILL_SCHED == 1
-			/* all candidates / compares first, then all mask logic, then all state updates */
-#pragma unroll
-			for (int j = M - 1; j >= 0; --j) phase1(j, misx);
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int j = M - 1; j >= 0; --j) phase2(j);
-			__builtin_amdgcn_sched_barrier(0);
-#elif CVX_FILL_SCHED == 2
-			/* software pipeline over the slots: the mask logic of slot j runs beside the compares of slot j-1 */
-#pragma unroll
-			for (int q = M; q >= -1; --q) {
-				if (q < M && q >= 0) phase1(q, misx);
-				if (q + 1 < M && q + 1 >= 0) phase2(q + 1);
-				__builtin_amdgcn_sched_barrier(0);
-			}
-#endif
 #pragma unroll
 			for (int j = M - 1; j >= 0; --j) {
-#if CVX_FILL_SCHED == 0 || CVX_FILL_SCHED == 3
 				if (GANG && j == 0) gang_take();
 				phase1(j, misx); phase2(j);
-#endif
 				phase3(j);
 				if (GANG && j == M - 1) gang_give();
-#if CVX_FILL_SCHED == 3
-				__builtin_amdgcn_sched_barrier(0);
-#endif
 				if (CHAIN && j == out_j && ct.has_next) {
 					/* the last row's new cell goes to the boundary stream (record index = its column in the row) */
 					if (lane == out_lane && (unsigned) (cnt[j] - 1) < (unsigned) len[j]) {

@@ -191,19 +191,12 @@ CVX_DEV bool lanes(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 CVX_DEV u64 rot1_m(u64 m) { return (m << 1) | (m >> 63); }
 /* acc = (acc << 1) | (lane's bit of m): one v_addc_co_u32 with the mask as carry-in.
  * m must come from SALU mask logic (it does: planes are s_or_b64 results). */
-#ifndef CVX_FILL_ADDC_SGPR
-#define CVX_FILL_ADDC_SGPR 1
-#endif
 CVX_DEV unsigned shl1_in(unsigned acc, u64 m) {
-#if CVX_FILL_ADDC_SGPR
 	/* the (unused) carry-out goes to an SGPR pair of the compiler's choice, not to VCC: in that form the
 	 * instruction issues beside a full-rate VALU op like any other half-rate one; with VCC as its
 	 * destination it does not (profiles/r03_ubench_pipes.txt, kinds 15-18) */
 	u64 carry_out;
 	asm volatile("v_addc_co_u32_e64 %0, %1, %0, %0, %2" : "+v"(acc), "=s"(carry_out) : "s"(m));
-#else
-	asm volatile("v_addc_co_u32_e64 %0, vcc, %0, %0, %1" : "+v"(acc) : "s"(m) : "vcc");
-#endif
 	return acc;
 }
 
@@ -426,55 +419,16 @@ template <bool WRAP> struct RunT { typedef float type; };
 template <> struct RunT<true> { typedef int type; };
 template <bool B> struct BoolTag { static constexpr bool value = B; };
 
-/* Occupancy target.  The M = 3 kernel (corridors of 310-370 columns, i.e. almost every
- * PacBio/ONT tile) is measured ~14 % faster at 6 waves/SIMD (80 VGPRs, the few spilled values are
- * tile constants outside the step loop) than at the 5 the allocator picks by itself; the other
- * classes keep the default.  CVX_FILL_WAVES_PER_EU overrides for A/B runs. */
-#ifndef CVX_FILL_WAVES_PER_EU
-#define CVX_FILL_WAVES_PER_EU 6
-#endif
-#ifndef CVX_FILL_WAVES_M4
-#define CVX_FILL_WAVES_M4 1
-#endif
-#ifndef CVX_FILL_WAVES_TAB
-#define CVX_FILL_WAVES_TAB 7
-#endif
-/* (round 5: the two-phase M = 3 instantiation with the penalty table -- the PacBio launch -- fits seven waves per SIMD: 72 VGPRs,
- * 4 KB of LDS per wave; 104.95 -> 101.7 ms per 49 108 tiles.  The exact and the gang instantiations keep six.) */
-#define CVX_FILL_OCC(M, SEVEN) __attribute__((amdgpu_waves_per_eu( \
-		(M) == 3 ? ((SEVEN) ? CVX_FILL_WAVES_TAB : CVX_FILL_WAVES_PER_EU) : ((M) == 4 ? CVX_FILL_WAVES_M4 : 1), \
-		(M) == 3 ? ((SEVEN) ? CVX_FILL_WAVES_TAB : CVX_FILL_WAVES_PER_EU) : ((M) == 4 && CVX_FILL_WAVES_M4 > 1 ? CVX_FILL_WAVES_M4 : 8))))
+/* Occupancy target, waves per SIMD as (min, max) of amdgpu_waves_per_eu.  The M = 3 kernels (corridors of 310-370 columns, i.e.
+ * almost every PacBio/ONT tile) ask for exactly six (80 VGPRs, the few spilled values are tile constants outside the step loop;
+ * ~14 % faster than at the five the allocator picks by itself), and for seven in the FAST form (TAB without a gang,
+ * cvx_fill_ring.inc: 72 VGPRs, 4 KB of LDS per wave -- the PacBio launch).  The other classes keep the default. */
+constexpr int fill_waves_min(const int m, const bool fast) { return m == 3 ? (fast ? 7 : 6) : 1; }
+constexpr int fill_waves_max(const int m, const bool fast) { return m == 3 ? (fast ? 7 : 6) : 8; }
+#define CVX_FILL_OCC(M, FAST) __attribute__((amdgpu_waves_per_eu(fill_waves_min(M, FAST), fill_waves_max(M, FAST))))
 
-/* TAB instantiation: 1 = the penalty read of a cell is consumed one step later, where the cell's offers to its two
- * consumers (V, Hc) are first needed -- the LDS round trip then has most of a step to come back; 0 = consumed at once */
-#ifndef CVX_FILL_TAB_LAZY
-#define CVX_FILL_TAB_LAZY 1
-#endif
-
-/* gang: s_sleep argument of a wave that waits for its neighbour's record (x 64 clocks; 0 = spin) */
-#ifndef CVX_GANG_SLEEP
-#define CVX_GANG_SLEEP 1
-#endif
-
-/* instruction-order experiments on the cell update (0: leave it to the compiler) */
-#ifndef CVX_FILL_SCHED
-#define CVX_FILL_SCHED 0
-#endif
-
-#ifndef CVX_FILL_PRIO
-#define CVX_FILL_PRIO 1
-#endif
-
-/* The cell update of the FAST form (TAB without a gang: cvx_fill_ring.inc), two switches for A/B builds (tools/build_variant.sh):
- *   CVX_CELL_NOMUL   the gap-extension offer as max(S + pen, -S) instead of max(S + pen, S * -2^100): no multiply
- *   CVX_CELL_CLAMP   the zero clamp of a cell's maximum as the clamp bit of v_max3_f32, on scores scaled by kScoreScale
- * DESIGN.md 5 has what each is worth, and the two forms of folding a lane rotate into its consumer that were measured and left out. */
-#ifndef CVX_CELL_NOMUL
-#define CVX_CELL_NOMUL 1
-#endif
-#ifndef CVX_CELL_CLAMP
-#define CVX_CELL_CLAMP 1
-#endif
+/* gang: s_sleep argument of a wave that waits for its neighbour's record (x 64 clocks) */
+constexpr int kGangWaitSleep = 1;
 
 /* What a cell that extends a gap offers: src/ConvexAlignFast.cpp:669-675, E = (score == 0) ? 0 : score + pen with
  * pen = min(gap_ext_min, gap_ext + run * decay).  score >= 0 and pen < 0, so this is max(score + pen, score * -2^100):
@@ -522,7 +476,7 @@ enum FillMode { kFillTwoPhase = 0, kFillExact = 1, kFillChain = 2 };
 #include "cvx_fill_ring.inc"
 #undef CVX_FILL_KERNEL
 #undef CVX_FILL_TWIN
-/* the scalar twin's forms (launch_fill_twin_t: every one-wave form; gangs are not built for it) */
+/* the scalar twin's forms (every one-wave form; gangs are not built for it: pick_fill) */
 #define CVX_FILL_KERNEL fill_ring_twin_kernel
 #define CVX_FILL_TWIN true
 #include "cvx_fill_ring.inc"
@@ -1043,60 +997,81 @@ chain_reduce_kernel(const int32_t *tiles, int n_tiles, const TileRun *trun, cons
 	}
 }
 
-/* gangs: G waves per tile on one ring of 64 * 3 * G slots (two-phase with the penalty table when the scoring allows, else
- * arithmetic; and the exact pass) */
-template <int G>
-static hipError_t launch_fill_gang(const FillArgs &a, int mode, hipStream_t st) {
-	if (mode == kFillExact) hipLaunchKernelGGL((fill_ring_kernel<3, false, kFillExact, false, G>), dim3(a.list_n), dim3(64 * G), 0, st, a);
-	else if (a.pen_table) hipLaunchKernelGGL((fill_ring_kernel<3, false, kFillTwoPhase, true, G>), dim3(a.list_n), dim3(64 * G), 0, st, a);
-	else hipLaunchKernelGGL((fill_ring_kernel<3, false, kFillTwoPhase, false, G>), dim3(a.list_n), dim3(64 * G), 0, st, a);
-	return hipGetLastError();
+/* Which instantiation serves (m, gang, wrap, mode, penalty table, twin): the one place that says so -- launch_fill launches what
+ * pick_fill returns, fill_two_phase_waves_per_simd asks the runtime about it -- and the only place that instantiates a fill
+ * kernel: what is reachable here is what the code object holds, in the order in which it is first named here. */
+typedef void (*FillKernel)(const FillArgs);
+
+template <bool TWIN, int M, bool WRAP, int MODE, bool TAB = false>
+static FillKernel wave_fill_kernel() {
+	if constexpr (TWIN) return fill_ring_twin_kernel<M, WRAP, MODE, TAB>;
+	else return fill_ring_kernel<M, WRAP, MODE, TAB>;
 }
 
-/* the same ladder for the scalar twin's instantiations */
-template <int M, bool WRAP>
-static hipError_t launch_fill_twin_t(const FillArgs &a, int mode, size_t pad_lds, hipStream_t st) {
+/* one wave per tile (per task for chained tiles): chain for the rings that are a power of two, the exact pass, and two-phase with
+ * the penalty table when the scoring allows it and the runs are floats, else arithmetic */
+template <bool TWIN, int M, bool WRAP>
+static FillKernel pick_wave_fill(int mode, bool pen_table) {
 	if (mode == kFillChain) {
-		if constexpr (M == 1 || M == 2 || M == 4) hipLaunchKernelGGL((fill_ring_twin_kernel<M, WRAP, kFillChain>), dim3(a.list_n), dim3(64), pad_lds, st, a);
-		else return hipErrorInvalidValue;
-	} else if (mode == kFillExact) hipLaunchKernelGGL((fill_ring_twin_kernel<M, WRAP, kFillExact>), dim3(a.list_n), dim3(64), 0, st, a);
-	else if (!WRAP && a.pen_table) hipLaunchKernelGGL((fill_ring_twin_kernel<M, false, kFillTwoPhase, true>), dim3(a.list_n), dim3(64), 0, st, a);
-	else hipLaunchKernelGGL((fill_ring_twin_kernel<M, WRAP, kFillTwoPhase>), dim3(a.list_n), dim3(64), 0, st, a);
-	return hipGetLastError();
-}
-
-template <int M, bool WRAP>
-static hipError_t launch_fill_t(const FillArgs &a, int mode, size_t pad_lds, hipStream_t st) {
-	/* one wave per tile of the list (per task for chained tiles; pad_lds = unused dynamic LDS that
-	 * caps how many waiting tasks are resident) */
-	if (a.twin) return launch_fill_twin_t<M, WRAP>(a, mode, pad_lds, st);
-	if (mode == kFillChain) {
-		if constexpr (M == 1 || M == 2 || M == 4) hipLaunchKernelGGL((fill_ring_kernel<M, WRAP, kFillChain>), dim3(a.list_n), dim3(64), pad_lds, st, a);
-		else return hipErrorInvalidValue;
-	} else if (mode == kFillExact) hipLaunchKernelGGL((fill_ring_kernel<M, WRAP, kFillExact>), dim3(a.list_n), dim3(64), 0, st, a);
-	else if (!WRAP && a.pen_table) hipLaunchKernelGGL((fill_ring_kernel<M, false, kFillTwoPhase, true>), dim3(a.list_n), dim3(64), 0, st, a);
-	else hipLaunchKernelGGL((fill_ring_kernel<M, WRAP, kFillTwoPhase>), dim3(a.list_n), dim3(64), 0, st, a);
-	return hipGetLastError();
+		if constexpr (M == 3) return nullptr;
+		else return wave_fill_kernel<TWIN, M, WRAP, kFillChain>();
+	}
+	if (mode == kFillExact) return wave_fill_kernel<TWIN, M, WRAP, kFillExact>();
+	if (!WRAP && pen_table) return wave_fill_kernel<TWIN, M, false, kFillTwoPhase, true>();
+	return wave_fill_kernel<TWIN, M, WRAP, kFillTwoPhase>();
 }
 
 template <int M>
-static hipError_t launch_fill_w(const FillArgs &a, bool wrap, int mode, size_t pad_lds, hipStream_t st) {
-	return wrap ? launch_fill_t<M, true>(a, mode, pad_lds, st) : launch_fill_t<M, false>(a, mode, pad_lds, st);
+static FillKernel pick_wave_fill(bool wrap, int mode, bool pen_table, bool twin) {
+	if (wrap) return twin ? pick_wave_fill<true, M, true>(mode, pen_table) : pick_wave_fill<false, M, true>(mode, pen_table);
+	return twin ? pick_wave_fill<true, M, false>(mode, pen_table) : pick_wave_fill<false, M, false>(mode, pen_table);
+}
+
+/* gangs: G waves per tile on one ring of 64 * 3 * G slots, float runs, whole tiles, not for the twin */
+template <int G>
+static FillKernel pick_gang_fill(int mode, bool pen_table) {
+	if (mode == kFillExact) return fill_ring_kernel<3, false, kFillExact, false, G>;
+	if (pen_table) return fill_ring_kernel<3, false, kFillTwoPhase, true, G>;
+	return fill_ring_kernel<3, false, kFillTwoPhase, false, G>;
+}
+
+struct FillPick {
+	FillKernel kernel;      /* nullptr: a combination that is not built */
+	int threads;            /* of a workgroup */
+};
+
+static FillPick pick_fill(int m, int gang, bool wrap, int mode, bool pen_table, bool twin) {
+	FillPick p = { nullptr, 64 };
+	if (gang > 1) {
+		p.threads = 64 * gang;
+		if (m != 3 || wrap || mode == kFillChain || twin) return p;
+		p.kernel = gang == 2 ? pick_gang_fill<2>(mode, pen_table) : gang == 3 ? pick_gang_fill<3>(mode, pen_table) : nullptr;
+		return p;
+	}
+	switch (m) {
+	case 1: p.kernel = pick_wave_fill<1>(wrap, mode, pen_table, twin); break;
+	case 2: p.kernel = pick_wave_fill<2>(wrap, mode, pen_table, twin); break;
+	case 3: p.kernel = pick_wave_fill<3>(wrap, mode, pen_table, twin); break;
+	case 4: p.kernel = pick_wave_fill<4>(wrap, mode, pen_table, twin); break;
+	}
+	return p;
 }
 
 hipError_t launch_fill(int m, int gang, bool wrap, int mode, const FillArgs &a, size_t pad_lds, hipStream_t st) {
 	if (a.list_n <= 0) return hipSuccess;
-	if (gang > 1) {
-		if (m != 3 || wrap || mode == kFillChain || a.twin) return hipErrorInvalidValue;
-		return gang == 2 ? launch_fill_gang<2>(a, mode, st) : gang == 3 ? launch_fill_gang<3>(a, mode, st) : hipErrorInvalidValue;
-	}
-	switch (m) {
-	case 1: return launch_fill_w<1>(a, wrap, mode, pad_lds, st);
-	case 2: return launch_fill_w<2>(a, wrap, mode, pad_lds, st);
-	case 3: return launch_fill_w<3>(a, wrap, mode, pad_lds, st);
-	case 4: return launch_fill_w<4>(a, wrap, mode, pad_lds, st);
-	default: return hipErrorInvalidValue;
-	}
+	const FillPick p = pick_fill(m, gang, wrap, mode, a.pen_table != 0, a.twin != 0);
+	if (p.kernel == nullptr) return hipErrorInvalidValue;
+	/* pad_lds: unused dynamic LDS that caps how many waiting tasks of a chain launch are resident */
+	hipLaunchKernelGGL(p.kernel, dim3(a.list_n), dim3(p.threads), mode == kFillChain ? pad_lds : 0, st, a);
+	return hipGetLastError();
+}
+
+int fill_two_phase_waves_per_simd(int m, bool wrap, bool pen_table, bool twin) {
+	const FillPick p = pick_fill(m, 1, wrap, kFillTwoPhase, pen_table, twin);
+	int blocks = 0;      /* workgroups of one wave on a CU = its four SIMDs */
+	if (p.kernel == nullptr) return -1;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, p.kernel, p.threads, 0) != hipSuccess) { (void) hipGetLastError(); return -1; }
+	return blocks > 0 ? blocks / 4 : -1;
 }
 
 hipError_t launch_chain_reduce(const int32_t *tiles, int n_tiles, const TileRun *trun, const ChainOut *cout, TileOut *tout, hipStream_t st) {
@@ -1125,24 +1100,22 @@ hipError_t launch_plan(const RowDesc *rows, const RowSrc *rsrc, const TileIn *ti
 	return hipGetLastError();
 }
 
+/* G lanes per tile, 64 / G tiles per wave */
+template <int G>
+static void launch_backtrack_grp(const BacktrackArgs &a, const int32_t *order, int n_order, hipStream_t st) {
+	hipLaunchKernelGGL(backtrack_grp_kernel<G>, dim3((n_order + 64 / G - 1) / (64 / G)), dim3(64), 0, st, a, order, n_order);
+}
+
 hipError_t launch_backtrack(const BacktrackArgs &a, const int32_t *order, int n_order, int group, hipStream_t st) {
 	if (a.n_tiles <= 0) return hipSuccess;
-	if (group == 16 && order != nullptr) {
-		if (n_order <= 0) return hipSuccess;
-		hipLaunchKernelGGL(backtrack_grp_kernel<16>, dim3((n_order + 3) / 4), dim3(64), 0, st, a, order, n_order);   /* four tiles per wave */
-	} else if (group == 4 && order != nullptr) {
-		if (n_order <= 0) return hipSuccess;
-		hipLaunchKernelGGL(backtrack_grp_kernel<4>, dim3((n_order + 15) / 16), dim3(64), 0, st, a, order, n_order);  /* sixteen tiles per wave (CVX_TUNE_BT_GROUP=4 only) */
-	} else if (group == 8 && order != nullptr) {
-		if (n_order <= 0) return hipSuccess;
-		hipLaunchKernelGGL(backtrack_grp_kernel<8>, dim3((n_order + 7) / 8), dim3(64), 0, st, a, order, n_order);    /* eight tiles per wave */
-	} else if (group == 32 && order != nullptr) {
-		if (n_order <= 0) return hipSuccess;
-		hipLaunchKernelGGL(backtrack_grp_kernel<32>, dim3((n_order + 1) / 2), dim3(64), 0, st, a, order, n_order);   /* two tiles per wave */
-	} else {
-		const int nb = order != nullptr ? n_order : a.n_tiles;
-		if (nb <= 0) return hipSuccess;
-		hipLaunchKernelGGL(backtrack_kernel, dim3(nb), dim3(64), 0, st, a, order, nb);   /* one wave per tile */
+	const int nb = order != nullptr ? n_order : a.n_tiles;
+	if (nb <= 0) return hipSuccess;
+	switch (order != nullptr ? group : 0) {      /* (the code object holds the kernels in the order of the cases) */
+	case 16: launch_backtrack_grp<16>(a, order, n_order, st); break;
+	case 4: launch_backtrack_grp<4>(a, order, n_order, st); break;       /* (CVX_TUNE_BT_GROUP=4 only) */
+	case 8: launch_backtrack_grp<8>(a, order, n_order, st); break;
+	case 32: launch_backtrack_grp<32>(a, order, n_order, st); break;
+	default: hipLaunchKernelGGL(backtrack_kernel, dim3(nb), dim3(64), 0, st, a, order, nb);   /* one wave per tile */
 	}
 	return hipGetLastError();
 }

@@ -14,6 +14,10 @@ namespace cvx {
  * this order, on one stream), 2 chained row blocks (a.tasks, list_n = number of tasks). */
 /* gang > 1 (2 or 3; m = 3, float runs, modes 0 / 1): that many waves share the tile's ring (cvx_kernels.hip, GANG) */
 hipError_t launch_fill(int m, int gang, bool wrap, int mode, const FillArgs &a, size_t pad_lds, hipStream_t st);
+/* m, wrap, pen_table, twin: as launch_fill(m, 1, wrap, 0, ...) reads them.  Waves per SIMD of that kernel resident on the current
+ * device, as the runtime reports it, or -1 when it cannot say (an m without a whole-tile kernel, a failed query).  The schedule
+ * sizes the tail of a split class by it (tail_split, cvx_host_logic.h). */
+int fill_two_phase_waves_per_simd(int m, bool wrap, bool pen_table, bool twin);
 hipError_t launch_chain_reduce(const int32_t *tiles, int n_tiles, const TileRun *trun, const ChainOut *cout, TileOut *tout, hipStream_t st);
 /* sub-read scoring (cvx_score.hip) */
 struct ScorePair {

@@ -30,7 +30,6 @@
 #include <string>
 #include <vector>
 
-#include "cvx_fill_occupancy.h"
 #include "cvx_qry_stage.h"
 #include "cvx_rt.h"
 

@@ -59,7 +59,7 @@ def test_fast_fills_keep_scratch_free_and_their_waves(device_asm):
         waves = min(MAX_WAVES, VGPRS_PER_SIMD_LANE // vg, (LDS_PER_CU // max(lds, 1)) // 4)
         assert waves >= PARENT_WAVES[M], (name, vg, lds, waves)
         if M == 3:
-            assert waves == 7, (name, vg, lds)      # (the kernel asks for exactly seven: CVX_FILL_WAVES_TAB)
+            assert waves == 7, (name, vg, lds)      # (the kernel asks for exactly seven: fill_waves_min / fill_waves_max, cvx_kernels.hip)
     assert seen == 8
 
 
@@ -69,3 +69,27 @@ def test_fast_cell_update_has_the_clamp_bit_and_no_multiply(device_asm):
         assert clamped >= 4 * M, (name, clamped)                       # one per slot and step of the unrolled group, in either tracking phase
         assert not re.search(r"^\s+v_mul_f32\w* .*0xf1800000", body, re.M), name      # -2^100
         assert not re.search(r"^\s+v_max3_f32 v\d+, v\d+, v\d+, 0\s*$", body, re.M), name
+
+
+def _built_rule():
+    """the instantiations the launcher's selector (pick_fill, cvx_kernels.hip) reaches: (kernel, M, wrap, mode, table, gang)"""
+    two_phase, exact, chain = 0, 1, 2
+    want = set()
+    for kernel in ("16fill_ring_kernel", "21fill_ring_twin_kernel"):
+        for M in (1, 2, 3, 4):
+            for wrap in (0, 1):
+                want.add((kernel, M, wrap, two_phase, 0, 1))
+                want.add((kernel, M, wrap, exact, 0, 1))
+                if M != 3:
+                    want.add((kernel, M, wrap, chain, 0, 1))      # (chained row blocks: rings of a power of two)
+            want.add((kernel, M, 0, two_phase, 1, 1))             # the penalty table: float runs, two-phase
+    for G in (2, 3):                                              # gangs: M = 3, float runs, whole tiles, not for the twin
+        want.update({("16fill_ring_kernel", 3, 0, exact, 0, G), ("16fill_ring_kernel", 3, 0, two_phase, 0, G), ("16fill_ring_kernel", 3, 0, two_phase, 1, G)})
+    return want
+
+
+def test_code_object_holds_exactly_the_fill_kernels_of_the_rule(device_asm):
+    want = {"_ZN3cvx%sILi%dELb%dELi%dELb%dELi%dEEEvNS_8FillArgsE" % k for k in _built_rule()}
+    assert len(want) == 58
+    got = set(re.findall(r"^(_ZN3cvx(?:16fill_ring_kernel|21fill_ring_twin_kernel)I\w+): *(?:;.*)?$", device_asm, re.M))
+    assert got == want, (sorted(got - want), sorted(want - got))
