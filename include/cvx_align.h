@@ -36,6 +36,8 @@
  * cvx_job_nm_regions / cvx_nm_regions_ops / cvx_nm_regions_host  the peak finder over that profile at the top of
  *                             detectMisalignment  src/AlignmentBuffer.cpp:1143-1148,1316-1395 (device: no profile leaves HBM)
  * CVX_CREATE_NM_REGIONS / cvx_job_regions  the same regions delivered with a job's results: no text stage, no round trip
+ * CVX_CREATE_JOB_TEXT / cvx_job_texts  cvx_job_text's records and strings delivered with a job's results (external clips zero)
+ * cvx_text_reclip             externalQStart / externalQEnd put onto such a record and its CIGAR, on the host
  * cvx_sam_record_text / cvx_sam_batch  SAMWriter::DoWriteReadGeneric  src/SAMWriter.cpp:87-224 (f3: SAM record assembly)
  * cvx_sam_unmapped_text       SAMWriter::DoWriteUnmappedReadGeneric  src/SAMWriter.cpp:308-357
  * cvx_score_batch             StrippedSW::BatchScore/SingleScore  src/StrippedSW.cpp:118-203 (next-row f2)
@@ -246,7 +248,12 @@ int cvx_create(int device_id, const cvx_params *params, uint64_t max_matrix_mb, 
  * cvx_genome_decode) from a thread that blocks in them -- its stream gets the device's highest priority, so that a 0.3 ms scoring
  * kernel does not queue behind a 10 ms fill of an aligning handle in the same process.  MEASURED AND OFF: inside ngmlr the run got
  * slower with it (profiles/r06_e2e_service_prio.txt); the flag is recorded in the handle, the priority applies only with CVX_SERVICE_PRIO=1. */
-enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2, CVX_CREATE_NM_REGIONS = 4 };
+enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2, CVX_CREATE_NM_REGIONS = 4, CVX_CREATE_JOB_TEXT = 16 };
+/* CVX_CREATE_JOB_TEXT (additive, ABI 9; the value 8 is not a flag and stays refused): every job of the handle runs the device text
+ * stage (cvx_job_text with both external clips zero) behind its op compaction -- and behind the regions finder where both flags are
+ * set -- on the job's own stream, and delivers records and strings with its results: cvx_job_texts after cvx_wait, no text stream, no
+ * round trip of its own.  Combines with CVX_CREATE_SCALAR_TWIN and CVX_CREATE_NM_REGIONS; refused (CVX_ERR_ARG) together with
+ * CVX_CREATE_SERVICE.  A handle without the flag launches, allocates and returns what it always did. */
 /* CVX_CREATE_NM_REGIONS (additive, ABI 9): every job of the handle finds the low-identity regions of its tiles' NM profile
  * (cvx_nm_region below) on the device, behind its op compaction on the job's own stream, and delivers them with its results:
  * cvx_job_regions after cvx_wait, no text stage, no extra round trip, no profile anywhere.  Combines with CVX_CREATE_SCALAR_TWIN;
@@ -699,6 +706,28 @@ int cvx_format_batch_ex(int32_t n, const cvx_result *results, const uint32_t *op
  * NUL-terminated string at (*text)[text_off[i]], its MD follows that NUL. */
 int cvx_job_text(cvx_handle h, cvx_job job, const int32_t *ext_qstart, const int32_t *ext_qend,
 		cvx_alignment_text *out, uint64_t *text_off, const char **text, uint64_t *text_bytes);
+/* The job form (additive, ABI 9): records and strings of ALL tiles of a job of a CVX_CREATE_JOB_TEXT handle, as they came back
+ * with the job's results -- valid after cvx_wait and before cvx_job_release, no device call of its own.  (*recs)[n_tiles] and
+ * the strings are what cvx_job_text(h, job, NULL, NULL, ...) returns for the same job: external clips ZERO (cvx_text_reclip below
+ * puts a caller's clips on), nm_count counted; on a scalar-twin handle cigar_op_count and sv_type are CVX_NOT_WRITTEN.
+ * (*text_off)[n_tiles + 1]: tile i's CIGAR is the NUL-terminated string at (*text)[(*text_off)[i]], its MD follows that NUL; the
+ * last offset is the job's total.  All three point at page-locked memory the job owns (any of the three arguments may be NULL).
+ * CVX_ERR_ARG, with a message, on a handle created without the flag, on a job cvx_wait has not returned for and on a NULL job.
+ * The device writes the strings into an arena sized by an estimate (1.48 bytes per read row + 64 per tile); a job with more text
+ * runs the write again over a larger arena while its ops are downloaded -- cvx_job_texts_info tells: *total_bytes the text of the
+ * job, *first_capacity the bytes the arena held when the write first ran, *rewrites how often it ran again (each may be NULL). */
+int cvx_job_texts(cvx_handle h, cvx_job job, const cvx_alignment_text **recs, const uint64_t **text_off, const char **text);
+int cvx_job_texts_info(cvx_handle h, cvx_job job, uint64_t *total_bytes, uint64_t *first_capacity, int32_t *rewrites);
+/* Pure host code, no device: external clips enter only the leading and trailing S piece of the CIGAR, qstart, qend, ret and
+ * cigar_op_count.  rec / cigar: a tile formatted with both external clips zero (cvx_job_texts; cigar: all rec->cigar_len
+ * characters).  *out (may be rec) and cigar_out[cigar_cap] receive what cvx_format_alignment_ex returns for the same tile with
+ * ext_qstart / ext_qend: a piece is present iff its sum is above 0; out->cigar_len is the full length, the string is truncated
+ * to cigar_cap - 1 characters + NUL as cvx_format_alignment truncates (cigar_cap 0: nothing is written, cigar_out may be NULL).
+ * A record with ret < 0 passes through unchanged with an empty string, an op count of CVX_NOT_WRITTEN stays.  The MD string and
+ * every other field do not depend on the clips.  CVX_ERR_ARG for a NULL record, a negative capacity, or a CIGAR shorter than the
+ * record's own clips. */
+int cvx_text_reclip(const cvx_alignment_text *rec, const char *cigar, int32_t ext_qstart, int32_t ext_qend,
+		char *cigar_out, int32_t cigar_cap, cvx_alignment_text *out);
 
 /* nmPerPosition (reference src/ConvexAlignFast.cpp:76-98,186-269: one (refPosition, readPosition, nm) triple per
  * EQ / X / D column once both positions passed 16; read by detectMisalignment, src/AlignmentBuffer.cpp:1320) of the

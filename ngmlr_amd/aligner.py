@@ -24,20 +24,23 @@ DEFAULT_SCORING = dict(match=2.0, mismatch=-5.0, gap_open=-5.0, gap_extend=-5.0,
 
 class ConvexAlignHip:
     def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, scalar_twin: bool = False,
-                 nm_regions: bool = False, **scoring):
+                 nm_regions: bool = False, job_text: bool = False, **scoring):
         """scalar_twin: the handle reproduces Convex::ConvexAlign (ngmlr --nosse) instead of Convex::ConvexAlignFast
         (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h); the host text helpers of its batches follow.
         nm_regions: every job delivers the low-identity regions of its tiles with its results (CVX_CREATE_NM_REGIONS,
-        Job.regions)."""
+        Job.regions).
+        job_text: every job delivers the device text stage's records and strings with its results (CVX_CREATE_JOB_TEXT, Job.texts)."""
         self.lib = capi.load(lib_path)
         self.scalar_twin = bool(scalar_twin)
         self.nm_regions = bool(nm_regions)
+        self.job_text = bool(job_text)
         sc = dict(DEFAULT_SCORING)
         sc.update(scoring)
         self.params = capi.CvxParams(sc["match"], sc["mismatch"], sc["gap_open"], sc["gap_extend"],
                                      sc["gap_extend_min"], sc["gap_decay"])
         self.h = C.c_void_p()
         flags = (capi.CREATE_SCALAR_TWIN if self.scalar_twin else 0) | (capi.CREATE_NM_REGIONS if self.nm_regions else 0)
+        flags |= capi.CREATE_JOB_TEXT if self.job_text else 0
         if flags:
             capi.check(self.lib.cvx_create_ex(device, C.byref(self.params), max_matrix_mb, flags, C.byref(self.h)))
         else:
@@ -222,6 +225,18 @@ def nm_regions_host(triples, scan_len: int, lib=None):
     return reg, opn[0]
 
 
+def reclip(rec, cigar: bytes, ext_qstart: int, ext_qend: int, cigar_cap: Optional[int] = None, lib=None):
+    """cvx_text_reclip (host code, no device): a record (capi.CvxAlignmentText) and a CIGAR formatted with both external clips zero
+    -> (record, CIGAR bytes) as the host text stage returns them with these clips.  cigar_cap: the capacity of the output buffer
+    (None: room for everything); the record's cigar_len is the full length whatever fits."""
+    lib = lib or capi.load()
+    cap = len(cigar) + 32 if cigar_cap is None else int(cigar_cap)
+    buf = C.create_string_buffer(max(cap, 1))
+    out = capi.CvxAlignmentText()
+    capi.check(lib.cvx_text_reclip(C.byref(rec), bytes(cigar), int(ext_qstart), int(ext_qend), buf if cap > 0 else None, cap, C.byref(out)))
+    return out, (buf.value if cap > 0 else b"")
+
+
 class Job:
     """One batch travelling through the streaming form (cvx_submit / cvx_wait / cvx_job_release)."""
 
@@ -392,6 +407,46 @@ class Job:
         total, cap, again = C.c_uint64(), C.c_uint64(), C.c_int32()
         capi.check(self.al.lib.cvx_job_regions_info(self.al.h, self.j, C.byref(total), C.byref(cap), C.byref(again)))
         return {"total": int(total.value), "first_capacity": int(cap.value), "rewrites": int(again.value)}
+
+    def texts_raw(self):
+        """cvx_job_texts (a ConvexAlignHip(job_text=True) job, after wait()): records, offsets and strings as they came back with
+        the job's results, external clips zero -- no text stream and no device call.
+        -> (list of CvxAlignmentText copies, offsets uint64[n + 1], the text bytes), copied out of the job's memory"""
+        pr, po, pt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        capi.check(self.al.lib.cvx_job_texts(self.al.h, self.j, C.byref(pr), C.byref(po), C.byref(pt)))
+        n = self.n
+        off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        recs = [capi.CvxAlignmentText.from_buffer_copy(C.string_at(pr.value + i * C.sizeof(capi.CvxAlignmentText), C.sizeof(capi.CvxAlignmentText)))
+                for i in range(n)]
+        raw = C.string_at(pt.value, int(off[n])) if int(off[n]) else b""
+        return recs, off, raw
+
+    def texts(self, ext_qstart=None, ext_qend=None) -> List[dict]:
+        """-> the list of dicts Job.text() returns, from cvx_job_texts; with external clips (per tile, either may be None = zeros)
+        every tile goes through cvx_text_reclip."""
+        recs, off, raw = self.texts_raw()
+        res = []
+        for i in range(self.n):
+            t = recs[i]
+            o = int(off[i])
+            cigar = raw[o:o + t.cigar_len]
+            md = raw[o + t.cigar_len + 1:o + t.cigar_len + 1 + t.md_len]
+            if ext_qstart is not None or ext_qend is not None:
+                t, cigar = reclip(t, cigar, int(ext_qstart[i]) if ext_qstart is not None else 0,
+                                  int(ext_qend[i]) if ext_qend is not None else 0, lib=self.al.lib)
+            d = {f: getattr(t, f) for f, _ in capi.CvxAlignmentText._fields_}
+            d["score_bits"] = int(np.float32(t.score).view(np.uint32))
+            d["cigar"] = cigar.decode()
+            d["md"] = md.decode()
+            res.append(d)
+        return res
+
+    def texts_info(self) -> dict:
+        """cvx_job_texts_info: bytes of the job's text, bytes the arena held when the device first wrote it, and how often the
+        write ran again over a larger arena."""
+        total, cap, again = C.c_uint64(), C.c_uint64(), C.c_int32()
+        capi.check(self.al.lib.cvx_job_texts_info(self.al.h, self.j, C.byref(total), C.byref(cap), C.byref(again)))
+        return {"total_bytes": int(total.value), "first_capacity": int(cap.value), "rewrites": int(again.value)}
 
     def release(self) -> None:
         if self.j:

@@ -222,7 +222,7 @@ void BatchingAligner::dispatchLoop() {
 		bool const canSubmit = (int) inFlight.size() < maxFlight && textPending < maxTextAhead;
 		if (canSubmit && shouldCut(inFlight.empty())) {
 			Launch * l = new Launch();
-			l->job = 0; l->results = 0; l->ops = 0; l->failed = false; l->text = 0; l->haveRegions = false; l->submitMs = l->waitMs = 0.0;
+			l->job = 0; l->results = 0; l->ops = 0; l->failed = false; l->text = 0; l->haveRegions = false; l->haveTexts = false; l->submitMs = l->waitMs = 0.0;
 			size_t const take = std::min(queue.size(), (size_t) maxBatch);
 			l->oldestAt = oldest;
 			l->cutAt = std::chrono::steady_clock::now();
@@ -270,6 +270,7 @@ void BatchingAligner::dispatchLoop() {
 					std::chrono::steady_clock::time_point const tw = std::chrono::steady_clock::now();
 					backend->Wait(l->job, &l->results, &l->ops);
 					l->haveRegions = !deviceText && backend->Regions(l->job, l->regions);      /* (they came back inside that wait) */
+					l->haveTexts = l->haveRegions && backend->JobTexts(l->job, l->texts);      /* (as did these) */
 					if (launchTrace) {
 						std::chrono::steady_clock::time_point const t = std::chrono::steady_clock::now();
 						l->waitMs = std::chrono::duration<double, std::milli>(t - tw).count();
@@ -365,7 +366,7 @@ int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int co
 	if (!failed) {
 		try {
 			if (l->text) backend->FinishText(req.tile, *r, *l->text, (int) (r - l->results));
-			else backend->Finish(req.tile, *r, ops, l->haveRegions ? &l->regions : 0, (int) (r - l->results));
+			else backend->Finish(req.tile, *r, ops, l->haveRegions ? &l->regions : 0, (int) (r - l->results), l->haveTexts ? &l->texts : 0);
 		} catch (...) {
 			threw = true;
 		}
@@ -425,7 +426,7 @@ void SharedAligner::ThreadBegin() { if (BatchingAligner * d = currentDispatcher(
 void SharedAligner::ThreadEnd() { if (BatchingAligner * d = currentDispatcher()) d->WorkerDone(); }
 
 SharedAligner::SharedAligner(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
-		float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId, bool const scalarTwin) : shared(0), device(0), perRead(false) {
+		float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId, bool const scalarTwin, bool const jobText) : shared(0), device(0), perRead(false) {
 	std::lock_guard<std::mutex> g(g_sharedMtx);
 	perRead = g_poolAccounting;
 	/* CVX_DEVICES=k: only the first k devices.  CVX_ALIAS_DEVICES=k: deal the workers over k LOGICAL devices (own backend, own
@@ -443,7 +444,7 @@ SharedAligner::SharedAligner(int const stdOutMode, float const match, float cons
 		if (const char * e = getenv("CVX_BATCH_MAX")) maxBatch = atoi(e);
 		if (const char * e = getenv("CVX_BATCH_TIMEOUT_US")) timeoutUs = atoi(e);
 		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device, 0, scalarTwin,
-				DeviceRegions::Enabled());   /* throws without a usable device; the regions of every launch come back with its results where a binding reads them */
+				DeviceRegions::Enabled(), DeviceRegions::Enabled() && (jobText || DeviceRegions::JobText()));   /* throws without a usable device; the regions of every launch come back with its results where a binding reads them */
 		g_shared[device] = new BatchingAligner(g_backend[device], 0, maxBatch, timeoutUs);   /* workers join one by one */
 		/* with alignment contexts off the CS threads (align_pool.h) a launch waits for 256 tiles, 30 ms at most: hundreds of
 		 * contexts hide that wait, and the device sees a few large launches instead of many small ones (CVX_BATCH_TARGET /
@@ -502,6 +503,11 @@ SharedAligner::~SharedAligner() {
 			long na = 0, nr = 0, np = 0;
 			DeviceRegions::Stats(na, nr, np);
 			if (na + np > 0) fprintf(stderr, "SharedAligner: %ld alignments handed detectMisalignment %ld regions from the device, %ld their profile (CVX_DEVICE_REGIONS=0 turns that off)\n", na, nr, np);
+		}
+		{
+			long fromDevice = 0, onHost = 0;
+			ConvexAlignHip::JobTextStats(fromDevice, onHost);
+			if (DeviceRegions::Enabled() && fromDevice + onHost > 0) fprintf(stderr, "SharedAligner: %ld alignments took their CIGAR and MD from the device, %ld were formatted on the host (CVX_JOB_TEXT=0 turns that off)\n", fromDevice, onHost);
 		}
 		if (g_lastTextLaunches > 0) fprintf(stderr, "SharedAligner: text stage on the device for %ld launches (cvx_job_text + cvx_job_nm_profile), %.3f s of the dispatchers' time\n", g_lastTextLaunches, g_lastTextSeconds);
 		fprintf(stderr, "SharedAligner: library loaded at 0, first worker joined at %.2f s, last one left at %.2f s\n",

@@ -118,6 +118,8 @@ private:
 		ConvexAlignHip::JobText * text;    /* CVX_DEVICE_TEXT=1: the launch's text stage ran on the device (else 0) */
 		ConvexAlignHip::JobRegions regions; /* a backend with NmRegions(): the launch's regions, for the requests among its tiles (Finish) */
 		bool haveRegions;
+		ConvexAlignHip::JobTextView texts;  /* a backend with JobTextOn(): the launch's device-made CIGAR / MD, for the same tiles */
+		bool haveTexts;
 	};
 	ConvexAlignHip * backend;
 	std::mutex mtx;
@@ -178,7 +180,8 @@ class SharedAligner: public IAlignment {
 public:
 	SharedAligner(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = -1 /* -1: workers are dealt over all devices */,
-			bool const scalarTwin = false /* the device's shared backend in scalar-twin mode (ConvexAlignHip; one mode per process, as --nosse is) */);
+			bool const scalarTwin = false /* the device's shared backend in scalar-twin mode (ConvexAlignHip; one mode per process, as --nosse is) */,
+			bool const jobText = false /* the shared backend delivers CIGAR and MD with its results where it delivers regions (ConvexAlignHip; CVX_JOB_TEXT=1 does the same) */);
 	virtual ~SharedAligner();
 
 	virtual int GetScoreBatchSize() const { return 0; }

@@ -156,10 +156,13 @@ namespace {
 std::atomic<bool> g_regionsAnnounced(false);
 std::atomic<long> g_noteAlignments(0), g_noteRegions(0), g_profileAlignments(0);
 bool const g_deviceRegions = [] { const char * e = getenv("CVX_DEVICE_REGIONS"); return !(e && atoi(e) == 0); }();
+bool const g_jobText = [] { const char * e = getenv("CVX_JOB_TEXT"); return e && atoi(e) != 0; }();
+std::atomic<long> g_textFromDevice(0), g_textOnHost(0);
 }
 
 void DeviceRegions::Announce() { g_regionsAnnounced.store(true); }
 bool DeviceRegions::Enabled() { return g_deviceRegions && g_regionsAnnounced.load(); }
+bool DeviceRegions::JobText() { return g_jobText && Enabled(); }
 void DeviceRegions::CountNote(int regions) {
 	g_noteAlignments.fetch_add(1, std::memory_order_relaxed);
 	g_noteRegions.fetch_add(regions, std::memory_order_relaxed);
@@ -183,6 +186,11 @@ void ConvexAlignHip::WindowStats(long & windowLaunches, long & windowTiles, long
 	mixedLaunches = g_mixedLaunches.load();
 }
 
+void ConvexAlignHip::JobTextStats(long & fromDevice, long & onHost) {
+	fromDevice = g_textFromDevice.load();
+	onHost = g_textOnHost.load();
+}
+
 void ConvexAlignHip::CorridorStats(long & prepared, long & closedForm) {
 	prepared = g_prepared.load();
 	closedForm = g_closedForm.load();
@@ -190,7 +198,7 @@ void ConvexAlignHip::CorridorStats(long & prepared, long & closedForm) {
 
 ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float const mismatch,
 		float const gapOpen, float const gapExtend, float const gapExtendMin, float const gapDecay,
-		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin, bool const nmRegions) : handle(0), twin(scalarTwin), regions(nmRegions), genome(0) {
+		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin, bool const nmRegions, bool const jobText_) : handle(0), twin(scalarTwin), regions(nmRegions), jobText(jobText_), genome(0) {
 	(void) stdOutMode;
 	cvx_params p;
 	p.match = match; p.mismatch = mismatch; p.gap_open = gapOpen;
@@ -200,7 +208,8 @@ ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float co
 	if (maxMatrixMB == 0) maxMatrixMB = (unsigned long) Config.getMaxMatrixSizeMB();
 #endif
 	if (maxMatrixMB == 0) maxMatrixMB = 10000;      /* IConfig's default (src/IConfig.h:47) */
-	uint32_t const flags = (twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u) | (regions ? (uint32_t) CVX_CREATE_NM_REGIONS : 0u);
+	uint32_t const flags = (twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u) | (regions ? (uint32_t) CVX_CREATE_NM_REGIONS : 0u) |
+			(jobText ? (uint32_t) CVX_CREATE_JOB_TEXT : 0u);
 	if (cvx_create_ex(deviceId, &p, (uint64_t) maxMatrixMB, flags, &handle) != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
 		throw "ConvexAlignHip: no usable MI355X / unsupported scoring";
@@ -441,6 +450,16 @@ bool ConvexAlignHip::Regions(cvx_job job, JobRegions & jr) {
 	return true;
 }
 
+bool ConvexAlignHip::JobTexts(cvx_job job, JobTextView & jx) {
+	jx.recs = 0; jx.off = 0; jx.text = 0;
+	if (!jobText) return false;
+	if (cvx_job_texts(handle, job, &jx.recs, &jx.off, &jx.text) != CVX_OK) {
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	return true;
+}
+
 bool ConvexAlignHip::WindowRefs(cvx_job job, Tile * const * tiles, int n) {
 	int nWindows = 0;
 	for (int i = 0; i < n; ++i) nWindows += tiles[i]->window ? 1 : 0;
@@ -492,17 +511,19 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 	std::vector<Tile *> ptrs((size_t) n);
 	for (int i = 0; i < n; ++i) { callers[(size_t) i] = tiles[i].refSeq; ptrs[(size_t) i] = &tiles[i]; }
 	JobRegions jr;
-	bool haveRegions = false;
+	JobTextView jx;
+	bool haveRegions = false, haveTexts = false;
 	try {
 		(void) WindowRefs(job, ptrs.data(), n);
 		haveRegions = Regions(job, jr);
+		haveTexts = JobTexts(job, jx);
 	} catch (...) {
 		Release(job);
 		throw;
 	}
 	for (int i = 0; i < n; ++i) {
 		try {
-			Finish(tiles[i], res[i], ops, haveRegions ? &jr : 0, i);
+			Finish(tiles[i], res[i], ops, haveRegions ? &jr : 0, i, haveTexts ? &jx : 0);
 		} catch (...) {
 			/* this tile's own hard error: the caller drops this alignment and no other (src/AlignmentBuffer.cpp:454-463) */
 			tiles[i].failed = true;
@@ -515,7 +536,7 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 }
 
 /* convertCigar + flags into the caller's Align (src/ConvexAlignFast.cpp:488-539) */
-void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr, int index) const {
+void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr, int index, JobTextView const * jx) const {
 	Align & a = *t.result;
 	int const refLen = t.refLen, qryLen = t.qryLen;
 	if (noAlignment(t, r)) return;      /* (a request stays where it is for the caller's retry) */
@@ -523,6 +544,12 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 	 * (nm_triples = NULL counts the entries and writes none) and the note goes where the profile would have gone; without them
 	 * the request -- or the note an earlier call left -- is cleared and the profile is written as always */
 	bool const asNote = jr != 0 && jr->off != 0 && NmRegionsNote::Begin(a.nmPerPosition, a.nmPerPostionLength, true);
+	if (asNote && jx != 0 && jx->recs != 0) {      /* the launch brought this tile's text: nothing walks its ops */
+		g_textFromDevice.fetch_add(1, std::memory_order_relaxed);
+		FinishJobText(t, *jx, *jr, index);
+		return;
+	}
+	g_textOnHost.fetch_add(1, std::memory_order_relaxed);
 	/* (the request's buffer is a few dozen rows, and the finder's loop scans alignmentLength rows of a profile: the buffer becomes
 	 * the one the caller allocates when it does not ask, and covers alignmentLength below) */
 	bool const fromRequest = !asNote && NmRegionsNote::BeginProfile(a.nmPerPosition, a.nmPerPostionLength, qryLen);
@@ -558,6 +585,34 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 		NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr->regions + jr->off[index]) : 0;
 		NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
 	}
+	if (txt.cigar_len > a.maxBufferLength) {
+		fprintf(stderr, "CIGAR/MD buffer not long enough (%d %d > %d %d). Please report this!\n",
+				txt.cigar_len, txt.md_len, a.maxBufferLength, a.maxMdBufferLength);
+		throw 1;
+	}
+	fillAlign(t, txt);
+}
+
+void ConvexAlignHip::FinishJobText(Tile & t, JobTextView const & jx, JobRegions const & jr, int index) const {
+	Align & a = *t.result;
+	cvx_alignment_text const & rec = jx.recs[index];
+	char const * src = jx.text + jx.off[index];
+	if (rec.md_len >= a.maxMdBufferLength) {       /* checkMdBufferLength: grow with new[] */
+		int cap = a.maxMdBufferLength > 0 ? a.maxMdBufferLength : 64;
+		while (cap <= rec.md_len) cap *= 2;
+		delete[] a.pBuffer2;
+		a.pBuffer2 = new char[cap];
+		a.maxMdBufferLength = cap;
+	}
+	cvx_alignment_text txt;
+	if (cvx_text_reclip(&rec, src, t.externalQStart, t.externalQEnd, a.pBuffer1, a.maxBufferLength, &txt) != CVX_OK) {
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	memcpy(a.pBuffer2, src + rec.cigar_len + 1, (size_t) rec.md_len + 1);
+	int const count = (int) (jr.off[index + 1] - jr.off[index]);
+	NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr.regions + jr.off[index]) : 0;
+	NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
 	if (txt.cigar_len > a.maxBufferLength) {
 		fprintf(stderr, "CIGAR/MD buffer not long enough (%d %d > %d %d). Please report this!\n",
 				txt.cigar_len, txt.md_len, a.maxBufferLength, a.maxMdBufferLength);

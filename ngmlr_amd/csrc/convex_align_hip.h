@@ -32,7 +32,11 @@ public:
 	ConvexAlignHip(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = 0,
 			unsigned long const maxMatrixSizeMB = 0 /* Config.getMaxMatrixSizeMB(); 0 = the reference's default 10000 */,
-			bool const scalarTwin = false, bool const nmRegions = false);
+			bool const scalarTwin = false, bool const nmRegions = false, bool const jobText = false);
+	/* jobText: the handle is created with CVX_CREATE_JOB_TEXT -- every launch brings CIGAR, MD and the scalar fields of its tiles back
+	 * with its results (external clips zero), and Finish copies them (FinishJobText) for every tile whose request it answers with a
+	 * note instead of walking the tile's ops; a tile that wants its profile keeps the host form, in the same launch. */
+	bool JobTextOn() const { return jobText; }
 	/* nmRegions: the handle is created with CVX_CREATE_NM_REGIONS -- every launch brings the low-identity regions of its tiles back
 	 * with its results, and Finish answers a request in Align::nmPerPosition (nm_regions_note.h) with a note of them instead of
 	 * the profile.  Without it (and on the CVX_DEVICE_TEXT=1 path) a request ends as the full profile. */
@@ -114,7 +118,24 @@ public:
 	bool Regions(cvx_job job, JobRegions & jr);      /* after Wait.  false: the handle delivers none (throws 1 when one that should cannot) */
 	/* jr / index: the launch's regions and the tile's place in it.  With them a request (or an earlier note) in
 	 * Align::nmPerPosition is answered with a note and no profile is written; without them it ends as the profile */
-	void Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr = 0, int index = 0) const;
+	/* the records and strings of a finished job (cvx_job_texts: the job's page-locked memory, valid until Release); tile i's CIGAR
+	 * is the string at text[off[i]], its MD follows that NUL */
+	struct JobTextView {
+		cvx_alignment_text const * recs;
+		uint64_t const * off;
+		char const * text;
+	};
+	bool JobTexts(cvx_job job, JobTextView & jx);      /* after Wait, once per launch.  false: the handle delivers none (throws 1 when one that should cannot) */
+	/* jx: the launch's device-made text.  With it a tile that is answered with a note takes its CIGAR and MD from there
+	 * (FinishJobText) and nothing walks its ops */
+	void Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr = 0, int index = 0, JobTextView const * jx = 0) const;
+	/* what Finish leaves in the caller's Align for a tile it answers with a note, copied out of the job's text: cvx_text_reclip puts
+	 * the tile's external clips on and writes pBuffer1, the MD is a memcpy; the same growth rule for pBuffer2 and the same hard
+	 * error for a CIGAR beyond maxBufferLength as FinishText.  The caller has made sure of the alignment (r.status) and of the
+	 * note (NmRegionsNote::Begin) */
+	void FinishJobText(Tile & t, JobTextView const & jx, JobRegions const & jr, int index) const;
+	/* alignments of this process that took their CIGAR and MD from the device, and alignments Finish formatted on the host */
+	static void JobTextStats(long & fromDevice, long & onHost);
 	void Release(cvx_job job);
 	/* one line on stderr about a finished job: tiles, device stages, fill classes (CVX_LAUNCH_TRACE=1 in the dispatcher) */
 	void Trace(cvx_job job, int nTiles, double serviceMs, double waitedMs) const;
@@ -150,6 +171,7 @@ private:
 	cvx_handle handle;
 	bool twin;
 	bool regions;
+	bool jobText;
 	unsigned long maxMatrixMB;
 	std::vector<cvx_tile> packed;
 	cvx_genome genome;                     /* DeviceWindows' genome on this aligner's device (uploaded by the first launch that carries a window) */
@@ -229,6 +251,7 @@ struct DeviceReads {
 struct DeviceRegions {
 	static void Announce();                /* the binding's finder site is compiled in */
 	static bool Enabled();                 /* announced, unless CVX_DEVICE_REGIONS=0 */
+	static bool JobText();                 /* Enabled() and CVX_JOB_TEXT=1 (default 0): the handles that deliver regions deliver CIGAR and MD too */
 	/* the binding's finder site: an alignment walked `regions` regions of a note / scanned its profile */
 	static void CountNote(int regions);
 	static void CountProfile();

@@ -13,6 +13,7 @@
 
 #include "cvx_align.h"
 #include "cvx_rt_err.h"
+#include "cvx_job_text_logic.h"
 
 namespace {
 
@@ -236,6 +237,16 @@ extern "C" int cvx_format_alignment_ex(const cvx_result *r, const uint32_t *ops_
 	}
 	out->sv_type = sv;
 	return CVX_OK;
+	ABI_GUARD_END
+}
+
+/* a caller's external clips onto a record and a CIGAR formatted without them (a CVX_CREATE_JOB_TEXT job's): cvx_job_text_logic.h */
+extern "C" int cvx_text_reclip(const cvx_alignment_text *rec, const char *cigar, int32_t ext_qstart, int32_t ext_qend,
+		char *cigar_out, int32_t cigar_cap, cvx_alignment_text *out) {
+	ABI_GUARD_BEGIN
+	const int rc = cvx::text_reclip(rec, cigar, ext_qstart, ext_qend, cigar_out, cigar_cap, out);
+	if (rc != CVX_OK) cvx::set_err("cvx_text_reclip: NULL record or output, negative capacity, or a CIGAR shorter than the record's own clips");
+	return rc;
 	ABI_GUARD_END
 }
 

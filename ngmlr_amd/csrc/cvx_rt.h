@@ -18,6 +18,7 @@
 #include "cvx_host_logic.h"
 #include "cvx_launch.h"
 #include "cvx_nm_regions.h"
+#include "cvx_job_text.h"
 #include "cvx_rt_err.h"
 #include "cvx_types.h"
 
@@ -235,6 +236,15 @@ struct cvx_batch_s {
 	bool jr_on = false;              /* this run of the compute stage queued the finder */
 	uint64_t jr_cap = 0, jr_total = 0;      /* regions the arena holds; regions of the job (after stage_results) */
 	int jr_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
+	/* the device text stage run with the job's results (a CVX_CREATE_JOB_TEXT handle: queue_job_text in stage_compute, cvx_job_texts);
+	 * buffers of their own, so that a cvx_job_text call on the text stream never meets them */
+	DevBuf<TextRec> d_jtrec;
+	DevBuf<unsigned long long> d_jtoff;  /* lengths[n], offsets[n], the total, the capacity the write ran with */
+	DevBuf<uint8_t> d_jtext;
+	PinBuf h_jtrec, h_jtoff, h_jtext;    /* records and offsets[n] + total + capacity arrive with the result records, the strings with the dense ops */
+	bool jt_on = false;              /* this run of the compute stage queued the text stage */
+	uint64_t jt_cap = 0, jt_total = 0;      /* bytes the arena holds; bytes of the job's text (after stage_results) */
+	int jt_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
 	PinBuf h_win;                    /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
 	PinBuf h_refs;                   /* ... and the decoded windows back on the host (cvx_job_window_refs): the reference part of d_seq */
 	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
@@ -303,6 +313,7 @@ struct cvx_batch_s {
 		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
 		d_nmroff.release(); d_nmopen.release(); d_nmstage.release(); d_nmreg.release(); h_nmroff.release(); h_nmopen.release(); h_nmreg.release();
 		d_jroff.release(); d_jropen.release(); d_jrstage.release(); d_jrreg.release(); h_jroff.release(); h_jropen.release(); h_jrreg.release();
+		d_jtrec.release(); d_jtoff.release(); d_jtext.release(); h_jtrec.release(); h_jtoff.release(); h_jtext.release();
 		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
 		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
 		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();
@@ -377,6 +388,8 @@ struct cvx_context {
 	                            * occupancy (0: not asked yet, -1: unknown); filled by stage_compute for the classes a batch uses */
 	bool bt_per_class = true;  /* tuning knob (env CVX_TUNE_BT_PER_CLASS = 0 clears it): a batch of several fill classes walks each class behind its own fill (build_schedule) */
 	bool overlap_post = false; /* tuning knob (env CVX_TUNE_OVERLAP_POST): backtrack/finalize/compaction of batch k on their own stream, beside the fills of batch k+1 */
+	bool job_text = false;    /* cvx_create_ex(CVX_CREATE_JOB_TEXT): every job runs the device text stage behind its compaction (cvx_job_texts) */
+	uint64_t tune_job_text_cap = 0; /* tuning knob (env CVX_TUNE_JOB_TEXT_CAP, bytes; 0: job_text_first_capacity's rule): the capacity a job's first text write runs with */
 	bool nm_regions = false;  /* cvx_create_ex(CVX_CREATE_NM_REGIONS): every job finds the low-identity regions of its tiles behind its compaction (cvx_job_regions) */
 	bool scalar_twin = false; /* cvx_create_ex(CVX_CREATE_SCALAR_TWIN): the semantics of Convex::ConvexAlign (cvx_host_logic.h, fill_semantics) */
 	bool force_generic = false; /* every tile to the catch-all kernel: sse_variant, or a twin handle whose scoring lacks the rings' sign structure */

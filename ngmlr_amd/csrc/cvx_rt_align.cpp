@@ -62,6 +62,7 @@ void recycle_batch(cvx_context *h, cvx_batch_s *b) {
 	b->have_refs = false;
 	b->text_done = false;
 	b->jr_on = false;
+	b->jt_on = false;
 	b->fail_rc = CVX_OK;
 	b->fail_msg.clear();
 	if (h) {
@@ -118,6 +119,7 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	b->have_refs = false;
 	b->text_done = false;
 	b->jr_on = false;
+	b->jt_on = false;
 	b->ops_total = 0;
 	b->seq_total = L.seq_total;
 	b->n_rows = L.n_rows;
@@ -384,6 +386,39 @@ int queue_job_regions(cvx_batch_s *b, hipStream_t st, bool rewrite) {
 	return CVX_OK;
 }
 
+/* A CVX_CREATE_JOB_TEXT handle: the device text stage over the batch's op lists and its sequences in HBM (cvx_text.hip), external
+ * clips zero, queued on `st` behind the compaction with no host step in between -- the size pass, the offset scan, then the write
+ * into an arena sized by an estimate (job_text_first_capacity over the job's read rows; tune: CVX_TUNE_JOB_TEXT_CAP).  Records,
+ * offsets, total and the capacity the write ran with travel in the copies queued here, in front of the event stage_results
+ * waits for; the strings themselves with the dense ops (stage_ops).  rewrite: the arena has grown, only the write runs again. */
+int queue_job_text(cvx_batch_s *b, hipStream_t st, bool rewrite, uint64_t tune = 0) {
+	const int n = b->n;
+	const size_t n1 = (size_t) n;
+	if (!rewrite) {
+		RC_TRY(b->d_jtrec.ensure(n1));
+		RC_TRY(b->d_jtoff.ensure(2 * n1 + 8));
+		RC_TRY(b->d_jtext.ensure((size_t) job_text_first_capacity(b->n_rows, (uint64_t) n, tune)));
+		RC_TRY(b->h_jtrec.ensure(n1 * sizeof(TextRec)));
+		RC_TRY(b->h_jtoff.ensure((n1 + 2) * sizeof(unsigned long long)));
+		b->jt_cap = b->d_jtext.cap;      /* (a slot's arena never shrinks: a job the arena already holds needs no estimate) */
+		b->jt_rewrites = 0;
+	}
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.seq = b->d_seq.p; a.tin = b->d_tin.p; a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
+	a.recs = b->d_jtrec.p;
+	a.text_len = b->d_jtoff.p; a.text_off = b->d_jtoff.p + n1; a.text_total = b->d_jtoff.p + 2 * n1;
+	a.text = b->d_jtext.p;
+	a.n_tiles = n;
+	if (!rewrite) HIP_TRY(launch_job_text_size(a, st));
+	HIP_TRY(launch_job_text_bounded(a, b->jt_cap, st));
+	if (!rewrite) {
+		HIP_TRY(hipMemcpyAsync(b->h_jtoff.p, a.text_off, (n1 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(b->h_jtrec.p, b->d_jtrec.p, n1 * sizeof(TextRec), hipMemcpyDeviceToHost, st));
+	}
+	return CVX_OK;
+}
+
 /* ---- stage 3: host planning, then every kernel of the batch on `main` (+ aux); nothing waits */
 int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	const int n = b->n;
@@ -405,7 +440,14 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	b->have_ops = false;
 	b->jr_on = h->nm_regions;
 	b->jr_total = 0;
+	b->jt_on = h->job_text;
+	b->jt_total = 0;
 	if (n == 0) {
+		if (b->jt_on) {      /* cvx_job_texts of an empty job: one offset, 0 */
+			RC_TRY(b->h_jtoff.ensure(2 * sizeof(unsigned long long)));
+			memset(b->h_jtoff.p, 0, 2 * sizeof(unsigned long long));
+			b->jt_cap = 0; b->jt_rewrites = 0;
+		}
 		if (b->jr_on) {      /* cvx_job_regions of an empty job: one offset, 0 */
 			RC_TRY(b->h_jroff.ensure(2 * sizeof(unsigned long long)));
 			memset(b->h_jroff.p, 0, 2 * sizeof(unsigned long long));
@@ -591,6 +633,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, b->d_dstoff.p + n, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
 	HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, n, b->dense_cap, st));
 	if (b->jr_on) RC_TRY(queue_job_regions(b, st, false));      /* (inside the compute stage's timing: ev[3] below) */
+	if (b->jt_on) RC_TRY(queue_job_text(b, st, false, h->tune_job_text_cap));      /* (as is this) */
 	HIP_TRY(hipEventRecord(b->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(b->h_res.p, b->d_res.p, (size_t) n * sizeof(ResultRec) + sizeof(BatchSummary), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(b->ev_res, st));
@@ -613,6 +656,13 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	const BatchSummary *s = b->summary();
 	b->ops_total = s->ops_total;
 	if (b->jr_on) b->jr_total = b->h_jroff.as<unsigned long long>()[(size_t) b->n];      /* (the total sits behind the n offsets) */
+	if (b->jt_on) {
+		b->jt_total = b->h_jtoff.as<unsigned long long>()[(size_t) b->n];
+		if (h->scalar_twin) {      /* Convex::ConvexAlign stores neither field (cvx_job_text does the same to its copy) */
+			TextRec *rec = b->h_jtrec.as<TextRec>();
+			for (int i = 0; i < b->n; ++i) { rec[i].cigar_op_count = CVX_NOT_WRITTEN; rec[i].sv_type = CVX_NOT_WRITTEN; }
+		}
+	}
 	const int launches = b->timing.n_fill_launches;
 	for (int i = 0; i < launches; ++i) {
 		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
@@ -673,6 +723,22 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 		/* the regions ride in front of the dense ops, under the one wait below (a job with regions has ops) */
 		RC_TRY(b->h_jrreg.ensure((size_t) b->jr_total * sizeof(NmRegion)));
 		HIP_TRY(hipMemcpyAsync(b->h_jrreg.p, b->d_jrreg.p, (size_t) b->jr_total * sizeof(NmRegion), hipMemcpyDeviceToHost, h->s_io));
+		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
+	}
+	if (b->jt_on && b->jt_total > b->jt_cap) {
+		/* more text than the estimate (sane reads stay below it: CVX_TUNE_JOB_TEXT_CAP reaches this) -- a larger arena, and the
+		 * write alone runs again: records, lengths and offsets are still the job's */
+		RC_TRY(b->d_jtext.ensure((size_t) b->jt_total));
+		b->jt_cap = b->d_jtext.cap;
+		b->jt_rewrites += 1;
+		hipStream_t ps = b->s_run ? b->s_run : h->s_main;
+		RC_TRY(queue_job_text(b, ps, true));
+		HIP_TRY(hipStreamSynchronize(ps));
+	}
+	if (b->jt_on && b->jt_total) {
+		/* the strings ride in front of the dense ops, under the one wait below (only a job without a valid tile has text and no ops) */
+		RC_TRY(b->h_jtext.ensure((size_t) b->jt_total));
+		HIP_TRY(hipMemcpyAsync(b->h_jtext.p, b->d_jtext.p, (size_t) b->jt_total, hipMemcpyDeviceToHost, h->s_io));
 		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
 	}
 	if (b->ops_total) {

@@ -366,6 +366,39 @@ int cvx_job_regions_info(cvx_handle h, cvx_job j, uint64_t *total, uint64_t *fir
 	ABI_GUARD_END
 }
 
+/* the same for the text stage: what queue_job_text queued behind the job's compaction */
+static int job_texts_ready(const char *who, cvx_handle h, cvx_job j) {
+	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
+	if (!h->job_text) { set_err("%s: the handle was created without CVX_CREATE_JOB_TEXT", who); return CVX_ERR_ARG; }
+	if (j->state < kFinished || !j->have_ops || !j->jt_on) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
+	return CVX_OK;
+}
+
+int cvx_job_texts(cvx_handle h, cvx_job j, const cvx_alignment_text **recs, const uint64_t **text_off, const char **text) {
+	ABI_GUARD_BEGIN
+	static_assert(sizeof(TextRec) == sizeof(cvx_alignment_text), "TextRec mirrors cvx_alignment_text");
+	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the offsets leave as the scan wrote them");
+	if (recs) *recs = nullptr;
+	if (text_off) *text_off = nullptr;
+	if (text) *text = nullptr;
+	RC_TRY(job_texts_ready("cvx_job_texts", h, j));
+	if (recs) *recs = j->n > 0 ? j->h_jtrec.as<cvx_alignment_text>() : nullptr;
+	if (text_off) *text_off = j->h_jtoff.as<uint64_t>();
+	if (text) *text = j->n > 0 ? j->h_jtext.as<char>() : "";
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_job_texts_info(cvx_handle h, cvx_job j, uint64_t *total_bytes, uint64_t *first_capacity, int32_t *rewrites) {
+	ABI_GUARD_BEGIN
+	RC_TRY(job_texts_ready("cvx_job_texts_info", h, j));
+	if (total_bytes) *total_bytes = j->jt_total;
+	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jtoff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
+	if (rewrites) *rewrites = j->jt_rewrites;
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
 int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
 		uint64_t *region_off, cvx_nm_region *regions, uint64_t cap_regions, cvx_nm_open *open) {
 	ABI_GUARD_BEGIN

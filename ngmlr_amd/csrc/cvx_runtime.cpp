@@ -232,9 +232,13 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 				p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay);
 		return CVX_ERR_PARAMS;
 	}
-	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN | CVX_CREATE_NM_REGIONS)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN | CVX_CREATE_NM_REGIONS | CVX_CREATE_JOB_TEXT)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
 	if ((flags & CVX_CREATE_NM_REGIONS) && (flags & CVX_CREATE_SERVICE)) {
 		set_err("cvx_create_ex: CVX_CREATE_NM_REGIONS on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
+		return CVX_ERR_ARG;
+	}
+	if ((flags & CVX_CREATE_JOB_TEXT) && (flags & CVX_CREATE_SERVICE)) {
+		set_err("cvx_create_ex: CVX_CREATE_JOB_TEXT on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
 		return CVX_ERR_ARG;
 	}
 	/* (a scalar-twin handle runs the scalar recurrence for any scoring: rings where their sign structure holds, else the
@@ -336,6 +340,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	if (const char *e = getenv("CVX_TUNE_GANGS")) c->tune_gangs = atoi(e) != 0 && !sem.no_gangs;
 	if (const char *e = getenv("CVX_TUNE_GANG_PRIO")) c->tune_gang_prio = atoi(e) != 0;
 	if (const char *e = getenv("CVX_TUNE_LATE_MIN")) c->tune_late_min = std::max(1, atoi(e));
+	c->tune_job_text_cap = job_text_cap_knob(getenv("CVX_TUNE_JOB_TEXT_CAP"));
 	if (const char *e = getenv("CVX_TUNE_LATE_SHIFT")) c->tune_late_shift = std::min(16, std::max(0, atoi(e)));
 	/* One stream now; the seven others an aligning handle uses (upload, post, text, the fill classes' side streams and the second
 	 * set for small jobs) are created by its first alignment call (ensure_streams).  ngmlr holds 32 handles that only ever
@@ -348,6 +353,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	hipError_t e = hipSuccess;
 	c->service = (flags & CVX_CREATE_SERVICE) != 0;
 	c->nm_regions = (flags & CVX_CREATE_NM_REGIONS) != 0;
+	c->job_text = (flags & CVX_CREATE_JOB_TEXT) != 0;
 	const char *sp = getenv("CVX_SERVICE_PRIO");
 	int shared = 4;      /* CVX_SERVICE_STREAMS: streams per device the service handles of a process share (0 = one of its own per handle) */
 	if (const char *e2 = getenv("CVX_SERVICE_STREAMS")) shared = atoi(e2) > 0 ? std::min(atoi(e2), kServiceStreamsMax) : 0;

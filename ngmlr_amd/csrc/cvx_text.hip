@@ -26,6 +26,7 @@
 #include "cvx_types.h"
 #include "cvx_launch.h"
 #include "cvx_nm_regions.h"
+#include "cvx_job_text.h"
 
 namespace cvx {
 
@@ -604,6 +605,45 @@ hipError_t launch_nm_regions_bounded(const TextArgs &a, int count, const unsigne
 		unsigned long long *total, const NmRegion *stage, NmRegion *regions, unsigned long long cap, hipStream_t st) {
 	if (count <= 0) return hipSuccess;
 	hipLaunchKernelGGL(nm_regions_bounded_kernel, dim3(count), dim3(64), 0, st, a, len, off, total, stage, regions, cap);
+	return hipGetLastError();
+}
+
+/* The job form of text_kernel<true> (stage_compute on a CVX_CREATE_JOB_TEXT handle), external clips zero: the arena was sized by
+ * an estimate before anybody knew the total, so tile t writes its strings only if all of them, [off, off + len), lie below `cap`
+ * -- the tile is the unit, not the byte: a tile cut in the middle would be no use to anybody and text_tile would need a bound in
+ * every store.  total[0] is the scan's true total; total[1] = cap, the capacity this write ran with, travels to the host beside
+ * it, and a job that needs more runs the write again over a larger arena (stage_ops). */
+__global__ void __launch_bounds__(64)
+text_bounded_kernel(const TextArgs a, const unsigned long long cap) {
+	const int t = (int) blockIdx.x;
+	const int lane = (int) threadIdx.x;
+	if (t == 0 && lane == 0) a.text_total[1] = cap;
+	if (t >= a.n_tiles) return;
+	const unsigned long long at = a.text_off[t];
+	if (!job_text_tile_fits(at, a.text_len[t], cap)) return;
+	const TileOut o = a.tout[t];
+	uint8_t *cig = a.text + at;
+	if (o.status != 0) {
+		if (lane == 0) { cig[0] = 0; cig[1] = 0; }
+		return;
+	}
+	const TileIn ti = a.tin[t];
+	TextRec rec;          /* (the size pass wrote the record) */
+	text_tile<true>(lane, o, a.ops + a.trun[t].ops_off + o.ops_first, a.seq + ti.ref_off, ti.W, 0, 0, cig, cig + a.recs[t].cigar_len + 1, rec);
+}
+
+hipError_t launch_job_text_size(const TextArgs &a, hipStream_t st) {
+	if (a.n_tiles <= 0) return hipSuccess;
+	TextArgs b = a;
+	b.ext_qstart = nullptr; b.ext_qend = nullptr;
+	hipLaunchKernelGGL(text_kernel<false>, dim3(b.n_tiles), dim3(64), 0, st, b);
+	hipLaunchKernelGGL(text_scan_kernel, dim3(1), dim3(256), 0, st, b.text_len, b.text_off, b.text_total, b.n_tiles);
+	return hipGetLastError();
+}
+
+hipError_t launch_job_text_bounded(const TextArgs &a, unsigned long long cap, hipStream_t st) {
+	if (a.n_tiles <= 0) return hipSuccess;
+	hipLaunchKernelGGL(text_bounded_kernel, dim3(a.n_tiles), dim3(64), 0, st, a, cap);
 	return hipGetLastError();
 }
 
