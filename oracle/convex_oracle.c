@@ -39,6 +39,7 @@ typedef struct {
 	float mat, mis, go_read, go_ref, gext, gext_min, gdecay;
 	uint64_t max_matrix_mb; /* src/IConfig.h:47 (10000) */
 	int use_spec_fill;      /* 0: restate the SSE path that runs; 1: scalar spec */
+	int keep_dirs;          /* 1: every call leaves its direction codes for oracle_port_last_dirs */
 } oracle_t;
 
 static const cell_t EMPTY = { 0.0f, 0, OP_STOP };
@@ -512,6 +513,16 @@ int oracle_port_last_ops(int32_t *out, int32_t cap) {
 	if (out && n > 0) memcpy(out, g_last_ops, sizeof(int) * (size_t) n);
 	return g_last_nops;
 }
+/* Port-only: the direction code of every cell inside the window (0 <= x < W) that the last call's forward fill wrote, row by
+ * row in x order -- the layout of oracle_ref_fill's dump (ref_fill_wrap.cpp).  Kept only while oracle_port_keep_dirs is on
+ * (a copy of the whole matrix per call otherwise).  Returns the number of codes, copies min(that, cap). */
+static __thread int8_t *g_last_dirs; static __thread int64_t g_last_ndirs;
+void oracle_port_keep_dirs(void *h, int on) { ((oracle_t *) h)->keep_dirs = on; }
+int64_t oracle_port_last_dirs(int8_t *out, int64_t cap) {
+	int64_t n = g_last_ndirs < cap ? g_last_ndirs : cap;
+	if (out && n > 0) memcpy(out, g_last_dirs, (size_t) n);
+	return g_last_ndirs;
+}
 void oracle_port_last_fwd(int32_t out[5]) {
 	out[0] = g_last_best_x; out[1] = g_last_best_y; out[2] = g_last_ref_position;
 	out[3] = g_last_qstart; out[4] = g_last_qend;
@@ -558,6 +569,16 @@ int oracle_align(void *h, const char *ref, const char *qry,
 				: fill_sse_semantics(o, &m, &f, ref, qry);
 
 		g_last_fill_score = score;
+		g_last_ndirs = 0;
+		if (o->keep_dirs) {
+			g_last_dirs = (int8_t *) realloc(g_last_dirs, (size_t) matrixSize + 1);
+			for (int y = 0; y < m.H && y < height; ++y) {
+				int x0 = row_offset[y] > 0 ? row_offset[y] : 0;
+				int x1 = row_offset[y] + row_length[y] < m.W ? row_offset[y] + row_length[y] : m.W;
+				for (int x = x0; x < x1; ++x)
+					g_last_dirs[g_last_ndirs++] = m.dirs[m.row_base[y] + (uint64_t) (x - row_offset[y])];
+			}
+		}
 		int bc_len = 200000; /* defaultMaxBinaryCigarLength, :36 */
 		if (bc_len < m.H) bc_len = m.H + 1; /* :480-485 */
 		int *bc = (int *) malloc(sizeof(int) * (size_t) bc_len);

@@ -67,6 +67,15 @@ int oracle_align_many(const float params[6], int32_t n_threads, int32_t n,
 		const int32_t *const *row_offset, const int32_t *const *row_length,
 		oracle_align_out *outs, char *text, const uint64_t *text_off, const int32_t *text_cap, double *busy_seconds);
 
+/* The raw forward fill alone: prepare / fwdFillMatrixSSESimple / clean on an oracle_create handle (ref_fill_wrap.cpp).
+ * *score: the fill's curr_max; best: best_ref_index, best_read_index; dirs (capacity dirs_cap): the direction code of every
+ * cell inside the window, row by row in x order.  Returns the number of codes, -1 if the matrix was not allocated, -2 if
+ * dirs is too small.  Only the reference build exports this symbol; the port's counterpart is oracle_port_keep_dirs /
+ * oracle_port_last_dirs around oracle_align (convex_oracle.c). */
+int64_t oracle_ref_fill(void *h, const char *ref, const char *qry,
+		const int32_t *row_offset, const int32_t *row_length, int32_t height,
+		float *score, int32_t best[2], int8_t *dirs, int64_t dirs_cap);
+
 /* Which implementation is this: "reference" or "port". */
 const char *oracle_kind(void);
 

@@ -66,6 +66,43 @@ class Oracle:
             self.lib.oracle_port_last_fwd.argtypes = [C.c_void_p]
             self.lib.oracle_port_last_ops.argtypes = [C.c_void_p, C.c_int32]
             self.lib.oracle_port_last_ops.restype = C.c_int
+            self.lib.oracle_port_last_fill_score.restype = C.c_float
+            self.lib.oracle_port_keep_dirs.argtypes = [C.c_void_p, C.c_int]
+            self.lib.oracle_port_last_dirs.argtypes = [C.c_void_p, C.c_int64]
+            self.lib.oracle_port_last_dirs.restype = C.c_int64
+        elif hasattr(self.lib, "oracle_ref_fill"):      # (a prebuilt oracle/_ref from before the fill wrapper lacks it)
+            self.lib.oracle_ref_fill.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p, C.c_int64]
+            self.lib.oracle_ref_fill.restype = C.c_int64
+
+    def fill(self, tile):
+        """The raw forward fill of one tile, of either checker: (score_bits, best_x, best_y, dirs).  score_bits: the bits of the
+        fill's curr_max (0xBF800000, -1, when no cell scored; the best cell means nothing then); dirs: int8, the direction code
+        (src/AlignmentMatrixFast.h:15-24) of every cell inside the window, row by row in x order.  The reference: one call of
+        fwdFillMatrixSSESimple (ref_fill_wrap.cpp); the port: the fill of align(), whichever set_spec_fill selects."""
+        H = len(tile.qry)
+        W = len(tile.ref)
+        off = np.ascontiguousarray(tile.row_offset, dtype=np.int32)
+        ln = np.ascontiguousarray(tile.row_length, dtype=np.int32)
+        assert len(off) == H and len(ln) == H
+        n_cells = int(np.sum(np.maximum(np.minimum(off.astype(np.int64) + ln, W) - np.maximum(off, 0), 0)))
+        dirs = np.zeros(n_cells + 1, dtype=np.int8)
+        if self.kind == "port":
+            self.lib.oracle_port_keep_dirs(self.h, 1)
+            try:
+                self.align(tile, want_nm=False)
+            finally:
+                self.lib.oracle_port_keep_dirs(self.h, 0)
+            n = self.lib.oracle_port_last_dirs(dirs.ctypes.data, n_cells)
+            f = self.last_fwd()
+            assert n == n_cells, (n, n_cells)
+            return self.last_fill_score_bits(), f["best_x"], f["best_y"], dirs[:n_cells]
+        score = C.c_float()
+        best = (C.c_int32 * 2)()
+        n = self.lib.oracle_ref_fill(self.h, tile.ref, tile.qry, off.ctypes.data, ln.ctypes.data, H,
+                                     C.byref(score), best, dirs.ctypes.data, n_cells)
+        assert n == n_cells, (n, n_cells)
+        return int(np.float32(score.value).view(np.uint32)), best[0], best[1], dirs[:n_cells]
 
     def close(self):
         if self.h:

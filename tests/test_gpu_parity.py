@@ -368,6 +368,11 @@ def test_sse_variant_scoring(built, k):
     al = ConvexAlignHip(device=0, **sc)
     tiles = util.tile_zoo(seed=50 + k, n=60, max_w=1800) + util.edge_tiles()
     _check(al, orc, tiles)
+    if orc.kind != "port":
+        # the reference's wrapper hands out alignments only: the raw fill (score bits, best cell) of every tile, also of those
+        # validPath rejects, against the port with the same scoring (pinned to the reference's fill cell by cell in this regime
+        # by tests/test_sse_fill_pin_cpu.py)
+        _check(al, Oracle("port", params), tiles)
     if k == 0:
         # and the regime really is different: the scalar recurrence gives other answers here
         spec = Oracle("port", params)
