@@ -36,6 +36,8 @@
  * cvx_job_nm_regions / cvx_nm_regions_ops / cvx_nm_regions_host  the peak finder over that profile at the top of
  *                             detectMisalignment  src/AlignmentBuffer.cpp:1143-1148,1316-1395 (device: no profile leaves HBM)
  * CVX_CREATE_NM_REGIONS / cvx_job_regions  the same regions delivered with a job's results: no text stage, no round trip
+ * CVX_CREATE_INV_CHECKS / cvx_job_checks / cvx_inv_checks / cvx_inv_checks_host  checkForSV's two scores per region
+ *                             src/AlignmentBuffer.cpp:1158-1235 (window and read part built and scored on the device)
  * CVX_CREATE_JOB_TEXT / cvx_job_texts  cvx_job_text's records and strings delivered with a job's results (external clips zero)
  * cvx_text_reclip             externalQStart / externalQEnd put onto such a record and its CIGAR, on the host
  * cvx_sam_record_text / cvx_sam_batch  SAMWriter::DoWriteReadGeneric  src/SAMWriter.cpp:87-224 (f3: SAM record assembly)
@@ -248,7 +250,14 @@ int cvx_create(int device_id, const cvx_params *params, uint64_t max_matrix_mb, 
  * cvx_genome_decode) from a thread that blocks in them -- its stream gets the device's highest priority, so that a 0.3 ms scoring
  * kernel does not queue behind a 10 ms fill of an aligning handle in the same process.  MEASURED AND OFF: inside ngmlr the run got
  * slower with it (profiles/r06_e2e_service_prio.txt); the flag is recorded in the handle, the priority applies only with CVX_SERVICE_PRIO=1. */
-enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2, CVX_CREATE_NM_REGIONS = 4, CVX_CREATE_JOB_TEXT = 16 };
+enum { CVX_CREATE_SERVICE = 1, CVX_CREATE_SCALAR_TWIN = 2, CVX_CREATE_NM_REGIONS = 4, CVX_CREATE_JOB_TEXT = 16, CVX_CREATE_INV_CHECKS = 32 };
+/* CVX_CREATE_INV_CHECKS (additive, ABI 9): every job of the handle that was submitted WITH A GENOME (cvx_submit_windows, or
+ * cvx_submit_segments with g) scores the inversion check of each of its regions (cvx_inv_check below: checkForSV's two
+ * StrippedSW::SingleScore calls) on the device, behind the regions finder on the job's own stream, and delivers the records with
+ * the regions: cvx_job_checks after cvx_wait, no round trip of its own.  The genome has to stay alive until cvx_wait has returned
+ * for the job.  Requires CVX_CREATE_NM_REGIONS (CVX_ERR_ARG without it); combines with CVX_CREATE_SCALAR_TWIN and
+ * CVX_CREATE_JOB_TEXT; refused (CVX_ERR_ARG) together with CVX_CREATE_SERVICE.  A job submitted without a genome has no checks.
+ * A handle without the flag launches, allocates and returns what it always did. */
 /* CVX_CREATE_JOB_TEXT (additive, ABI 9; the value 8 is not a flag and stays refused): every job of the handle runs the device text
  * stage (cvx_job_text with both external clips zero) behind its op compaction -- and behind the regions finder where both flags are
  * set -- on the job's own stream, and delivers records and strings with its results: cvx_job_texts after cvx_wait, no text stream, no
@@ -814,6 +823,42 @@ int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const
  * written, CVX_ERR_CAPACITY when cap is smaller -- or regions == NULL (cap 0): the count and open only.  open may be NULL. */
 int cvx_nm_regions_host(const int32_t *triples, int64_t n_entries, int64_t scan_len, cvx_nm_region *regions, int64_t cap,
 		int64_t *n_regions, cvx_nm_open *open);
+
+/* The inversion check of a region (ABI 9, additive): what AlignmentBuffer::checkForSV (reference src/AlignmentBuffer.cpp:1158-1235)
+ * computes for every region the finder hands it, up to the two scores its decision reads (:1217-1227).  For a region of a tile
+ * whose read has H = strlen(fullReadSeq) = qry_len characters, whose window starts at P = ref_position (interval->onRefStart) and
+ * whose result has O = cvx_result.ref_position (Align::PositionOffset), in int arithmetic as at :1360-1362:
+ *   midRef = (ref_start + ref_stop) / 2, midRead = (read_start + read_stop) / 2, invLen = abs(ref_stop - ref_start);
+ *   invLen <= 10                                     CVX_CHECK_TOO_SHORT, nothing is scored;
+ *   not (50 <= midRead && midRead + 50 < H)          CVX_CHECK_NO_READ, nothing is scored;
+ *   window = DecodeRefSequence(buf, 0, P + O + midRef - 250 - invLen / 2, invLen + 500): cvx_score_window's rule, the position
+ *   in uint64 wrap-around arithmetic; where it returns false the reference scores against the zeroed buffer:
+ *                                                    CVX_CHECK_NO_WINDOW, the scores of ("", read part);
+ *   query = qry[midRead - 50 .. midRead + 50), and its reverse complement by computeReverseSeq / cplBase (:1117-1141);
+ *   score_fwd, score_rev = what cvx_score_batch returns for (window, query) and (window, reverse complement), the -1.0f of a
+ *   window of 99 999 characters or more included                          CVX_CHECK_SCORED.
+ * Wherever nothing is scored both scores are 0.0f, checkForSV's initial value.  window_chars = strlen of the window scored
+ * (0 for every other status). */
+typedef struct { float score_fwd, score_rev; int32_t status; int32_t window_chars; } cvx_inv_check;
+enum { CVX_CHECK_SCORED = 0, CVX_CHECK_TOO_SHORT = 1, CVX_CHECK_NO_READ = 2, CVX_CHECK_NO_WINDOW = 3 };
+/* The job form: the checks of ALL regions of a job of a CVX_CREATE_INV_CHECKS handle, parallel to cvx_job_regions' regions, as
+ * they came back with them -- valid after cvx_wait and before cvx_job_release, no device call of its own.  *checks = NULL for a
+ * job that was submitted without a genome and for a job without a region.  CVX_ERR_ARG, with a message, on a handle created
+ * without the flag and on a job cvx_wait has not returned for. */
+int cvx_job_checks(cvx_handle h, cvx_job job, const cvx_inv_check **checks);
+/* The same kernel over regions the caller holds (the twin of cvx_nm_regions_ops): tile i has the query qrys[i] of qry_len[i]
+ * characters, ref_position[i], position_offset[i] and the regions regions[region_off[i] .. region_off[i + 1]); checks: room for
+ * region_off[n_tiles] records.  Synchronous; any handle serves.  *kernel_ms (may be NULL): the kernel's own duration.
+ * CVX_ERR_ARG for offsets that do not start at 0 or descend, a negative qry_len, or g on another device than h. */
+int cvx_inv_checks(cvx_handle h, cvx_genome g, int32_t n_tiles, const char *const *qrys, const int32_t *qry_len,
+		const uint64_t *ref_position, const int32_t *position_offset,
+		const uint64_t *region_off, const cvx_nm_region *regions, cvx_inv_check *checks, double *kernel_ms);
+/* The rule on the host, from an encoded genome (cvx_genome_encode's output or ngmlr's own binRef): the window decoded statement
+ * by statement, the full gapped recurrence of the scorer.  Pure host code, no device needed. */
+int cvx_inv_checks_host(const uint8_t *bin_ref, uint64_t n_nibbles, const uint64_t *start_table, int32_t n_starts,
+		int32_t n_tiles, const char *const *qrys, const int32_t *qry_len,
+		const uint64_t *ref_position, const int32_t *position_offset,
+		const uint64_t *region_off, const cvx_nm_region *regions, cvx_inv_check *checks);
 
 /* ---- SAM record assembly (reference src/SAMWriter.cpp:87-224, :308-357) ----
  *

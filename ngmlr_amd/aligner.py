@@ -24,16 +24,19 @@ DEFAULT_SCORING = dict(match=2.0, mismatch=-5.0, gap_open=-5.0, gap_extend=-5.0,
 
 class ConvexAlignHip:
     def __init__(self, device: int = 0, max_matrix_mb: int = 10000, lib_path: str = None, scalar_twin: bool = False,
-                 nm_regions: bool = False, job_text: bool = False, **scoring):
+                 nm_regions: bool = False, job_text: bool = False, inv_checks: bool = False, **scoring):
         """scalar_twin: the handle reproduces Convex::ConvexAlign (ngmlr --nosse) instead of Convex::ConvexAlignFast
         (CVX_CREATE_SCALAR_TWIN, include/cvx_align.h); the host text helpers of its batches follow.
         nm_regions: every job delivers the low-identity regions of its tiles with its results (CVX_CREATE_NM_REGIONS,
         Job.regions).
-        job_text: every job delivers the device text stage's records and strings with its results (CVX_CREATE_JOB_TEXT, Job.texts)."""
+        job_text: every job delivers the device text stage's records and strings with its results (CVX_CREATE_JOB_TEXT, Job.texts).
+        inv_checks: every job submitted with a genome delivers the inversion check of each of its regions with them
+        (CVX_CREATE_INV_CHECKS, Job.checks); needs nm_regions."""
         self.lib = capi.load(lib_path)
         self.scalar_twin = bool(scalar_twin)
         self.nm_regions = bool(nm_regions)
         self.job_text = bool(job_text)
+        self.inv_checks_on = bool(inv_checks)
         sc = dict(DEFAULT_SCORING)
         sc.update(scoring)
         self.params = capi.CvxParams(sc["match"], sc["mismatch"], sc["gap_open"], sc["gap_extend"],
@@ -41,6 +44,7 @@ class ConvexAlignHip:
         self.h = C.c_void_p()
         flags = (capi.CREATE_SCALAR_TWIN if self.scalar_twin else 0) | (capi.CREATE_NM_REGIONS if self.nm_regions else 0)
         flags |= capi.CREATE_JOB_TEXT if self.job_text else 0
+        flags |= capi.CREATE_INV_CHECKS if self.inv_checks_on else 0
         if flags:
             capi.check(self.lib.cvx_create_ex(device, C.byref(self.params), max_matrix_mb, flags, C.byref(self.h)))
         else:
@@ -187,6 +191,16 @@ class ConvexAlignHip:
         capi.check(lib.cvx_nm_regions_ops(self.h, n, res, arena.ctypes.data, len(arena), off.ctypes.data, reg.ctypes.data, len(reg), opn.ctypes.data))
         return off, reg, opn
 
+    def inv_checks(self, genome: "Genome", qrys: Sequence[bytes], ref_positions, position_offsets, region_off, regions):
+        """cvx_inv_checks: checkForSV's two scores for regions the caller holds, scored on the device against the resident genome
+        (the kernel a ConvexAlignHip(inv_checks=True) job runs behind its regions finder).  qrys: the tiles' reads;
+        ref_positions / position_offsets per tile; region_off uint64[n + 1] and regions int32[r, 4] as Job.regions() returns them.
+        -> (checks INV_CHECK_DTYPE[r], the kernel's ms)"""
+        call, chk = _inv_checks_call(qrys, ref_positions, position_offsets, region_off, regions)
+        ms = C.c_double()
+        capi.check(call(lambda *io: self.lib.cvx_inv_checks(self.h, genome.g, *io, C.byref(ms))))
+        return chk, float(ms.value)
+
     # ------------------------------------------------------------------ reference-shaped API
     def batch_align(self, tiles: Sequence, want_nm: bool = True, closed_form: bool = False) -> List[dict]:
         """N x SingleAlign: returns one Align-like dict per tile (keys = the Align fields)."""
@@ -208,6 +222,39 @@ assert RESULT_DTYPE.itemsize == C.sizeof(capi.CvxResult)
 # cvx_nm_open: the state detectMisalignment's peak finder ends in; a region is (ref_start, ref_stop, read_start, read_stop)
 NM_OPEN_DTYPE = np.dtype([("open", np.int32), ("distance", np.int32), ("region", np.int32, (4,))])
 assert NM_OPEN_DTYPE.itemsize == C.sizeof(capi.CvxNmOpen)
+
+
+# cvx_inv_check: checkForSV's two scores for one region, capi.CHECK_* in status
+INV_CHECK_DTYPE = np.dtype([("score_fwd", np.float32), ("score_rev", np.float32), ("status", np.int32), ("window_chars", np.int32)])
+assert INV_CHECK_DTYPE.itemsize == C.sizeof(capi.CvxInvCheck)
+
+
+def _inv_checks_call(qrys, ref_positions, position_offsets, region_off, regions):
+    """the tile and region arguments both stand-alone check entries take -> (call(entry) -> rc, the records' array)"""
+    n = len(qrys)
+    arr = (C.c_char_p * max(n, 1))(*[bytes(q) for q in qrys])
+    ql = np.array([len(q) for q in qrys], dtype=np.int32)
+    pos = np.ascontiguousarray(ref_positions, dtype=np.uint64)
+    po = np.ascontiguousarray(position_offsets, dtype=np.int32)
+    off = np.ascontiguousarray(region_off, dtype=np.uint64)
+    reg = np.ascontiguousarray(regions, dtype=np.int32).reshape(-1, 4)
+    assert len(pos) == n and len(po) == n and len(off) == n + 1 and int(off[n]) == len(reg), "one position and offset per tile, region_off[n] regions"
+    chk = np.zeros(len(reg), dtype=INV_CHECK_DTYPE)
+
+    def call(entry):
+        return entry(n, arr, ql.ctypes.data, pos.ctypes.data, po.ctypes.data, off.ctypes.data, reg.ctypes.data, chk.ctypes.data)
+    return call, chk
+
+
+def inv_checks_host(binref, nibbles, starts, qrys, ref_positions, position_offsets, region_off, regions, lib=None):
+    """cvx_inv_checks_host: the same records from an encoded genome on the host (no device): the window decoded statement by
+    statement, the scorer's full recurrence.  -> checks INV_CHECK_DTYPE[r]"""
+    lib = lib or capi.load()
+    b = np.ascontiguousarray(binref, dtype=np.uint8)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    call, chk = _inv_checks_call(qrys, ref_positions, position_offsets, region_off, regions)
+    capi.check(call(lambda *io: lib.cvx_inv_checks_host(b.ctypes.data, int(nibbles), st.ctypes.data, len(st), *io)))
+    return chk
 
 
 def nm_regions_host(triples, scan_len: int, lib=None):
@@ -400,6 +447,17 @@ class Job:
         opn = (np.ctypeslib.as_array(C.cast(pn, C.POINTER(C.c_uint8)), shape=(n * NM_OPEN_DTYPE.itemsize,)).view(NM_OPEN_DTYPE).copy()
                if n else np.zeros(0, dtype=NM_OPEN_DTYPE))
         return off, reg, opn
+
+    def checks(self):
+        """cvx_job_checks (a ConvexAlignHip(nm_regions=True, inv_checks=True) job, after wait()): the inversion check of every
+        region, parallel to regions()' regions, as it came back with them -- no device call.
+        -> INV_CHECK_DTYPE[r], copied out of the job's memory; None for a job without a genome or without a region"""
+        pc = C.c_void_p()
+        capi.check(self.al.lib.cvx_job_checks(self.al.h, self.j, C.byref(pc)))
+        if not pc.value:
+            return None
+        r = self.regions_info()["total"]
+        return np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_uint8)), shape=(r * INV_CHECK_DTYPE.itemsize,)).view(INV_CHECK_DTYPE).copy()
 
     def regions_info(self) -> dict:
         """cvx_job_regions_info: regions of the job, regions the arena held when the device first wrote them, and how often

@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CVX_LIB") or os.path.join(HERE, "libcvxalign.so")   # CVX_LIB: A/B builds while tuning
 
 CVX_OK = 0
-CREATE_SERVICE, CREATE_SCALAR_TWIN, CREATE_NM_REGIONS, CREATE_JOB_TEXT = 1, 2, 4, 16      # cvx_create_ex flags (8 is none)
+CREATE_SERVICE, CREATE_SCALAR_TWIN, CREATE_NM_REGIONS, CREATE_JOB_TEXT, CREATE_INV_CHECKS = 1, 2, 4, 16, 32      # cvx_create_ex flags (8 is none)
+CHECK_SCORED, CHECK_TOO_SHORT, CHECK_NO_READ, CHECK_NO_WINDOW = 0, 1, 2, 3      # cvx_inv_check.status
 FORMAT_SCALAR_TWIN = 1                         # cvx_format_alignment_ex / cvx_format_batch_ex flags
 NOT_WRITTEN = -1                               # cigar_op_count / sv_type of the scalar twin's text stage
 STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS, STAGE_SEARCH_SCORE, STAGE_SEGMENTS = 0, 1, 2, 3, 4, 5      # cvx_stage_kernel_ms
@@ -38,7 +39,8 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_score_submit", "cvx_score_poll", "cvx_score_wait", "cvx_format_alignment_ex", "cvx_format_batch_ex",
            "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len",
            "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes",
-           "cvx_handle_pen_table", "cvx_job_regions", "cvx_job_regions_info", "cvx_job_texts", "cvx_job_texts_info", "cvx_text_reclip")
+           "cvx_handle_pen_table", "cvx_job_regions", "cvx_job_regions_info", "cvx_job_texts", "cvx_job_texts_info", "cvx_text_reclip",
+           "cvx_job_checks", "cvx_inv_checks", "cvx_inv_checks_host")
 
 
 class CvxParams(C.Structure):
@@ -99,6 +101,13 @@ class CvxNmRegion(C.Structure):
 
 class CvxNmOpen(C.Structure):
     _fields_ = [("open", C.c_int32), ("distance", C.c_int32), ("r", CvxNmRegion)]
+
+
+class CvxInvCheck(C.Structure):
+    _fields_ = [("score_fwd", C.c_float), ("score_rev", C.c_float), ("status", C.c_int32), ("window_chars", C.c_int32)]
+
+
+assert C.sizeof(CvxInvCheck) == 16
 
 
 class CvxSamOther(C.Structure):
@@ -222,6 +231,11 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_text_reclip.argtypes = [C.POINTER(CvxAlignmentText), C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(CvxAlignmentText)]
     lib.cvx_nm_regions_ops.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.cvx_nm_regions_host.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
+    # (n_tiles, qrys, qry_len, ref_position, position_offset, region_off, regions, checks) of both stand-alone check entries
+    chk_io = [C.c_int32, C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cvx_job_checks.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.cvx_inv_checks.argtypes = [C.c_void_p, C.c_void_p] + chk_io + [C.POINTER(C.c_double)]
+    lib.cvx_inv_checks_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32] + chk_io
     lib.cvx_sam_record_text.argtypes = [C.POINTER(CvxSamRecord), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.cvx_sam_unmapped_text.argtypes = [C.POINTER(CvxSamUnmapped), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.cvx_sam_batch.argtypes = [C.c_int32, C.POINTER(CvxSamRecord), C.c_void_p, C.c_uint64, C.c_void_p]

@@ -16,6 +16,7 @@
 
 #include "cvx_align.h"
 #include "cvx_host_logic.h"
+#include "cvx_inv_checks_dev.h"
 #include "cvx_launch.h"
 #include "cvx_nm_regions.h"
 #include "cvx_job_text.h"
@@ -236,6 +237,13 @@ struct cvx_batch_s {
 	bool jr_on = false;              /* this run of the compute stage queued the finder */
 	uint64_t jr_cap = 0, jr_total = 0;      /* regions the arena holds; regions of the job (after stage_results) */
 	int jr_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
+	/* the inversion checks of those regions (a CVX_CREATE_INV_CHECKS handle, a job submitted with a genome: inv_checks_kernel behind the
+	 * finder's write in queue_job_regions, cvx_job_checks): one record per region of the arena, to the host with the regions */
+	DevBuf<InvCheck> d_jrchk;
+	PinBuf h_jrchk;
+	const uint8_t *jc_bin = nullptr; /* the genome the job was submitted with (its owner keeps it alive until cvx_wait), NULL: none, or no flag */
+	uint64_t jc_L = 0;               /* its GetConcatRefLen() */
+	bool jc_on = false;              /* this run of the compute stage queued the checks */
 	/* the device text stage run with the job's results (a CVX_CREATE_JOB_TEXT handle: queue_job_text in stage_compute, cvx_job_texts);
 	 * buffers of their own, so that a cvx_job_text call on the text stream never meets them */
 	DevBuf<TextRec> d_jtrec;
@@ -313,6 +321,7 @@ struct cvx_batch_s {
 		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
 		d_nmroff.release(); d_nmopen.release(); d_nmstage.release(); d_nmreg.release(); h_nmroff.release(); h_nmopen.release(); h_nmreg.release();
 		d_jroff.release(); d_jropen.release(); d_jrstage.release(); d_jrreg.release(); h_jroff.release(); h_jropen.release(); h_jrreg.release();
+		d_jrchk.release(); h_jrchk.release();
 		d_jtrec.release(); d_jtoff.release(); d_jtext.release(); h_jtrec.release(); h_jtoff.release(); h_jtext.release();
 		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
 		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
@@ -391,6 +400,7 @@ struct cvx_context {
 	bool job_text = false;    /* cvx_create_ex(CVX_CREATE_JOB_TEXT): every job runs the device text stage behind its compaction (cvx_job_texts) */
 	uint64_t tune_job_text_cap = 0; /* tuning knob (env CVX_TUNE_JOB_TEXT_CAP, bytes; 0: job_text_first_capacity's rule): the capacity a job's first text write runs with */
 	bool nm_regions = false;  /* cvx_create_ex(CVX_CREATE_NM_REGIONS): every job finds the low-identity regions of its tiles behind its compaction (cvx_job_regions) */
+	bool inv_checks = false;  /* cvx_create_ex(CVX_CREATE_INV_CHECKS): a job submitted with a genome scores the inversion check of every region behind the finder (cvx_job_checks) */
 	bool scalar_twin = false; /* cvx_create_ex(CVX_CREATE_SCALAR_TWIN): the semantics of Convex::ConvexAlign (cvx_host_logic.h, fill_semantics) */
 	bool force_generic = false; /* every tile to the catch-all kernel: sse_variant, or a twin handle whose scoring lacks the rings' sign structure */
 	bool sse_variant = false; /* scoring outside the regime where the reference's SSE path equals the scalar recurrence:

@@ -62,6 +62,7 @@ void recycle_batch(cvx_context *h, cvx_batch_s *b) {
 	b->have_refs = false;
 	b->text_done = false;
 	b->jr_on = false;
+	b->jc_on = false;
 	b->jt_on = false;
 	b->fail_rc = CVX_OK;
 	b->fail_msg.clear();
@@ -119,6 +120,9 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 	b->have_refs = false;
 	b->text_done = false;
 	b->jr_on = false;
+	b->jc_on = false;
+	b->jc_bin = (h->inv_checks && genome && n > 0) ? genome->d_bin.p : nullptr;      /* (then d_win holds every tile's ref_position) */
+	b->jc_L = genome ? score_windows_concat_len(genome->n_nibbles) : 0;
 	b->jt_on = false;
 	b->ops_total = 0;
 	b->seq_total = L.seq_total;
@@ -379,6 +383,20 @@ int queue_job_regions(cvx_batch_s *b, hipStream_t st, bool rewrite) {
 	unsigned long long *d_len = b->d_jroff.p, *d_off = b->d_jroff.p + n1, *d_total = d_off + n1;
 	if (!rewrite) HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_off, d_total, b->d_jropen.p, b->d_jrstage.p, st));
 	HIP_TRY(launch_nm_regions_bounded(a, n, d_len, d_off, d_total, b->d_jrstage.p, b->d_jrreg.p, b->jr_cap, st));
+	if (b->jc_on) {
+		/* the checks of whatever the write has just put into the arena, behind it on the same stream: the total is the device's
+		 * (d_off[n], right behind the offsets), so the first launch covers the arena; a rewrite knows it and runs over the grown
+		 * arena again, all records */
+		RC_TRY(b->d_jrchk.ensure((size_t) b->jr_cap));
+		InvCheckArgs c;
+		memset(&c, 0, sizeof(c));
+		c.bin = b->jc_bin; c.L = b->jc_L;
+		c.seq = b->d_seq.p; c.tin = b->d_tin.p; c.win = b->d_win.p;
+		c.rec = reinterpret_cast<const ResultRec *>(b->d_res.p);
+		c.off = d_off; c.regions = b->d_jrreg.p; c.checks = b->d_jrchk.p;
+		c.cap = b->jr_cap; c.n_tiles = n;
+		HIP_TRY(launch_inv_checks(c, rewrite ? std::min<unsigned long long>(b->jr_total, b->jr_cap) : b->jr_cap, st));
+	}
 	if (!rewrite) {
 		HIP_TRY(hipMemcpyAsync(b->h_jroff.p, d_off, (n1 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(b->h_jropen.p, b->d_jropen.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
@@ -440,6 +458,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	b->have_ops = false;
 	b->jr_on = h->nm_regions;
 	b->jr_total = 0;
+	b->jc_on = b->jr_on && b->jc_bin != nullptr && n > 0;
 	b->jt_on = h->job_text;
 	b->jt_total = 0;
 	if (n == 0) {
@@ -723,6 +742,10 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 		/* the regions ride in front of the dense ops, under the one wait below (a job with regions has ops) */
 		RC_TRY(b->h_jrreg.ensure((size_t) b->jr_total * sizeof(NmRegion)));
 		HIP_TRY(hipMemcpyAsync(b->h_jrreg.p, b->d_jrreg.p, (size_t) b->jr_total * sizeof(NmRegion), hipMemcpyDeviceToHost, h->s_io));
+		if (b->jc_on) {      /* ... and their checks beside them */
+			RC_TRY(b->h_jrchk.ensure((size_t) b->jr_total * sizeof(InvCheck)));
+			HIP_TRY(hipMemcpyAsync(b->h_jrchk.p, b->d_jrchk.p, (size_t) b->jr_total * sizeof(InvCheck), hipMemcpyDeviceToHost, h->s_io));
+		}
 		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
 	}
 	if (b->jt_on && b->jt_total > b->jt_cap) {

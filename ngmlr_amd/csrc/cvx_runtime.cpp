@@ -232,13 +232,21 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 				p->match, p->mismatch, p->gap_open, p->gap_extend, p->gap_extend_min, p->gap_decay);
 		return CVX_ERR_PARAMS;
 	}
-	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN | CVX_CREATE_NM_REGIONS | CVX_CREATE_JOB_TEXT)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
+	if (flags & ~(uint32_t) (CVX_CREATE_SERVICE | CVX_CREATE_SCALAR_TWIN | CVX_CREATE_NM_REGIONS | CVX_CREATE_JOB_TEXT | CVX_CREATE_INV_CHECKS)) { set_err("cvx_create_ex: unknown flags 0x%x", flags); return CVX_ERR_ARG; }
 	if ((flags & CVX_CREATE_NM_REGIONS) && (flags & CVX_CREATE_SERVICE)) {
 		set_err("cvx_create_ex: CVX_CREATE_NM_REGIONS on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
 		return CVX_ERR_ARG;
 	}
 	if ((flags & CVX_CREATE_JOB_TEXT) && (flags & CVX_CREATE_SERVICE)) {
 		set_err("cvx_create_ex: CVX_CREATE_JOB_TEXT on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
+		return CVX_ERR_ARG;
+	}
+	if ((flags & CVX_CREATE_INV_CHECKS) && (flags & CVX_CREATE_SERVICE)) {
+		set_err("cvx_create_ex: CVX_CREATE_INV_CHECKS on a CVX_CREATE_SERVICE handle (a service handle runs no alignment jobs)");
+		return CVX_ERR_ARG;
+	}
+	if ((flags & CVX_CREATE_INV_CHECKS) && !(flags & CVX_CREATE_NM_REGIONS)) {
+		set_err("cvx_create_ex: CVX_CREATE_INV_CHECKS without CVX_CREATE_NM_REGIONS (the checks are those of the job's regions)");
 		return CVX_ERR_ARG;
 	}
 	/* (a scalar-twin handle runs the scalar recurrence for any scoring: rings where their sign structure holds, else the
@@ -353,6 +361,7 @@ int cvx_create_ex(int device_id, const cvx_params *p, uint64_t max_matrix_mb, ui
 	hipError_t e = hipSuccess;
 	c->service = (flags & CVX_CREATE_SERVICE) != 0;
 	c->nm_regions = (flags & CVX_CREATE_NM_REGIONS) != 0;
+	c->inv_checks = (flags & CVX_CREATE_INV_CHECKS) != 0;
 	c->job_text = (flags & CVX_CREATE_JOB_TEXT) != 0;
 	const char *sp = getenv("CVX_SERVICE_PRIO");
 	int shared = 4;      /* CVX_SERVICE_STREAMS: streams per device the service handles of a process share (0 = one of its own per handle) */
