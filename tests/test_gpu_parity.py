@@ -436,7 +436,10 @@ def test_runtime_knobs_do_not_change_results(built, port_oracle, monkeypatch, en
     """Every lanes-per-tile setting of the backtrack (the default picks 8 / 16 / 32 / 64 by the number of tiles walked together; -1: round 4's rule), the
     post-fill overlap, and one walk behind all fills instead of one per fill class (the default for a batch of several
     classes, as this one is): same alignments.  A batch of > 4096 tiles so that the grouped kernels really run,
-    chained and whole tiles mixed, a few reads much longer than the rest."""
+    chained and whole tiles mixed, a few reads much longer than the rest.
+    A random batch: at 15 % error a diagonal run is about 7 cells long, so the edges of a form's own geometry (a gap at lane 0 or
+    G - 1 of a probe, a run as long as the probe, a deletion that ends at the edge of a direction word, ...) are met here by
+    chance only.  tests/test_gpu_walk_forms.py pins every form at those edges on script-written tiles."""
     from ngmlr_amd import synth
     from ngmlr_amd.aligner import ConvexAlignHip
     for k, v in env.items():
