@@ -464,6 +464,65 @@ int cvx_job_zero_copy_bytes(cvx_job job, uint64_t *bytes);
 int cvx_stage_segments_host(int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
 		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used);
 
+/* The corridor retry ladder of AlignmentBuffer::computeAlignment inside one job (additive to ABI 9; reference
+ * src/AlignmentBuffer.cpp:259-425).  When an attempt is invalid the reference rebuilds the corridor at multiplier 2, 3, ... and
+ * aligns again, up to five times.  A tile of a ladder job carries what that loop reads instead of one corridor, and the library
+ * climbs by itself: rung 1 is an ordinary job; behind a rung's result records ladder_next_kernel (cvx_ladder.hip) reads every
+ * live tile's status, decides with the rule below and writes, compacted, the next rung's corridor and tile records; the plan
+ * kernel runs over that list, its records come back the way a job's plan does, and the host queues the rung's fills and walks
+ * with the unchanged schedule builder.  A rung no tile climbs to ends the job.  No sequence byte is uploaded, packed, copied or
+ * decoded again for a later rung; the device never waits between rungs (the host's only waits are on the plan read-back, polled
+ * from cvx_submit / cvx_job_poll, blocking only inside cvx_wait).
+ *
+ *   cvx_ladder        corridor = computeAlignment's `corridor` argument before the clamp at :266; left / right =
+ *                     getCorridorEndpointsWithAnchors' corridorLeft / corridorRight after :178-182 and before the multiplier
+ *                     (:184-185), read only with CVX_LADDER_ANCHORS (interval->anchorLength > 0); CVX_LADDER_REALIGN = realign,
+ *                     CVX_LADDER_SHORT = shortRead, CVX_LADDER_FULL = fullAlignment.
+ *   the rule          rung m = 1, 2, ... exists while min(corridor, 2 * L) * m <= 2 * L and fewer than 5 attempts have run
+ *                     (FULL: 1 attempt), where L is computeAlignment's refSeqLen = onRefStop - onRefStart + 1 (:209): the length
+ *                     of the decoded string PLUS ONE, that is tiles[i].ref_len + 1 (ref_len is strlen(refSeq), which the
+ *                     builders' k is computed from; the recordings of the unmodified reference pin both,
+ *                     tests/golden/ladder_*.npz).  Its corridor is what the reference's builder writes at multiplier m:
+ *                       FULL                          CVX_CORRIDOR_CONST, offset (int) (L * -0.2), width L + (int) (L * 0.2)
+ *                       SHORT                         k = 1, width = corridor * m, d = width / 2 (integer)
+ *                       ANCHORS && !REALIGN && m < 3  k = qry_len * 1.0f / ref_len, d = 0, right' = right * m, left' = left * m,
+ *                                                     width = (int) (left' + right')
+ *                       otherwise                     the same k, width = corridor * m / (REALIGN ? 1 : 4), d = width / 2.0f, right = 0
+ *                     (corridor already clamped; binary32 operations each rounded on its own).  A rung that ends CVX_TILE_OK
+ *                     resolves the tile; any other reference outcome (INVALID_*, TOO_LARGE, EMPTY) is the reference's -1 and the
+ *                     tile climbs if a further rung exists; CVX_TILE_UNSUPPORTED stops the ladder for the tile and is reported.
+ *                     A tile with qry_len == 0 or ref_len == 0 has no slope: its rungs are constant rows (offset 0) and EMPTY.
+ *   cvx_ladder_rung   the rule for callers and tests, host only: 1 and *form's corridor fields written (the others left alone)
+ *                     if rung m of (tile->ref_len, tile->qry_len, *l) exists, 0 if it does not, CVX_ERR_ARG on a bad argument
+ *                     (corridor < 0, an unknown flag, left / right negative, not finite or beyond 1e8, ref_len beyond 2^29).
+ *   cvx_submit_ladder g == NULL: cvx_submit's sequences; with g the references are cvx_submit_windows' windows (ref_position as
+ *                     there, cvx_job_window_refs works).  tiles[i]'s own corridor fields are ignored: rung 1 comes from
+ *                     ladders[i] like every other rung.  cvx_wait, cvx_job_poll, cvx_job_timing, cvx_job_launch_info and
+ *                     cvx_job_release work as for any job: results[i] is the record of the rung that resolved tile i, or of the
+ *                     last rung attempted; the dense ops arena holds the ops of exactly those records, in tile order; the timing
+ *                     sums over the rungs; the launch list is the rungs' launches one after the other.  Every rung keeps its own
+ *                     result block and ops on the host, and cvx_wait merges them there.  The text and profile calls for finished
+ *                     jobs (cvx_job_text*, cvx_job_nm_*) refuse a ladder job.
+ *                     Default and CVX_CREATE_SCALAR_TWIN handles; a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS
+ *                     or _SERVICE refuses the call with CVX_ERR_ARG (running those stages behind the final rung is a follow-up).
+ *   cvx_job_ladder    after cvx_wait, valid until cvx_job_release: per tile the rung reported (1-based), the attempts made and
+ *                     that rung's corridor width.
+ *   cvx_job_ladder_info  after cvx_wait: rungs the job ran, tiles[r] = tiles that took part in rung r + 1, and the sequence
+ *                     bytes uploaded, packed, copied or decoded after cvx_submit_ladder returned (0). */
+enum { CVX_LADDER_ANCHORS = 1, CVX_LADDER_REALIGN = 2, CVX_LADDER_SHORT = 4, CVX_LADDER_FULL = 8 };
+typedef struct {
+	int32_t corridor;
+	float left, right;
+	int32_t flags;
+} cvx_ladder;
+typedef struct { int32_t rung, attempts, width, reserved; } cvx_ladder_result;
+typedef struct { int32_t rungs_run; int32_t tiles[5]; uint64_t seq_bytes_after_submit; } cvx_ladder_info;
+int cvx_ladder_rung(const cvx_tile *tile, const cvx_ladder *l, int32_t m, cvx_tile *form);
+int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n_tiles, const cvx_tile *tiles,
+		const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out);
+int cvx_job_ladder(cvx_handle h, cvx_job job, const cvx_ladder_result **out);
+int cvx_job_ladder_info(cvx_job job, cvx_ladder_info *out);
+
 /* Candidate search (search half): the k-mer vote of CS::RunRead (src/CS.cpp:324-398: PrefixIteration
  * src/CSstatic.cpp:23-73, PrefixSearch / AddLocationStd src/CS.cpp:57-149, CollectResultsStd :219-268) for a batch of
  * (sub-)reads over the reference's k-mer table resident in HBM.

@@ -168,6 +168,19 @@ class ConvexAlignHip:
                                                 seg.ctypes.data, C.byref(j)))
         return Job(self, j, len(tiles), (keep, arena, offsets, seg, pos))
 
+    def submit_ladder(self, tiles: Sequence, ladders, genome: "Genome" = None, ref_positions=None) -> "Job":
+        """cvx_submit_ladder: cvx_submit (or, with `genome` and `ref_positions`, cvx_submit_windows) whose tiles carry the retry
+        ladder of AlignmentBuffer::computeAlignment instead of one corridor; the library climbs it on the device.  tiles: Tile
+        objects (their corridors are ignored).  ladders: (corridor, left, right, flags) per tile, or a LADDER_DTYPE array."""
+        arr, keep = self._pack(tiles, closed_form=True)
+        lad = _ladders(ladders)
+        assert len(lad) == len(tiles), "one ladder per tile"
+        pos = np.ascontiguousarray(ref_positions, dtype=np.uint64) if genome is not None else None
+        j = C.c_void_p()
+        capi.check(self.lib.cvx_submit_ladder(self.h, genome.g if genome is not None else None, len(tiles), arr,
+                                              pos.ctypes.data if pos is not None else None, lad.ctypes.data, C.byref(j)))
+        return Job(self, j, len(tiles), (keep, lad, pos))
+
     def stage_segments(self, reads, segments, lengths) -> List[bytes]:
         """cvx_stage_segments: the strings stage_segments_kernel builds for (read, start, flags) + length, back on the host."""
         arena, offsets, n_reads = _window_reads(reads)
@@ -227,6 +240,27 @@ assert NM_OPEN_DTYPE.itemsize == C.sizeof(capi.CvxNmOpen)
 # cvx_inv_check: checkForSV's two scores for one region, capi.CHECK_* in status
 INV_CHECK_DTYPE = np.dtype([("score_fwd", np.float32), ("score_rev", np.float32), ("status", np.int32), ("window_chars", np.int32)])
 assert INV_CHECK_DTYPE.itemsize == C.sizeof(capi.CvxInvCheck)
+
+
+# cvx_ladder / cvx_ladder_result
+LADDER_DTYPE = np.dtype([("corridor", np.int32), ("left", np.float32), ("right", np.float32), ("flags", np.int32)])
+LADDER_RESULT_DTYPE = np.dtype([("rung", np.int32), ("attempts", np.int32), ("width", np.int32), ("reserved", np.int32)])
+assert LADDER_DTYPE.itemsize == C.sizeof(capi.CvxLadder) and LADDER_RESULT_DTYPE.itemsize == C.sizeof(capi.CvxLadderResult)
+
+
+def _ladders(ladders) -> np.ndarray:
+    if isinstance(ladders, np.ndarray) and ladders.dtype == LADDER_DTYPE:
+        return np.ascontiguousarray(ladders)
+    out = np.zeros(len(ladders), dtype=LADDER_DTYPE)
+    for i, l in enumerate(ladders):
+        out[i] = (int(l[0]), float(l[1]), float(l[2]), int(l[3]))
+    return out
+
+
+def ladder_rung(tile, ladder, m: int):
+    """cvx_ladder_rung: rung m of the retry ladder of `tile` (only its two lengths are read); ladder = (corridor, left, right,
+    flags).  -> (kind, k, d, right, offset, width), or None where the rung does not exist."""
+    return capi.ladder_rung(len(tile.ref), len(tile.qry), ladder, m)
 
 
 def _inv_checks_call(qrys, ref_positions, position_offsets, region_off, regions):
@@ -304,6 +338,22 @@ class Job:
                         .view(RESULT_DTYPE) if self.n else np.zeros(0, RESULT_DTYPE))
         self.ops = (np.ctypeslib.as_array(ops, shape=(int(n_ops.value),)) if n_ops.value else np.zeros(0, np.uint32))
         return self.results, self.ops
+
+    def ladder(self) -> np.ndarray:
+        """cvx_job_ladder (after wait, a job of submit_ladder): per tile the rung reported (1-based), the attempts made and that
+        rung's corridor width, LADDER_RESULT_DTYPE."""
+        p = C.c_void_p()
+        capi.check(self.al.lib.cvx_job_ladder(self.al.h, self.j, C.byref(p)))
+        if not self.n:
+            return np.zeros(0, LADDER_RESULT_DTYPE)
+        buf = (C.c_uint8 * (self.n * LADDER_RESULT_DTYPE.itemsize)).from_address(p.value)
+        return np.frombuffer(buf, dtype=LADDER_RESULT_DTYPE).copy()
+
+    def ladder_info(self) -> dict:
+        """cvx_job_ladder_info: rungs the job ran, tiles per rung, sequence bytes moved after the submit call"""
+        info = capi.CvxLadderInfo()
+        capi.check(self.al.lib.cvx_job_ladder_info(self.j, C.byref(info)))
+        return {"rungs_run": int(info.rungs_run), "tiles": [int(x) for x in info.tiles], "seq_bytes_after_submit": int(info.seq_bytes_after_submit)}
 
     def zero_copy_bytes(self) -> int:
         """cvx_job_zero_copy_bytes: bytes of this job's upload the device pulled straight out of the caller's page-locked memory"""

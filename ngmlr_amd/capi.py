@@ -19,6 +19,7 @@ FORMAT_SCALAR_TWIN = 1                         # cvx_format_alignment_ex / cvx_f
 NOT_WRITTEN = -1                               # cigar_op_count / sv_type of the scalar twin's text stage
 STAGE_SCORE, STAGE_DECODE, STAGE_SEARCH, STAGE_SCORE_WINDOWS, STAGE_SEARCH_SCORE, STAGE_SEGMENTS = 0, 1, 2, 3, 4, 5      # cvx_stage_kernel_ms
 SEG_REVCOMP = 1                                # cvx_read_segment.flags
+LADDER_ANCHORS, LADDER_REALIGN, LADDER_SHORT, LADDER_FULL = 1, 2, 4, 8      # cvx_ladder.flags
 ERR_NAMES = {0: "CVX_OK", -1: "CVX_ERR_NO_DEVICE", -2: "CVX_ERR_PARAMS", -3: "CVX_ERR_ARG",
              -4: "CVX_ERR_OOM", -5: "CVX_ERR_HIP", -6: "CVX_ERR_CAPACITY"}
 TILE_STATUS = {0: "ok", 1: "invalid-row0", 2: "invalid-edge", 3: "invalid-length", 4: "too-large",
@@ -40,7 +41,8 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_score_windows_submit", "cvx_score_windows", "cvx_stage_windows", "cvx_stage_windows_host", "cvx_genome_concat_len",
            "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes",
            "cvx_handle_pen_table", "cvx_job_regions", "cvx_job_regions_info", "cvx_job_texts", "cvx_job_texts_info", "cvx_text_reclip",
-           "cvx_job_checks", "cvx_inv_checks", "cvx_inv_checks_host")
+           "cvx_job_checks", "cvx_inv_checks", "cvx_inv_checks_host",
+           "cvx_ladder_rung", "cvx_submit_ladder", "cvx_job_ladder", "cvx_job_ladder_info")
 
 
 class CvxParams(C.Structure):
@@ -150,6 +152,21 @@ class CvxReadSegment(C.Structure):
 
 
 assert C.sizeof(CvxReadSegment) == 16
+
+
+class CvxLadder(C.Structure):
+    _fields_ = [("corridor", C.c_int32), ("left", C.c_float), ("right", C.c_float), ("flags", C.c_int32)]
+
+
+class CvxLadderResult(C.Structure):
+    _fields_ = [("rung", C.c_int32), ("attempts", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CvxLadderInfo(C.Structure):
+    _fields_ = [("rungs_run", C.c_int32), ("tiles", C.c_int32 * 5), ("seq_bytes_after_submit", C.c_uint64)]
+
+
+assert C.sizeof(CvxLadder) == 16 and C.sizeof(CvxLadderResult) == 16 and C.sizeof(CvxLadderInfo) == 32
 
 
 class CvxError(RuntimeError):
@@ -285,6 +302,10 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_submit_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CvxTile), C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.cvx_job_zero_copy_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.cvx_ladder_rung.argtypes = [C.POINTER(CvxTile), C.POINTER(CvxLadder), C.c_int32, C.POINTER(CvxTile)]
+    lib.cvx_submit_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CvxTile), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.cvx_job_ladder.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.cvx_job_ladder_info.argtypes = [C.c_void_p, C.POINTER(CvxLadderInfo)]
     lib.cvx_genome_concat_len.argtypes = [C.c_uint64, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]
     lib.cvx_format_alignment.argtypes = [C.POINTER(CvxResult), C.c_void_p, C.c_char_p, C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32,
@@ -317,4 +338,20 @@ def corridor_fit(row_offset, row_length, ref_len, qry_len, stride_bytes=4):
     rc = lib.cvx_corridor_fit(off.ctypes.data, ln.ctypes.data, stride_bytes, n, ref_len, qry_len, C.byref(form))
     if rc != CVX_OK:
         raise RuntimeError("cvx_corridor_fit: %s" % ERR_NAMES.get(rc, rc))
+    return (form.corridor_kind, form.corridor_k, form.corridor_d, form.corridor_right, form.corridor_offset, form.corridor_width)
+
+
+def ladder_rung(ref_len: int, qry_len: int, ladder, m: int):
+    """cvx_ladder_rung (host code, no device): rung m of the retry ladder of a tile of these lengths; ladder = (corridor, left,
+    right, flags).  -> (kind, k, d, right, offset, width) as Tile.desc has it, or None where the rung does not exist."""
+    lib = load()
+    t = CvxTile()
+    t.ref_len, t.qry_len = int(ref_len), int(qry_len)
+    l = CvxLadder(int(ladder[0]), float(ladder[1]), float(ladder[2]), int(ladder[3]))
+    form = CvxTile()
+    rc = lib.cvx_ladder_rung(C.byref(t), C.byref(l), int(m), C.byref(form))
+    if rc < 0:
+        raise CvxError(rc, lib.cvx_last_error().decode(errors="replace"))
+    if rc == 0:
+        return None
     return (form.corridor_kind, form.corridor_k, form.corridor_d, form.corridor_right, form.corridor_offset, form.corridor_width)

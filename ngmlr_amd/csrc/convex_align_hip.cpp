@@ -535,6 +535,54 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 	Release(job);
 }
 
+void ConvexAlignHip::AlignLadders(LadderTile * tiles, int n) {
+	if (n <= 0) return;
+	std::vector<cvx_tile> ct((size_t) n);
+	std::vector<cvx_ladder> lad((size_t) n);
+	for (int i = 0; i < n; ++i) {
+		cvx_tile & c = ct[(size_t) i];
+		memset(&c, 0, sizeof(c));
+		c.ref = tiles[i].refSeq; c.qry = tiles[i].qrySeq;
+		c.ref_len = (int32_t) strlen(tiles[i].refSeq); c.qry_len = (int32_t) strlen(tiles[i].qrySeq);
+		c.row_stride_bytes = 4;
+		lad[(size_t) i] = tiles[i].ladder;
+		tiles[i].ret = -1; tiles[i].failed = false; tiles[i].rung = tiles[i].attempts = tiles[i].width = 0;
+	}
+	cvx_job job = 0;
+	if (cvx_submit_ladder(handle, 0, n, ct.data(), 0, lad.data(), &job) != CVX_OK) {
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	cvx_result const * res = 0;
+	uint32_t const * ops = 0;
+	cvx_ladder_result const * lr = 0;
+	try {
+		Wait(job, &res, &ops);
+		if (cvx_job_ladder(handle, job, &lr) != CVX_OK) { fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error()); throw 1; }
+	} catch (...) {
+		Release(job);
+		throw;
+	}
+	for (int i = 0; i < n; ++i) {
+		Tile t;
+		memset(&t, 0, sizeof(t));
+		t.refSeq = tiles[i].refSeq; t.qrySeq = tiles[i].qrySeq; t.result = tiles[i].result;
+		t.externalQStart = tiles[i].externalQStart; t.externalQEnd = tiles[i].externalQEnd;
+		t.refLen = ct[(size_t) i].ref_len; t.qryLen = ct[(size_t) i].qry_len; t.corridorHeight = t.qryLen;
+		t.ret = -1;
+		tiles[i].rung = lr[i].rung; tiles[i].attempts = lr[i].attempts; tiles[i].width = lr[i].width;
+		try {
+			Finish(t, res[i], ops);
+			tiles[i].ret = t.ret;
+		} catch (...) {
+			tiles[i].failed = true;
+			tiles[i].ret = -1;
+			tiles[i].result->Score = -1.0f;
+		}
+	}
+	Release(job);
+}
+
 /* convertCigar + flags into the caller's Align (src/ConvexAlignFast.cpp:488-539) */
 void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops, JobRegions const * jr, int index, JobTextView const * jx) const {
 	Align & a = *t.result;

@@ -96,6 +96,24 @@ public:
 	 * a failure of the launch itself throws. */
 	void AlignTiles(Tile * tiles, int n);
 
+	/* One request of AlignLadders(): what AlignmentBuffer::computeAlignment's retry loop reads (src/AlignmentBuffer.cpp:259-425)
+	 * in place of one CorridorLine[] -- see cvx_ladder, include/cvx_align.h. */
+	struct LadderTile {
+		char const * refSeq;
+		char const * qrySeq;
+		Align * result;
+		int externalQStart;
+		int externalQEnd;
+		cvx_ladder ladder;     /* corridor as passed to computeAlignment; left / right of the anchors builder; CVX_LADDER_* flags */
+		int ret;               /* out: the reference's cigarLength of the rung reported, or -1 */
+		bool failed;           /* out: this tile hit a hard error */
+		int rung, attempts, width;      /* out: the rung reported (1-based), the attempts made, that rung's corridor width */
+	};
+	/* n retry ladders in one device job (cvx_submit_ladder): every tile's corridor is rebuilt at multiplier 2, 3, ... and aligned
+	 * again on the device while its attempt is invalid and a further rung exists; `result` is filled the way SingleAlign fills it
+	 * for the rung reported.  Hard errors as for AlignTiles; a handle created with nmRegions or jobText refuses (throws 1). */
+	void AlignLadders(LadderTile * tiles, int n);
+
 	/* The same in stages, for a driver that keeps launches in flight.  Prepare / Finish may run on any thread (they
 	 * touch only the tile and the caller's Align); Submit / Wait / Release belong to the ONE thread that owns this
 	 * aligner's device handle.

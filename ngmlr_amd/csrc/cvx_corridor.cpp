@@ -284,3 +284,21 @@ extern "C" int cvx_corridor_fit_batch(int32_t n_tiles, cvx_tile *tiles, int32_t 
 	return err.load();
 	ABI_GUARD_END
 }
+
+/* The retry ladder's rule for callers and tests (cvx_ladder_logic.h; the kernel runs the same functions): rung m of the tile's
+ * ladder as a closed form. */
+#include "cvx_ladder_logic.h"
+
+extern "C" int cvx_ladder_rung(const cvx_tile *tile, const cvx_ladder *l, int32_t m, cvx_tile *form) {
+	ABI_GUARD_BEGIN
+	if (!tile || !l || !form || m < 1 || !cvx::ladder_args_ok(*l, tile->ref_len, tile->qry_len)) { cvx::set_err("cvx_ladder_rung: bad argument"); return CVX_ERR_ARG; }
+	if (!cvx::ladder_rung_exists(l->corridor, l->flags, tile->ref_len, m)) return 0;
+	cvx::RowSrc f;
+	cvx::ladder_form(l->corridor, l->left, l->right, l->flags, tile->ref_len, tile->qry_len, m, f);
+	form->corridor_kind = f.fmt == cvx::kRowsConst ? CVX_CORRIDOR_CONST : CVX_CORRIDOR_AFFINE;
+	form->corridor_k = f.k; form->corridor_d = f.d; form->corridor_right = f.right;
+	form->corridor_offset = f.off0;
+	form->corridor_width = f.width;
+	return 1;
+	ABI_GUARD_END
+}

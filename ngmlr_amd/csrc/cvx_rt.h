@@ -167,6 +167,9 @@ enum LaunchEvent { kLevStart = 0, kLevTwoPhase = 1, kLevExact = 2, kLevWalked = 
 
 enum BatchState { kFailed = -1, kEmpty = 0, kUploaded = 1, kPlanned = 2, kComputed = 3, kFinished = 4 };
 
+struct LadderState;              /* below: what the first rung of a ladder job (cvx_submit_ladder) carries */
+void ladder_drop(struct cvx_batch_s *root);      /* frees it and the later rungs' batches (cvx_rt_align.cpp); the device is idle, or has nothing of them queued */
+
 struct cvx_batch_s {
 	int n = 0;
 	int state = kEmpty;
@@ -266,6 +269,15 @@ struct cvx_batch_s {
 	DevBuf<BoundaryRec> d_bnd;
 	uint32_t bnd_epoch = 0;          /* tag of the records the latest launch wrote (0: buffer freshly zeroed) */
 	DevBuf<ChainOut> d_chain_out;
+	/* ladder jobs (cvx_submit_ladder): the job the caller holds is rung 1; every later rung is a batch of its own -- its own plan,
+	 * lists, direction words, result block and ops -- that reads the sequences of rung 1 */
+	LadderState *ladder = nullptr;   /* rung 1: the job's ladder */
+	cvx_batch_s *ladder_root = nullptr;      /* a later rung: the rung 1 whose sequence arena it reads */
+	DevBuf<int32_t> d_lhead;         /* a later rung: tiles that climbed to it, then the job tile of each (ladder_next_kernel) */
+	PinBuf h_lhead;
+	DevBuf<cvx_ladder> d_lad;        /* rung 1: cvx_ladder[n] as submitted */
+	PinBuf h_lad;
+	PinBuf h_lres, h_lops, h_lout;   /* rung 1: the job's answer merged by cvx_wait -- ResultRec[n], dense ops, cvx_ladder_result[n] */
 
 	hipEvent_t ev_bt0 = nullptr, ev_bt1 = nullptr;   /* fork / join of the long-read backtrack launch */
 	hipEvent_t ev_in = nullptr;      /* upload + plan records on the host */
@@ -306,6 +318,9 @@ struct cvx_batch_s {
 		return CVX_OK;
 	}
 	void release() {
+		if (ladder) ladder_drop(this);
+		ladder_root = nullptr;
+		d_lhead.release(); h_lhead.release(); d_lad.release(); h_lad.release(); h_lres.release(); h_lops.release(); h_lout.release();
 		h_zero.release(); zero_cap = 0;
 		h_seq.release(); h_delta.release(); h_rsrc.release(); h_rowsx.release(); h_tin.release();
 		d_delta.release(); d_rsrc.release(); d_rowsx.release(); h_plan.release(); h_trun.release(); h_tout.release();
@@ -334,6 +349,21 @@ struct cvx_batch_s {
 		for (auto &e : lev) if (e) (void) hipEventDestroy(e);
 		lev.clear();
 	}
+};
+
+/* The ladder of one job.  Where a tile's reported record and ops are kept: every rung's batch keeps its own result block and
+ * dense ops in its own page-locked memory, as any job does, and cvx_wait merges them on the host -- per tile the record of the
+ * last rung it took part in, its ops copied into one arena in tile order. */
+struct LadderState {
+	std::vector<cvx_batch_s *> rungs;      /* rungs[r]: the batch of rung r + 1; rungs[0] is the job itself */
+	cvx_batch_s *next = nullptr;     /* the rung whose list and plan are on their way back (its ev_in says when) */
+	bool done = false;               /* no further rung will be queued */
+	bool merged = false;             /* the job's h_lres / h_lops / h_lout hold its answer */
+	int max_rungs = 0;               /* the longest ladder any tile of the job has (host rule at submit) */
+	uint64_t ops_total = 0;          /* ops of the merged arena */
+	uint64_t seq_bytes_after_submit = 0;   /* sequence bytes queued for upload, copy or decode by a later rung: nothing adds to it */
+	cvx_timing timing;               /* summed over the rungs */
+	std::vector<cvx_launch_info> launches; /* the rungs' launches, in order */
 };
 
 struct cvx_context {
@@ -412,6 +442,7 @@ struct cvx_context {
 	std::vector<cvx_batch_s *> pool;
 	std::vector<cvx_batch_s *> pending;      /* streaming jobs whose compute stage is not queued yet */
 	std::vector<cvx_batch_s *> live;         /* every streaming job the caller has not released yet (cvx_destroy frees what is left) */
+	std::vector<cvx_batch_s *> climbing;     /* ladder jobs whose first rung is queued and whose ladder is not done (pump advances them) */
 	float segments_kernel_ms = 0.0f;   /* stage_segments_kernel of the last cvx_stage_segments (cvx_stage_kernel_ms) */
 	float decode_kernel_ms = 0.0f;     /* decode_windows_kernel of the last cvx_genome_decode (cvx_stage_kernel_ms) */
 	bool score_no_diag = false;   /* test knob (env CVX_TUNE_SCORE_NO_DIAG): always the row-by-row kernels */

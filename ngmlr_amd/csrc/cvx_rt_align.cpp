@@ -30,6 +30,8 @@
 #include <string>
 #include <vector>
 
+#include "cvx_ladder.h"
+#include "cvx_ladder_logic.h"
 #include "cvx_qry_stage.h"
 #include "cvx_rt.h"
 
@@ -54,7 +56,29 @@ cvx_batch_s *acquire_batch(cvx_context *h) {
 	return new (std::nothrow) cvx_batch_s();
 }
 
+void recycle_batch(cvx_context *h, cvx_batch_s *b);
+
+/* a ladder job leaves: its later rungs' batches go where the job goes (the pool, with their arenas, or the allocator) */
+void ladder_release(cvx_context *h, cvx_batch_s *root) {
+	LadderState *L = root->ladder;
+	if (!L) return;
+	if (h) {
+		auto it = std::find(h->climbing.begin(), h->climbing.end(), root);
+		if (it != h->climbing.end()) h->climbing.erase(it);
+	}
+	root->ladder = nullptr;
+	if (L->next) L->rungs.push_back(L->next);
+	for (size_t r = 1; r < L->rungs.size(); ++r) {
+		cvx_batch_s *c = L->rungs[r];
+		c->ladder_root = nullptr;
+		if (root->state == kFailed) c->state = kFailed;
+		recycle_batch(h, c);
+	}
+	delete L;
+}
+
 void recycle_batch(cvx_context *h, cvx_batch_s *b) {
+	if (b->ladder) ladder_release(h, b);
 	const bool failed = b->state == kFailed;
 	b->state = kEmpty;
 	b->in_flight = false;
@@ -85,6 +109,8 @@ void discard_batch(cvx_context *h, cvx_batch_s *b) {
 		if (it != h->pending.end()) h->pending.erase(it);
 		it = std::find(h->live.begin(), h->live.end(), b);
 		if (it != h->live.end()) h->live.erase(it);
+		it = std::find(h->climbing.begin(), h->climbing.end(), b);
+		if (it != h->climbing.end()) h->climbing.erase(it);
 	}
 	b->release();
 	delete b;
@@ -292,7 +318,7 @@ int stage_plan(cvx_context *h, cvx_batch_s *b, hipStream_t st) {
 /* ---- stage 3's helpers */
 /* the kernels' arguments of a batch; a fill launch adds its own list, chain fields and priority */
 void kernel_args(const cvx_context *h, const cvx_batch_s *b, const ChainBlk *chain_blk, FillArgs &a, BacktrackArgs &ba) {
-	a.seq = ba.seq = b->d_seq.p;
+	a.seq = ba.seq = b->ladder_root ? b->ladder_root->d_seq.p : b->d_seq.p;      /* (a later rung of a ladder job reads rung 1's sequences where they lie) */
 	a.rows = ba.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
 	a.rsrc = ba.rsrc = b->d_rsrc.p;
 	a.tin = ba.tin = b->d_tin.p;
@@ -782,9 +808,188 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 	return CVX_OK;
 }
 
+/* ---- ladder jobs (cvx_submit_ladder): a rung is the plan -> schedule -> fill -> walk -> records cycle of a job run again,
+ * over the tiles ladder_next_kernel found climbing.  Rung r + 1 is a batch of its own from the handle's pool (its own plan,
+ * lists, direction words, result block, ops: nothing of rung r is overwritten, so nothing has to wait for rung r's readers)
+ * that reads rung 1's sequence arena.  Order: the kernel waits, on the device, for the event behind rung r's result records;
+ * the host waits for nothing but the event behind the next rung's list and plan records -- queried from pump, blocking only
+ * inside cvx_wait. */
+
+/* behind rung `prev` (rung m, computed) of `root`: the decision kernel, the plan of the tiles it lists, and list, tile records,
+ * corridors and plan records on their way to the host; L->next is the batch they belong to */
+int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m) {
+	LadderState *L = root->ladder;
+	const int np = prev->n;
+	if (np <= 0 || m >= L->max_rungs) { L->done = true; return CVX_OK; }
+	cvx_batch_s *c = acquire_batch(h);
+	if (!c) { set_err("cvx_submit_ladder: no memory for rung %d", m + 1); return CVX_ERR_OOM; }
+	c->bind(h->marks);
+	c->n = 0; c->state = kEmpty; c->in_flight = false; c->have_ops = false; c->have_refs = false; c->text_done = false;
+	c->jr_on = c->jc_on = c->jt_on = false; c->jc_bin = nullptr; c->jc_L = 0;
+	c->ops_total = 0; c->seq_total = 0; c->n_rows = 0; c->n_rowsx = 0; c->zero_copy_bytes = 0;
+	memset(&c->timing, 0, sizeof(c->timing));
+	c->ladder_root = root;
+	L->next = c;      /* (from here on the batch leaves with the job, whatever fails) */
+	RC_TRY(c->make_events());
+	const size_t n1 = (size_t) np;
+	RC_TRY(c->h_rsrc.ensure(n1 * sizeof(RowSrc)));
+	RC_TRY(c->h_tin.ensure(n1 * sizeof(TileIn)));
+	RC_TRY(c->h_plan.ensure(n1 * sizeof(TilePlan)));
+	RC_TRY(c->h_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	RC_TRY(c->h_lhead.ensure((n1 + 1) * sizeof(int32_t)));
+	RC_TRY(c->d_lhead.ensure(n1 + 1));
+	RC_TRY(c->d_rsrc.ensure(n1));
+	RC_TRY(c->d_rows.ensure(1));      /* closed forms own no rows */
+	RC_TRY(c->d_tin.ensure(n1));
+	RC_TRY(c->d_plan.ensure(n1));
+	RC_TRY(c->d_trun.ensure(n1));
+	RC_TRY(c->d_tout.ensure(n1));
+	RC_TRY(c->d_dstoff.ensure(n1 + 2 * (size_t) finalize_blocks(np)));
+	RC_TRY(c->d_lists.ensure(2 * n1));
+	if (c->d_counters.cap < 64) {
+		RC_TRY(c->d_counters.ensure(64));
+		HIP_TRY(hipMemset(c->d_counters.p, 0, c->d_counters.cap * sizeof(int32_t)));
+	}
+	RC_TRY(c->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	hipStream_t st = h->s_main;
+	HIP_TRY(hipStreamWaitEvent(st, prev->ev_res, 0));      /* rung m's records are final */
+	LadderNextArgs a;
+	a.res = reinterpret_cast<const ResultRec *>(prev->d_res.p);
+	a.prev_idx = prev == root ? nullptr : prev->d_lhead.p + 1;
+	a.tin0 = root->d_tin.p;
+	a.lad = root->d_lad.p;
+	a.n_prev = np;
+	a.m = m;
+	a.rsrc = c->d_rsrc.p; a.tin = c->d_tin.p; a.head = c->d_lhead.p;
+	HIP_TRY(launch_ladder_next(a, st));
+	HIP_TRY(hipEventRecord(c->ev[0], st));
+	HIP_TRY(launch_plan(c->d_rows.p, c->d_rsrc.p, c->d_tin.p, c->d_plan.p, np, root->n ? root->n_rows / (uint64_t) root->n : 0, h->max_matrix_mb, st));
+	HIP_TRY(hipMemcpyAsync(c->h_plan.p, c->d_plan.p, n1 * sizeof(TilePlan), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipEventRecord(c->ev[1], st));
+	HIP_TRY(hipMemcpyAsync(c->h_lhead.p, c->d_lhead.p, (n1 + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(c->h_tin.p, c->d_tin.p, n1 * sizeof(TileIn), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(c->h_rsrc.p, c->d_rsrc.p, n1 * sizeof(RowSrc), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipEventRecord(c->ev_in, st));
+	c->state = kPlanned;
+	return CVX_OK;
+}
+
+/* the ladder of `root` as far as the device has answered (block: to its end); a failure is the job's */
+void ladder_advance(cvx_context *h, cvx_batch_s *root, bool block) {
+	LadderState *L = root->ladder;
+	while (root->state != kFailed && !L->done) {
+		int rc = CVX_OK;
+		if (!L->next) {
+			rc = ladder_queue_next(h, root, L->rungs.back(), (int) L->rungs.size());
+			if (rc != CVX_OK) { (void) fail_job(root, rc); break; }
+			continue;
+		}
+		cvx_batch_s *c = L->next;
+		if (!block) {
+			hipError_t q = hipEventQuery(c->ev_in);
+			if (q == hipErrorNotReady) { (void) hipGetLastError(); return; }
+			if (q != hipSuccess) { set_err("hipEventQuery: %s", hipGetErrorString(q)); (void) fail_job(root, CVX_ERR_HIP); break; }
+		} else {
+			hipError_t q = hipEventSynchronize(c->ev_in);
+			if (q != hipSuccess) { set_err("hipEventSynchronize: %s", hipGetErrorString(q)); (void) fail_job(root, CVX_ERR_HIP); break; }
+		}
+		const int count = c->h_lhead.as<int32_t>()[0];
+		L->next = nullptr;
+		if (count <= 0) {      /* nobody climbs: the job ends (what was queued for the batch has run: its event is behind all of it) */
+			c->ladder_root = nullptr;
+			recycle_batch(h, c);
+			L->done = true;
+			break;
+		}
+		c->n = count;
+		c->n_rows = 0;
+		for (int i = 0; i < count; ++i) c->n_rows += (uint64_t) c->tin()[(size_t) i].H;
+		L->rungs.push_back(c);
+		rc = stage_compute(h, c, true);
+		if (rc != CVX_OK) { (void) fail_job(root, rc); break; }
+		if ((int) L->rungs.size() >= kLadderMaxRungs) L->done = true;
+	}
+	if (root->state == kFailed) L->done = true;
+	if (L->done) {
+		auto it = std::find(h->climbing.begin(), h->climbing.end(), root);
+		if (it != h->climbing.end()) h->climbing.erase(it);
+	}
+}
+
+/* every climbing job as far as it has come, without waiting */
+void ladder_pump(cvx_context *h) {
+	const std::vector<cvx_batch_s *> jobs = h->climbing;      /* (ladder_advance takes finished ladders off the list) */
+	for (cvx_batch_s *root : jobs) ladder_advance(h, root, false);
+}
+
+/* the job's answer, once its ladder is done: every rung's records and ops waited for, then merged on the host -- per tile the
+ * record of the last rung it took part in, its ops copied into one arena in tile order (ops_begin rebased), the ladder record
+ * beside it; timing summed, launches strung together */
+int ladder_finish(cvx_context *h, cvx_batch_s *root) {
+	LadderState *L = root->ladder;
+	if (L->merged) return CVX_OK;
+	for (cvx_batch_s *c : L->rungs) {
+		if (c->state < kFinished) RC_TRY(stage_results(h, c));
+		RC_TRY(stage_ops(h, c));
+	}
+	const int n = root->n;
+	const size_t n1 = (size_t) std::max(n, 1);
+	std::vector<int32_t> rung_of((size_t) n, 0), at((size_t) n);
+	for (int i = 0; i < n; ++i) at[(size_t) i] = i;
+	for (size_t r = 1; r < L->rungs.size(); ++r) {
+		const cvx_batch_s *c = L->rungs[r];
+		const int32_t *head = c->h_lhead.as<int32_t>();
+		for (int j = 0; j < c->n; ++j) {
+			const int32_t i = head[1 + j];
+			if (i < 0 || i >= n) { set_err("internal: rung %zu lists tile %d of %d", r + 1, i, n); return CVX_ERR_HIP; }
+			rung_of[(size_t) i] = (int32_t) r;
+			at[(size_t) i] = j;
+		}
+	}
+	uint64_t total = 0;
+	for (int i = 0; i < n; ++i) total += (uint64_t) L->rungs[(size_t) rung_of[(size_t) i]]->res()[at[(size_t) i]].n_ops;
+	RC_TRY(root->h_lres.ensure(n1 * sizeof(ResultRec)));
+	RC_TRY(root->h_lout.ensure(n1 * sizeof(cvx_ladder_result)));
+	RC_TRY(root->h_lops.ensure((size_t) std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
+	ResultRec *res = root->h_lres.as<ResultRec>();
+	cvx_ladder_result *out = root->h_lout.as<cvx_ladder_result>();
+	uint32_t *ops = root->h_lops.as<uint32_t>();
+	const cvx_ladder *lad = root->h_lad.as<cvx_ladder>();
+	uint64_t used = 0;
+	for (int i = 0; i < n; ++i) {
+		const cvx_batch_s *c = L->rungs[(size_t) rung_of[(size_t) i]];
+		ResultRec r = c->res()[at[(size_t) i]];
+		if (r.n_ops > 0) memcpy(ops + used, c->h_ops.as<uint32_t>() + r.ops_begin, (size_t) r.n_ops * sizeof(uint32_t));
+		r.ops_begin = used;
+		used += (uint64_t) std::max(r.n_ops, 0);
+		res[i] = r;
+		const TileIn &ti = root->tin()[(size_t) i];
+		RowSrc f;
+		ladder_form(lad[i].corridor, lad[i].left, lad[i].right, lad[i].flags, ti.W, ti.H, rung_of[(size_t) i] + 1, f);
+		out[i].rung = out[i].attempts = rung_of[(size_t) i] + 1;
+		out[i].width = f.width;
+		out[i].reserved = 0;
+	}
+	L->ops_total = used;
+	memset(&L->timing, 0, sizeof(L->timing));
+	L->launches.clear();
+	for (const cvx_batch_s *c : L->rungs) {
+		const cvx_timing &t = c->timing;
+		L->timing.plan_ms += t.plan_ms; L->timing.fill_ms += t.fill_ms; L->timing.backtrack_ms += t.backtrack_ms; L->timing.total_ms += t.total_ms;
+		L->timing.cells += t.cells; L->timing.active_cells += t.active_cells; L->timing.dir_bytes += t.dir_bytes;
+		L->timing.n_fill_launches += t.n_fill_launches; L->timing.n_tiles_fast += t.n_tiles_fast; L->timing.n_tiles_redone += t.n_tiles_redone;
+		L->timing.n_tiles_chained += t.n_tiles_chained;
+		L->timing.chain_task_ticks += t.chain_task_ticks; L->timing.chain_poll_ticks += t.chain_poll_ticks;
+		L->launches.insert(L->launches.end(), c->launches.begin(), c->launches.end());
+	}
+	L->merged = true;
+	return CVX_OK;
+}
+
 /* queue the compute stage of every submitted batch whose plan records have arrived (all of them,
  * up to `upto`, when `block`): keeps the device one batch ahead of the host */
 int pump(cvx_context *h, bool block, const cvx_batch_s *upto) {
+	if (!h->climbing.empty()) ladder_pump(h);
 	while (!h->pending.empty()) {
 		cvx_batch_s *b = h->pending.front();
 		if (!block) {
@@ -797,6 +1002,10 @@ int pump(cvx_context *h, bool block, const cvx_batch_s *upto) {
 		 * to THIS job: it is recorded on it and reported by its own cvx_wait, never against another job's call */
 		const int rc = stage_compute(h, b, true);
 		if (rc != CVX_OK) (void) fail_job(b, rc);
+		else if (b->ladder) {      /* rung 1 of a ladder job is queued: its decision kernel and the next rung's plan go right behind it */
+			h->climbing.push_back(b);
+			ladder_advance(h, b, false);
+		}
 		if (upto && b == upto) break;
 	}
 	return CVX_OK;
@@ -826,6 +1035,20 @@ int stage_segments_plan(const char *who, int32_t n_reads, const uint8_t *arena, 
 }
 
 }  // namespace
+
+/* cvx_batch_s::release of a ladder job (cvx_destroy, a failed submit): the later rungs' batches go back to the allocator with it */
+void ladder_drop(cvx_batch_s *root) {
+	LadderState *L = root->ladder;
+	root->ladder = nullptr;
+	if (!L) return;
+	if (L->next) L->rungs.push_back(L->next);
+	for (size_t r = 1; r < L->rungs.size(); ++r) {
+		L->rungs[r]->ladder_root = nullptr;
+		L->rungs[r]->release();
+		delete L->rungs[r];
+	}
+	delete L;
+}
 
 extern "C" {
 
@@ -865,15 +1088,16 @@ int cvx_batch_run(cvx_handle h, cvx_batch b) {
 int cvx_batch_timing(cvx_batch b, cvx_timing *t) {
 	ABI_GUARD_BEGIN
 	if (!b || !t) { set_err("cvx_batch_timing: NULL argument"); return CVX_ERR_ARG; }
-	*t = b->timing;
+	*t = (b->ladder && b->ladder->merged) ? b->ladder->timing : b->timing;
 	return CVX_OK;
 	ABI_GUARD_END
 }
 
 int cvx_batch_launch_info(cvx_batch b, int32_t i, cvx_launch_info *info) {
 	ABI_GUARD_BEGIN
-	if (!b || !info || b->state < kFinished || i < 0 || (size_t) i >= b->launches.size()) { set_err("cvx_batch_launch_info: bad index"); return CVX_ERR_ARG; }
-	*info = b->launches[(size_t) i];
+	const std::vector<cvx_launch_info> *ls = b ? ((b->ladder && b->ladder->merged) ? &b->ladder->launches : &b->launches) : nullptr;
+	if (!b || !info || b->state < kFinished || i < 0 || (size_t) i >= ls->size()) { set_err("cvx_batch_launch_info: bad index"); return CVX_ERR_ARG; }
+	*info = (*ls)[(size_t) i];
 	return CVX_OK;
 	ABI_GUARD_END
 }
@@ -967,7 +1191,7 @@ int cvx_align_batch(cvx_handle h, int32_t n, const cvx_tile *tiles, cvx_result *
 /* ------------------------------------------------------------------ streaming form */
 
 static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const cvx_genome_s *genome, const uint64_t *ref_position, cvx_job *out,
-		const SegmentsIn *segs = nullptr) {
+		const SegmentsIn *segs = nullptr, const cvx_ladder *ladders = nullptr, int max_rungs = 0) {
 	if (!h || !out || n < 0 || (n > 0 && !tiles) || (genome && n > 0 && !ref_position)) { set_err("cvx_submit: bad argument"); return CVX_ERR_ARG; }
 	*out = nullptr;
 	if (genome && genome->device != h->device) { set_err("cvx_submit_windows: the genome lives on device %d, the handle on %d", genome->device, h->device); return CVX_ERR_ARG; }
@@ -985,6 +1209,24 @@ static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const c
 	const auto t2 = std::chrono::steady_clock::now();
 	int rc = stage_upload(h, b, n, tiles, genome, ref_position, segs);
 	const auto t3 = std::chrono::steady_clock::now();
+	if (rc == CVX_OK && ladders) {
+		/* a ladder job: the tiles' ladders go up behind the batch's inputs, in front of the event its compute stage waits for */
+		LadderState *L = new (std::nothrow) LadderState();
+		if (!L) rc = CVX_ERR_OOM;
+		else {
+			L->max_rungs = max_rungs;
+			L->rungs.push_back(b);
+			b->ladder = L;
+			const size_t bytes = (size_t) std::max(n, 1) * sizeof(cvx_ladder);
+			rc = b->h_lad.ensure(bytes);
+			if (rc == CVX_OK) rc = b->d_lad.ensure((size_t) std::max(n, 1));
+			if (rc == CVX_OK && n) {
+				memcpy(b->h_lad.p, ladders, (size_t) n * sizeof(cvx_ladder));
+				hipError_t e = hipMemcpyAsync(b->d_lad.p, b->h_lad.p, (size_t) n * sizeof(cvx_ladder), hipMemcpyHostToDevice, h->s_io);
+				if (e != hipSuccess) { set_err("cvx_submit_ladder: %s", hipGetErrorString(e)); rc = CVX_ERR_HIP; }
+			}
+		}
+	}
 	if (rc == CVX_OK) rc = stage_plan(h, b, h->s_io);
 	if (rc != CVX_OK) { discard_batch(h, b); return rc; }
 	b->in_flight = true;
@@ -1018,6 +1260,64 @@ int cvx_submit_segments(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *t
 	if (n_reads < 0 || !offsets || (n_reads > 0 && !arena) || (n > 0 && !qry) || (!g && ref_position)) { set_err("cvx_submit_segments: bad argument"); return CVX_ERR_ARG; }
 	const SegmentsIn segs = { n_reads, arena, offsets, qry };
 	return submit_common(h, n, tiles, g, ref_position, out, &segs);
+	ABI_GUARD_END
+}
+
+int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out) {
+	ABI_GUARD_BEGIN
+	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("cvx_submit_ladder: bad argument"); return CVX_ERR_ARG; }
+	if (h->nm_regions || h->job_text || h->inv_checks || h->service) {
+		set_err("cvx_submit_ladder: not on a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS or _SERVICE");
+		return CVX_ERR_ARG;
+	}
+	/* rung 1's corridor from the ladder, like every later rung's; every rung a tile can reach checked here, on the host,
+	 * so that the kernel writes none the device would refuse */
+	std::vector<cvx_tile> forms(tiles, tiles + n);
+	int max_rungs = 0;
+	for (int32_t i = 0; i < n; ++i) {
+		cvx_tile &t = forms[(size_t) i];
+		const cvx_ladder &l = ladders[i];
+		if (!ladder_args_ok(l, t.ref_len, t.qry_len)) {
+			set_err("cvx_submit_ladder: tile %d: corridor %d, left %g, right %g, flags %d, ref_len %d, qry_len %d", i, l.corridor, (double) l.left, (double) l.right, l.flags, t.ref_len, t.qry_len);
+			return CVX_ERR_ARG;
+		}
+		const int len = ladder_length(l.corridor, l.flags, t.ref_len);
+		max_rungs = std::max(max_rungs, len);
+		for (int m = len; m >= 1; --m) {      /* (downwards: rung 1's form is the one left in the tile) */
+			RowSrc f;
+			ladder_form(l.corridor, l.left, l.right, l.flags, t.ref_len, t.qry_len, m, f);
+			if (f.width < 0 || (f.fmt == kRowsAffine && !affine_form_ok(f.k, f.d, f.right, t.qry_len))) {
+				set_err("cvx_submit_ladder: tile %d: the corridor of rung %d is out of range", i, m);
+				return CVX_ERR_ARG;
+			}
+			t.corridor_kind = f.fmt == kRowsConst ? CVX_CORRIDOR_CONST : CVX_CORRIDOR_AFFINE;
+			t.corridor_k = f.k; t.corridor_d = f.d; t.corridor_right = f.right;
+			t.corridor_offset = f.off0; t.corridor_width = f.width;
+		}
+		t.row_offset = nullptr; t.row_length = nullptr; t.row_stride_bytes = 4;
+	}
+	static const cvx_ladder none = { 0, 0.0f, 0.0f, 0 };      /* (an empty job is a ladder job too) */
+	return submit_common(h, n, forms.data(), g, ref_position, out, nullptr, ladders ? ladders : &none, max_rungs);
+	ABI_GUARD_END
+}
+
+int cvx_job_ladder(cvx_handle h, cvx_job j, const cvx_ladder_result **out) {
+	ABI_GUARD_BEGIN
+	if (!h || !j || !out || !j->ladder || !j->ladder->merged) { set_err("cvx_job_ladder: not a finished ladder job (cvx_submit_ladder, then cvx_wait)"); return CVX_ERR_ARG; }
+	*out = j->h_lout.as<cvx_ladder_result>();
+	return CVX_OK;
+	ABI_GUARD_END
+}
+
+int cvx_job_ladder_info(cvx_job j, cvx_ladder_info *out) {
+	ABI_GUARD_BEGIN
+	if (!j || !out || !j->ladder || !j->ladder->merged) { set_err("cvx_job_ladder_info: not a finished ladder job (cvx_submit_ladder, then cvx_wait)"); return CVX_ERR_ARG; }
+	memset(out, 0, sizeof(*out));
+	const LadderState *L = j->ladder;
+	out->rungs_run = (int32_t) L->rungs.size();
+	for (size_t r = 0; r < L->rungs.size() && r < 5; ++r) out->tiles[r] = L->rungs[r]->n;
+	out->seq_bytes_after_submit = L->seq_bytes_after_submit;
+	return CVX_OK;
 	ABI_GUARD_END
 }
 
@@ -1088,13 +1388,19 @@ int cvx_wait(cvx_handle h, cvx_job j, const cvx_result **results, const uint32_t
 	/* A job that failed (now or in an earlier call) stays valid until cvx_job_release and keeps answering with its
 	 * own error; nothing of another job is ever returned in its place. */
 	if (j->state != kFailed && j->state < kComputed) (void) pump(h, true, j);
-	if (j->state != kFailed && j->state < kFinished) { const int rc = stage_results(h, j); if (rc != CVX_OK) (void) fail_job(j, rc); }
-	if (j->state != kFailed) { const int rc = stage_ops(h, j); if (rc != CVX_OK) (void) fail_job(j, rc); }
+	if (j->ladder) {
+		/* a ladder job: the rungs still to come, each behind the blocking wait for its list and plan records, then all their results merged */
+		if (j->state != kFailed) ladder_advance(h, j, true);
+		if (j->state != kFailed) { const int rc = ladder_finish(h, j); if (rc != CVX_OK) (void) fail_job(j, rc); }
+	} else {
+		if (j->state != kFailed && j->state < kFinished) { const int rc = stage_results(h, j); if (rc != CVX_OK) (void) fail_job(j, rc); }
+		if (j->state != kFailed) { const int rc = stage_ops(h, j); if (rc != CVX_OK) (void) fail_job(j, rc); }
+	}
 	if (j->state == kFailed) { g_err = j->fail_msg; return j->fail_rc; }
 	(void) pump(h, false, nullptr);      /* later jobs whose inputs have arrived meanwhile */
-	if (results) *results = reinterpret_cast<const cvx_result *>(j->res());
-	if (ops) *ops = j->h_ops.as<uint32_t>();
-	if (n_ops) *n_ops = j->ops_total;
+	if (results) *results = reinterpret_cast<const cvx_result *>(j->ladder ? j->h_lres.as<ResultRec>() : j->res());
+	if (ops) *ops = j->ladder ? j->h_lops.as<uint32_t>() : j->h_ops.as<uint32_t>();
+	if (n_ops) *n_ops = j->ladder ? j->ladder->ops_total : j->ops_total;
 	return CVX_OK;
 	ABI_GUARD_END
 }
@@ -1117,6 +1423,14 @@ int cvx_job_poll(cvx_handle h, cvx_job j, int32_t *done) {
 	(void) pump(h, false, nullptr);          /* queue the kernels of whatever has its corridor plans back */
 	*done = 0;
 	if (j->state == kFailed || j->state >= kFinished) { *done = 1; return CVX_OK; }
+	if (j->ladder && j->state >= kComputed) {      /* done when no rung is to come and the last one's records are on the host */
+		if (!j->ladder->done) return CVX_OK;
+		hipError_t q = hipEventQuery(j->ladder->rungs.back()->ev_res);
+		if (q == hipSuccess) *done = 1;
+		else if (q == hipErrorNotReady) (void) hipGetLastError();
+		else { set_err("hipEventQuery: %s", hipGetErrorString(q)); return CVX_ERR_HIP; }
+		return CVX_OK;
+	}
 	if (j->state >= kComputed) {
 		hipError_t q = hipEventQuery(j->ev_res);
 		if (q == hipSuccess) *done = 1;

@@ -54,6 +54,7 @@ int cvx_job_text(cvx_handle h, cvx_job j, const int32_t *ext_qstart, const int32
 	ABI_GUARD_BEGIN
 	static_assert(sizeof(TextRec) == sizeof(cvx_alignment_text), "TextRec mirrors cvx_alignment_text");
 	if (!h || !j || j->state < kFinished) { set_err("cvx_job_text: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->ladder) { set_err("cvx_job_text: the stages of a finished job do not take a ladder job (cvx_submit_ladder)"); return CVX_ERR_ARG; }
 	const int n = j->n;
 	if (n > 0 && (!out || !text_off || !text)) { set_err("cvx_job_text: NULL output"); return CVX_ERR_ARG; }
 	if (text_bytes) *text_bytes = 0;
@@ -94,6 +95,7 @@ int cvx_job_text_all(cvx_handle h, cvx_job j, const int32_t *ext_qstart, const i
 		uint64_t *nm_entry_off, const int32_t **triples) {
 	ABI_GUARD_BEGIN
 	if (!h || !j || j->state < kFinished) { set_err("cvx_job_text_all: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->ladder) { set_err("cvx_job_text_all: the stages of a finished job do not take a ladder job (cvx_submit_ladder)"); return CVX_ERR_ARG; }
 	const int n = j->n;
 	if (!text || !triples || (n > 0 && (!out || !text_off || !nm_entry_off))) { set_err("cvx_job_text_all: NULL output"); return CVX_ERR_ARG; }
 	if (text_bytes) *text_bytes = 0;
@@ -143,6 +145,7 @@ static int nm_profile_common(cvx_handle h, cvx_job j, int32_t first, int32_t cou
 		int32_t *triples, uint64_t cap_entries, double *kernel_ms, bool sizes_only, const int32_t **resident = nullptr) {
 	if (kernel_ms) *kernel_ms = 0.0;
 	if (!h || !j || j->state < kFinished) { set_err("cvx_job_nm_profile: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->ladder) { set_err("cvx_job_nm_profile: the stages of a finished job do not take a ladder job (cvx_submit_ladder)"); return CVX_ERR_ARG; }
 	if (!j->text_done) { set_err("cvx_job_nm_profile: call cvx_job_text first (it counts the entries)"); return CVX_ERR_ARG; }
 	if (first < 0 || count < 0 || (int64_t) first + count > j->n || (count > 0 && !entry_off)) { set_err("cvx_job_nm_profile: bad tile range / NULL offsets"); return CVX_ERR_ARG; }
 	if (count == 0) return CVX_OK;
@@ -285,6 +288,7 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 	if (kernel_ms) *kernel_ms = 0.0;
 	if (regions) *regions = nullptr;
 	if (!h || !j || j->state < kFinished) { set_err("cvx_job_nm_regions: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->ladder) { set_err("cvx_job_nm_regions: the stages of a finished job do not take a ladder job (cvx_submit_ladder)"); return CVX_ERR_ARG; }
 	if (!j->text_done) { set_err("cvx_job_nm_regions: call cvx_job_text first"); return CVX_ERR_ARG; }
 	if (first < 0 || count < 0 || (int64_t) first + count > j->n || (count > 0 && (!region_off || !regions))) { set_err("cvx_job_nm_regions: bad tile range / NULL output"); return CVX_ERR_ARG; }
 	if (count == 0) return CVX_OK;

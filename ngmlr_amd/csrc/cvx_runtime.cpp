@@ -424,6 +424,7 @@ void cvx_destroy(cvx_handle h) {
 	for (cvx_batch_s *b : h->live) { b->release(); delete b; }
 	h->live.clear();
 	h->pending.clear();
+	h->climbing.clear();
 	score_state_free(h->score);
 	search_state_free(h->search);
 	delete h;
