@@ -471,12 +471,36 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				float lc = lcv, dc = diag_cell, uc = uV;
 				/* SCALED: one v_max3_f32 with the clamp bit.  The sign of a zero result is the instruction's; it is not observable: a
 				 * zero is never positive and enters compares only as equal to zero */
-				const float mx = SCALED ? __builtin_amdgcn_fmed3f(fmaxf(fmaxf(lc, dc), uc), 0.0f, 1.0f) : fmaxf(fmaxf(fmaxf(lc, dc), uc), 0.0f);
-				p_lc[j] = lc; p_dc[j] = dc; p_uc[j] = uc; p_mx[j] = mx;
-				p_eL[j] = ballot(mx == lc);
-				p_eU[j] = ballot(mx == uc);
-				p_eG[j] = ballot(mx == dc);
-				p_act[j] = ballot((unsigned) cnt[j] < (unsigned) len[j]);
+				if (FAST) {
+					/* Row activity through EXEC: v_cmpx writes act = cnt < len to EXEC as well, the clamped maximum is then written
+					 * into a register that holds 0 and the three equalities into masks that come back clear outside the row -- sc
+					 * without its select, nD and nI without their `& act` (phase2, phase3), one half-rate op and one scalar op less
+					 * per cell for one full-rate v_mov.  Everything else of the slot runs under full EXEC, outside the block: a lane
+					 * outside its row still shifts its plane words, counts, rotates and offers.  EXEC goes back to all lanes: the
+					 * workgroup is one full wave (no gang) and the step loops are wave-uniform -- a constant, because a saved copy
+					 * handed in changed the code of the other forms.  Five instructions lie between v_cmpx and whatever follows the
+					 * block, the wait states a DPP op needs after a VALU write of EXEC; the compiler does not look inside
+					 * (profiles/r26_fill_cell.txt) */
+					float sc = 0.0f;
+					u64 act, eL, eU, eG;
+					asm volatile("v_cmpx_lt_u32_e64 %1, %5, %6\n\t"
+					             "v_max3_f32 %0, %7, %8, %9 clamp\n\t"
+					             "v_cmp_eq_f32_e64 %2, %0, %7\n\t"
+					             "v_cmp_eq_f32_e64 %3, %0, %9\n\t"
+					             "v_cmp_eq_f32_e64 %4, %0, %8\n\t"
+					             "s_mov_b64 exec, -1"
+					             : "+v"(sc), "=&s"(act), "=&s"(eL), "=&s"(eU), "=&s"(eG)
+					             : "v"(cnt[j]), "v"(len[j]), "v"(lc), "v"(dc), "v"(uc));
+					p_lc[j] = lc; p_dc[j] = dc; p_uc[j] = uc; p_mx[j] = sc;
+					p_eL[j] = asm_mask(eL); p_eU[j] = asm_mask(eU); p_eG[j] = asm_mask(eG); p_act[j] = asm_mask(act);
+				} else {
+					const float mx = SCALED ? __builtin_amdgcn_fmed3f(fmaxf(fmaxf(lc, dc), uc), 0.0f, 1.0f) : fmaxf(fmaxf(fmaxf(lc, dc), uc), 0.0f);
+					p_lc[j] = lc; p_dc[j] = dc; p_uc[j] = uc; p_mx[j] = mx;
+					p_eL[j] = ballot(mx == lc);
+					p_eU[j] = ballot(mx == uc);
+					p_eG[j] = ballot(mx == dc);
+					p_act[j] = ballot((unsigned) cnt[j] < (unsigned) len[j]);
+				}
 				p_isDl[j] = WRAP ? ballot(drun[j] > 0) : mD[j];
 				p_isIu[j] = WRAP ? ballot(uI > 0) : mIu;
 			};
@@ -486,8 +510,9 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				 * (src/ConvexAlignFast.cpp:703-738), on lane masks; nothing fires on a
 				 * lane that is outside its row */
 				const u64 c2 = isIu & eU;
-				const u64 nD = eL & (isDl | ~(c2 | eG)) & act;
-				const u64 nI = ~nD & eU & (isIu | ~eG) & act;
+				/* (FAST: the equalities are clear outside the row already) */
+				const u64 nD = FAST ? eL & (isDl | ~(c2 | eG)) : eL & (isDl | ~(c2 | eG)) & act;
+				const u64 nI = FAST ? ~nD & eU & (isIu | ~eG) : ~nD & eU & (isIu | ~eG) & act;
 				p_nD[j] = nD; p_nI[j] = nI;
 				p_gap[j] = nD | nI;
 				/* plane 1 = nI | nG with nG = eG & ~gap & act; the act term is dropped: direction
@@ -499,8 +524,8 @@ CVX_FILL_KERNEL(const FillArgs a) {
 				const run_t uI = (j > 0) ? irun[j > 0 ? j - 1 : 0] : uI0;
 				const u64 nD = p_nD[j], nI = p_nI[j], isDl = p_isDl[j], isIu = p_isIu[j];
 				const float mx = p_mx[j];
-				/* outside the row the new "cell" is the empty element: score 0 */
-				const float sc = lanes(p_act[j]) ? mx : 0.0f;
+				/* outside the row the new "cell" is the empty element: score 0 (FAST: p_mx is that already) */
+				const float sc = FAST ? mx : (lanes(p_act[j]) ? mx : 0.0f);
 				run_t nd, ni;
 				float runf = 0.0f;
 				if (FAST) {

@@ -187,6 +187,11 @@ template <typename T> CVX_DEV T *in_sgpr(T *p) {
 	return (T *) (((u64) hi << 32) | (u64) lo);
 }
 CVX_DEV bool lanes(u64 m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+/* A lane mask that inline assembly wrote to an SGPR pair: the compiler takes the outputs of an asm with a vector output for
+ * per-lane values and would move the mask logic behind them to the VALU; readfirstlane of a scalar register is a copy it folds away */
+CVX_DEV u64 asm_mask(u64 m) {
+	return ((u64) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) (m >> 32)) << 32) | (u64) (unsigned) __builtin_amdgcn_readfirstlane((int) (unsigned) m);
+}
 /* mask of lane i <- mask of lane (i-1) mod 64 : the SALU twin of wave_ror:1 */
 CVX_DEV u64 rot1_m(u64 m) { return (m << 1) | (m >> 63); }
 /* acc = (acc << 1) | (lane's bit of m): one v_addc_co_u32 with the mask as carry-in.
