@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cvx_align.h"
+#include "cvx_buf.h"
 #include "cvx_host_logic.h"
 #include "cvx_inv_checks_dev.h"
 #include "cvx_launch.h"
@@ -31,6 +32,16 @@ using namespace cvx;      /* (only the runtime's own files include this header, 
 		if (e_ != hipSuccess) {                                                    \
 			set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
 			return (e_ == hipErrorOutOfMemory) ? CVX_ERR_OOM : CVX_ERR_HIP;        \
+		}                                                                          \
+	} while (0)
+
+/* the same for an entry that reports every HIP failure after its allocations as CVX_ERR_HIP, under its own name */
+#define HIP_TRY_IN(who, expr)                                                      \
+	do {                                                                           \
+		hipError_t e_ = (expr);                                                    \
+		if (e_ != hipSuccess) {                                                    \
+			set_err("%s: %s", who, hipGetErrorString(e_));                         \
+			return CVX_ERR_HIP;                                                    \
 		}                                                                          \
 	} while (0)
 
@@ -62,86 +73,43 @@ struct DeferredFrees {
 };
 extern DeferredFrees g_deferred;
 
-template <typename T>
-struct DevBuf {
-	T *p = nullptr;
-	size_t cap = 0; /* elements */
-	size_t *hwm = nullptr;      /* shared by the same buffer of every job slot of the handle (bytes) */
-	int ensure(size_t n) {
-		if (n <= cap) return CVX_OK;
-		const size_t old = cap;
-		if (p) {
-			std::lock_guard<std::mutex> lk(g_deferred.mtx);
-			g_deferred.dev.push_back(p);
-			p = nullptr; cap = 0;
-		}
-		const size_t asked = n + n / 8 + 64;
-		size_t want = asked;
-		if (want < 2 * old) want = 2 * old;      /* a buffer that has to grow at least doubles; the first allocation stays close to what was asked for */
-		if (hwm && want * sizeof(T) < *hwm && *hwm / 16 <= asked * sizeof(T)) want = (*hwm + sizeof(T) - 1) / sizeof(T);      /* (never more than 16 x what was asked for) */
-		hipError_t e = hipMalloc((void **) &p, want * sizeof(T));
-		if (e != hipSuccess && want > asked) {      /* the generous size does not fit: give back what is parked, then what was asked for may */
-			(void) hipGetLastError();
-			g_deferred.drain();
-			want = asked;
-			e = hipMalloc((void **) &p, want * sizeof(T));
-		}
-		if (e != hipSuccess) {
-			set_err("hipMalloc(%zu bytes) failed: %s", want * sizeof(T), hipGetErrorString(e));
-			p = nullptr;
-			return CVX_ERR_OOM;
-		}
-		cap = want;
-		if (hwm && cap * sizeof(T) > *hwm) *hwm = cap * sizeof(T);
-		return CVX_OK;
-	}
-	void release() {
-		if (p) (void) hipFree(p);
-		p = nullptr;
-		cap = 0;
-	}
+/* the two memories of cvx_buf.h's buffer: an outgrown block is parked in g_deferred, a buffer that dies frees its block at once */
+struct DevMem {
+	static constexpr size_t kSlack = 64;
+	static constexpr const char *kName = "hipMalloc";
+	static const char *alloc(void **p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes); return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+	static void free(void *p) { (void) hipFree(p); }
+	static void park(void *p) { std::lock_guard<std::mutex> lk(g_deferred.mtx); g_deferred.dev.push_back(p); }
+	static void drain() { (void) hipGetLastError(); g_deferred.drain(); }      /* (a failed hipMalloc's error is cleared where a retry follows, and only there) */
 };
+struct PinMem {
+	static constexpr size_t kSlack = 4096;
+	static constexpr const char *kName = "hipHostMalloc";
+	static const char *alloc(void **p, size_t bytes) {
+		const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+		if (e == hipSuccess) return nullptr;
+		(void) hipGetLastError();
+		return hipGetErrorString(e);
+	}
+	static void free(void *p) { (void) hipHostFree(p); }
+	static void park(void *p) { std::lock_guard<std::mutex> lk(g_deferred.mtx); g_deferred.host.push_back(p); }
+	static void drain() { g_deferred.drain(); }
+};
+template <typename T> using DevBuf = Buf<T, DevMem>;      /* cap in elements */
+using PinBuf = Buf<void, PinMem>;                         /* grow-only page-locked host buffer, cap in bytes */
 
-/* grow-only page-locked host buffer */
-struct PinBuf {
-	void *p = nullptr;
-	size_t cap = 0; /* bytes */
-	size_t *hwm = nullptr;
-	int ensure(size_t bytes) {
-		if (bytes <= cap) return CVX_OK;
-		const size_t old = cap;
-		if (p) {
-			std::lock_guard<std::mutex> lk(g_deferred.mtx);
-			g_deferred.host.push_back(p);
-			p = nullptr; cap = 0;
-		}
-		const size_t asked = bytes + bytes / 8 + 4096;
-		size_t want = asked;
-		if (want < 2 * old) want = 2 * old;                     /* (see DevBuf::ensure) */
-		if (hwm && want < *hwm && *hwm / 16 <= asked) want = *hwm;
-		hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-		if (e != hipSuccess && want > asked) {
-			(void) hipGetLastError();
-			g_deferred.drain();
-			want = asked;
-			e = hipHostMalloc(&p, want, hipHostMallocDefault);
-		}
-		if (e != hipSuccess) {
-			(void) hipGetLastError();
-			set_err("hipHostMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-			p = nullptr;
-			return CVX_ERR_OOM;
-		}
-		cap = want;
-		if (hwm && cap > *hwm) *hwm = cap;
-		return CVX_OK;
-	}
-	void release() {
-		if (p) (void) hipHostFree(p);
-		p = nullptr;
-		cap = 0;
-	}
-	template <typename T> T *as() const { return static_cast<T *>(p); }
+/* an event made when first asked for, with the flags of its site, and destroyed with its owner */
+struct Event {
+	hipEvent_t e = nullptr;
+	Event() = default;
+	Event(const Event &) = delete;
+	Event &operator=(const Event &) = delete;
+	Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+	Event &operator=(Event &&o) noexcept { if (this != &o) { reset(); e = o.e; o.e = nullptr; } return *this; }
+	~Event() { reset(); }
+	hipError_t make(unsigned flags = hipEventDefault) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+	void reset() { if (e) (void) hipEventDestroy(e); e = nullptr; }
+	operator hipEvent_t() const { return e; }
 };
 
 bool in_pinned_block(const void *p, uint64_t bytes);      /* [p, p + bytes) lies inside one block of cvx_host_alloc */
@@ -224,7 +192,7 @@ struct cvx_batch_s {
 	DevBuf<int32_t> d_nm;            /* ... and the triples */
 	PinBuf h_nmoff;
 	PinBuf h_nm;                     /* the triples on the host (cvx_job_nm_profile_resident) */
-	hipEvent_t ev_nm0 = nullptr, ev_nm1 = nullptr;
+	Event ev_nm0, ev_nm1;
 	DevBuf<unsigned long long> d_nmroff; /* the profile's low-identity regions (cvx_job_nm_regions): counts, offsets, total of the tile range */
 	DevBuf<NmOpen> d_nmopen;         /* ... the state every tile's scan ends in */
 	DevBuf<NmRegion> d_nmstage;      /* ... kNmStage regions per tile as the first pass found them */
@@ -279,11 +247,11 @@ struct cvx_batch_s {
 	PinBuf h_lad;
 	PinBuf h_lres, h_lops, h_lout;   /* rung 1: the job's answer merged by cvx_wait -- ResultRec[n], dense ops, cvx_ladder_result[n] */
 
-	hipEvent_t ev_bt0 = nullptr, ev_bt1 = nullptr;   /* fork / join of the long-read backtrack launch */
-	hipEvent_t ev_in = nullptr;      /* upload + plan records on the host */
-	hipEvent_t ev_res = nullptr;     /* result records on the host */
-	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   /* timing: plan begin/end, fills done, all done, fills may start */
-	std::vector<hipEvent_t> lev;     /* kLevPerLaunch events per fill launch (LaunchEvent) */
+	Event ev_bt0, ev_bt1;   /* fork / join of the long-read backtrack launch */
+	Event ev_in;      /* upload + plan records on the host */
+	Event ev_res;     /* result records on the host */
+	Event ev[5];   /* timing: plan begin/end, fills done, all done, fills may start */
+	std::vector<Event> lev;     /* kLevPerLaunch events per fill launch (LaunchEvent) */
 	std::vector<cvx_launch_info> launches;
 	std::vector<int> launch_tail;    /* per fill launch: tiles of its tail (0: not split, its tail events were not recorded) */
 	cvx_timing timing;
@@ -310,45 +278,11 @@ struct cvx_batch_s {
 		static_assert(11 + 17 + 4 + 4 <= kSharedMarks, "marks");
 	}
 	int make_events() {
-		if (!ev_in) HIP_TRY(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-		if (!ev_res) HIP_TRY(hipEventCreateWithFlags(&ev_res, hipEventDisableTiming));
-		if (!ev_bt0) HIP_TRY(hipEventCreateWithFlags(&ev_bt0, hipEventDisableTiming));
-		if (!ev_bt1) HIP_TRY(hipEventCreateWithFlags(&ev_bt1, hipEventDisableTiming));
-		for (auto &e : ev) if (!e) HIP_TRY(hipEventCreate(&e));
+		for (Event *e : { &ev_in, &ev_res, &ev_bt0, &ev_bt1 }) HIP_TRY(e->make(hipEventDisableTiming));
+		for (Event &e : ev) HIP_TRY(e.make());
 		return CVX_OK;
 	}
-	void release() {
-		if (ladder) ladder_drop(this);
-		ladder_root = nullptr;
-		d_lhead.release(); h_lhead.release(); d_lad.release(); h_lad.release(); h_lres.release(); h_lops.release(); h_lout.release();
-		h_zero.release(); zero_cap = 0;
-		h_seq.release(); h_delta.release(); h_rsrc.release(); h_rowsx.release(); h_tin.release();
-		d_delta.release(); d_rsrc.release(); d_rowsx.release(); h_plan.release(); h_trun.release(); h_tout.release();
-		h_lists.release(); h_goff.release(); h_res.release(); h_ops.release();
-		d_seq.release(); d_rows.release(); d_tin.release(); d_plan.release(); d_trun.release();
-		d_tout.release(); d_dirs.release(); d_regions.release(); d_lists.release();
-		d_counters.release(); d_dstoff.release(); d_dense.release(); d_res.release();
-		d_gscratch.release(); d_gscratch_off.release();
-		h_win.release(); d_win.release(); h_refs.release();
-		h_reads.release(); h_segs.release(); d_reads.release(); d_segs.release();
-		h_ext.release(); h_trec.release(); h_toff.release(); h_text.release();
-		d_ext.release(); d_trec.release(); d_tlen.release(); d_text.release();
-		d_nmoff.release(); d_nm.release(); h_nmoff.release(); h_nm.release();
-		d_nmroff.release(); d_nmopen.release(); d_nmstage.release(); d_nmreg.release(); h_nmroff.release(); h_nmopen.release(); h_nmreg.release();
-		d_jroff.release(); d_jropen.release(); d_jrstage.release(); d_jrreg.release(); h_jroff.release(); h_jropen.release(); h_jrreg.release();
-		d_jrchk.release(); h_jrchk.release();
-		d_jtrec.release(); d_jtoff.release(); d_jtext.release(); h_jtrec.release(); h_jtoff.release(); h_jtext.release();
-		if (ev_nm0) { (void) hipEventDestroy(ev_nm0); ev_nm0 = nullptr; }
-		if (ev_nm1) { (void) hipEventDestroy(ev_nm1); ev_nm1 = nullptr; }
-		h_chain.release(); d_chain.release(); d_bnd.release(); d_chain_out.release();
-		if (ev_in) { (void) hipEventDestroy(ev_in); ev_in = nullptr; }
-		if (ev_res) { (void) hipEventDestroy(ev_res); ev_res = nullptr; }
-		if (ev_bt0) { (void) hipEventDestroy(ev_bt0); ev_bt0 = nullptr; }
-		if (ev_bt1) { (void) hipEventDestroy(ev_bt1); ev_bt1 = nullptr; }
-		for (auto &e : ev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
-		for (auto &e : lev) if (e) (void) hipEventDestroy(e);
-		lev.clear();
-	}
+	~cvx_batch_s() { if (ladder) ladder_drop(this); }      /* a ladder job's later rungs go with it; the buffers and events free themselves */
 };
 
 /* The ladder of one job.  Where a tile's reported record and ops are kept: every rung's batch keeps its own result block and

@@ -96,7 +96,6 @@ void recycle_batch(cvx_context *h, cvx_batch_s *b) {
 	}
 	/* (a job that failed half-way keeps nothing worth pooling: its arenas go back to the allocator) */
 	if (h && !failed && h->pool.size() < kPoolBatches) { h->pool.push_back(b); return; }
-	b->release();
 	delete b;
 }
 
@@ -112,7 +111,6 @@ void discard_batch(cvx_context *h, cvx_batch_s *b) {
 		it = std::find(h->climbing.begin(), h->climbing.end(), b);
 		if (it != h->climbing.end()) h->climbing.erase(it);
 	}
-	b->release();
 	delete b;
 }
 
@@ -580,14 +578,14 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	fill_streams[kOnSide0] = S_aux[0]; fill_streams[kOnPost] = S_post; fill_streams[kOnMain] = st; fill_streams[kOnSide1] = S_aux[1];
 	const int launches = (int) sch.launches.size();
 	while (b->lev.size() < (size_t) launches * kLevPerLaunch) {
-		hipEvent_t e;
-		HIP_TRY(hipEventCreate(&e));
-		b->lev.push_back(e);
+		Event e;
+		HIP_TRY(e.make());
+		b->lev.push_back(std::move(e));
 	}
 	for (int i = 0; i < launches; ++i) {
 		const FillLaunch &L = sch.launches[(size_t) i];
 		const hipStream_t ls = fill_streams[L.stream];
-		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		const Event *le = &b->lev[(size_t) i * kLevPerLaunch];
 		const bool wrap = L.wrap != 0;
 		b->launches.push_back(L.info);
 		b->launch_tail.push_back(L.tail_count);
@@ -710,7 +708,7 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	}
 	const int launches = b->timing.n_fill_launches;
 	for (int i = 0; i < launches; ++i) {
-		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		const Event *le = &b->lev[(size_t) i * kLevPerLaunch];
 		b->launches[(size_t) i].ms = ev_ms(le[kLevStart], le[kLevTwoPhase]);
 		/* a split class: one record, from the head's start to the later of the two two-phase ends */
 		if (b->launch_tail[(size_t) i] > 0) b->launches[(size_t) i].ms = std::max(b->launches[(size_t) i].ms, ev_ms(le[kLevStart], le[kLevTailTwoPhase]));
@@ -720,7 +718,7 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	 * class is walked behind its own fill, the walks of the early classes lie inside `fill`: the two still add up) */
 	float fill_end = 0.0f;
 	for (int i = 0; i < launches; ++i) {
-		const hipEvent_t *le = &b->lev[(size_t) i * kLevPerLaunch];
+		const Event *le = &b->lev[(size_t) i * kLevPerLaunch];
 		fill_end = std::max(fill_end, ev_ms(b->ev[4], le[kLevExact]));
 		if (b->launch_tail[(size_t) i] > 0) {      /* (the head's walk then lies inside `fill`: it runs while the tail still fills) */
 			fill_end = std::max(fill_end, ev_ms(b->ev[4], le[kLevTailExact]));
@@ -1036,17 +1034,13 @@ int stage_segments_plan(const char *who, int32_t n_reads, const uint8_t *arena, 
 
 }  // namespace
 
-/* cvx_batch_s::release of a ladder job (cvx_destroy, a failed submit): the later rungs' batches go back to the allocator with it */
+/* a ladder job is deleted (cvx_destroy, a failed submit): the later rungs' batches go back to the allocator with it */
 void ladder_drop(cvx_batch_s *root) {
 	LadderState *L = root->ladder;
 	root->ladder = nullptr;
 	if (!L) return;
 	if (L->next) L->rungs.push_back(L->next);
-	for (size_t r = 1; r < L->rungs.size(); ++r) {
-		L->rungs[r]->ladder_root = nullptr;
-		L->rungs[r]->release();
-		delete L->rungs[r];
-	}
+	for (size_t r = 1; r < L->rungs.size(); ++r) delete L->rungs[r];
 	delete L;
 }
 
@@ -1331,6 +1325,30 @@ int cvx_job_zero_copy_bytes(cvx_job j, uint64_t *bytes) {
 
 /* the kernel alone: the strings back to back in a device arena of their own, and back (nothing here is on the path of a job,
  * so the buffers are the call's own) */
+static int stage_segments_run(cvx_handle h, const SegPlan &sp, const uint8_t *arena, const uint64_t *offsets, int32_t n, uint8_t *out) {
+	static const char who[] = "cvx_stage_segments";
+	const size_t dbytes = (size_t) n * sizeof(SegDesc), cbytes = sp.chunks.size() * sizeof(SegChunk);
+	DevBuf<uint8_t> d_reads, d_segs, d_out;
+	Event e0, e1;
+	RC_TRY(d_reads.ensure((size_t) sp.read_bytes + 256));
+	RC_TRY(d_segs.ensure(dbytes + cbytes + 64));
+	RC_TRY(d_out.ensure((size_t) sp.seg_bytes + 256));
+	hipStream_t st = h->s_main;
+	HIP_TRY_IN(who, e0.make());
+	HIP_TRY_IN(who, e1.make());
+	HIP_TRY_IN(who, hipMemcpyAsync(d_reads.p, arena + offsets[0], (size_t) sp.read_bytes, hipMemcpyHostToDevice, st));
+	HIP_TRY_IN(who, hipMemcpyAsync(d_segs.p, sp.desc.data(), dbytes, hipMemcpyHostToDevice, st));
+	HIP_TRY_IN(who, hipMemcpyAsync(d_segs.p + dbytes, sp.chunks.data(), cbytes, hipMemcpyHostToDevice, st));
+	HIP_TRY_IN(who, hipEventRecord(e0, st));
+	HIP_TRY_IN(who, launch_stage_segments(d_reads.p, reinterpret_cast<const SegDesc *>(d_segs.p), reinterpret_cast<const SegChunk *>(d_segs.p + dbytes),
+			(int) sp.chunks.size(), d_out.p, st));
+	HIP_TRY_IN(who, hipEventRecord(e1, st));
+	HIP_TRY_IN(who, hipMemcpyAsync(out, d_out.p, (size_t) sp.seg_bytes, hipMemcpyDeviceToHost, st));
+	HIP_TRY_IN(who, hipStreamSynchronize(st));
+	h->segments_kernel_ms = ev_ms(e0, e1);
+	return CVX_OK;
+}
+
 int cvx_stage_segments(cvx_handle h, int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, int32_t n,
 		const cvx_read_segment *seg, const int32_t *len, uint8_t *out, uint64_t cap, uint64_t *qry_off, uint64_t *used) {
 	ABI_GUARD_BEGIN
@@ -1340,34 +1358,9 @@ int cvx_stage_segments(cvx_handle h, int32_t n_reads, const uint8_t *arena, cons
 	if (sp.chunks.empty()) return CVX_OK;
 	HIP_TRY(hipSetDevice(h->device));
 	RC_TRY(ensure_streams(h));
-	const size_t dbytes = (size_t) n * sizeof(SegDesc), cbytes = sp.chunks.size() * sizeof(SegChunk);
-	DevBuf<uint8_t> d_reads, d_segs, d_out;
-	int rc = d_reads.ensure((size_t) sp.read_bytes + 256);
-	if (rc == CVX_OK) rc = d_segs.ensure(dbytes + cbytes + 64);
-	if (rc == CVX_OK) rc = d_out.ensure((size_t) sp.seg_bytes + 256);
-	hipError_t e = hipSuccess;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	if (rc == CVX_OK) {
-		hipStream_t st = h->s_main;
-		e = hipEventCreate(&e0);
-		if (e == hipSuccess) e = hipEventCreate(&e1);
-		if (e == hipSuccess) e = hipMemcpyAsync(d_reads.p, arena + offsets[0], (size_t) sp.read_bytes, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(d_segs.p, sp.desc.data(), dbytes, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(d_segs.p + dbytes, sp.chunks.data(), cbytes, hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) e = hipEventRecord(e0, st);
-		if (e == hipSuccess) e = launch_stage_segments(d_reads.p, reinterpret_cast<const SegDesc *>(d_segs.p), reinterpret_cast<const SegChunk *>(d_segs.p + dbytes),
-				(int) sp.chunks.size(), d_out.p, st);
-		if (e == hipSuccess) e = hipEventRecord(e1, st);
-		if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t) sp.seg_bytes, hipMemcpyDeviceToHost, st);
-		if (e == hipSuccess) e = hipStreamSynchronize(st);
-		if (e == hipSuccess) h->segments_kernel_ms = ev_ms(e0, e1);
-	}
-	if (e0) (void) hipEventDestroy(e0);
-	if (e1) (void) hipEventDestroy(e1);
-	d_reads.release(); d_segs.release(); d_out.release();
-	if (rc != CVX_OK) return rc;
-	if (e != hipSuccess) { (void) hipGetLastError(); set_err("cvx_stage_segments: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
-	return CVX_OK;
+	const int rc = stage_segments_run(h, sp, arena, offsets, n, out);
+	if (rc == CVX_ERR_HIP) (void) hipGetLastError();      /* (a HIP call of the run failed: the next call starts clean) */
+	return rc;
 	ABI_GUARD_END
 }
 
@@ -1490,24 +1483,19 @@ int cvx_corridor_rows(cvx_handle h, const cvx_tile *tile, int32_t *offset, int32
 	TileIn ti;
 	memset(&ti, 0, sizeof(ti));
 	ti.H = H;
+	static const char who[] = "cvx_corridor_rows";
+	std::vector<RowDesc> rows((size_t) H);
 	DevBuf<RowSrc> d_rs;
 	DevBuf<TileIn> d_ti;
 	DevBuf<RowDesc> d_rows;
-	int rc = d_rs.ensure(1);
-	if (rc == CVX_OK) rc = d_ti.ensure(1);
-	if (rc == CVX_OK) rc = d_rows.ensure((size_t) H);
-	std::vector<RowDesc> rows((size_t) H);
-	hipError_t e = hipSuccess;
-	if (rc == CVX_OK) {
-		e = hipMemcpy(d_rs.p, &rs, sizeof(rs), hipMemcpyHostToDevice);
-		if (e == hipSuccess) e = hipMemcpy(d_ti.p, &ti, sizeof(ti), hipMemcpyHostToDevice);
-		if (e == hipSuccess) e = launch_expand_rows(d_rs.p, d_ti.p, nullptr, nullptr, d_rows.p, 1, true, h->s_main);
-		if (e == hipSuccess) e = hipStreamSynchronize(h->s_main);
-		if (e == hipSuccess) e = hipMemcpy(rows.data(), d_rows.p, (size_t) H * sizeof(RowDesc), hipMemcpyDeviceToHost);
-	}
-	d_rs.release(); d_ti.release(); d_rows.release();
-	if (rc != CVX_OK) return rc;
-	if (e != hipSuccess) { set_err("cvx_corridor_rows: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
+	RC_TRY(d_rs.ensure(1));
+	RC_TRY(d_ti.ensure(1));
+	RC_TRY(d_rows.ensure((size_t) H));
+	HIP_TRY_IN(who, hipMemcpy(d_rs.p, &rs, sizeof(rs), hipMemcpyHostToDevice));
+	HIP_TRY_IN(who, hipMemcpy(d_ti.p, &ti, sizeof(ti), hipMemcpyHostToDevice));
+	HIP_TRY_IN(who, launch_expand_rows(d_rs.p, d_ti.p, nullptr, nullptr, d_rows.p, 1, true, h->s_main));
+	HIP_TRY_IN(who, hipStreamSynchronize(h->s_main));
+	HIP_TRY_IN(who, hipMemcpy(rows.data(), d_rows.p, (size_t) H * sizeof(RowDesc), hipMemcpyDeviceToHost));
 	for (int y = 0; y < H; ++y) { offset[y] = rows[(size_t) y].off; length[y] = rows[(size_t) y].len; }
 	return CVX_OK;
 	ABI_GUARD_END

@@ -26,6 +26,53 @@ int checks_args(const char *who, int32_t n_tiles, const char *const *qrys, const
 	return CVX_OK;
 }
 
+/* the device side of cvx_inv_checks: the call's buffers and events belong to the entry, which waits for the device before they go */
+struct InvChecksBufs {
+	DevBuf<uint8_t> d_seq;
+	DevBuf<TileIn> d_tin;
+	DevBuf<WindowDesc> d_win;
+	DevBuf<ResultRec> d_rec;
+	DevBuf<unsigned long long> d_off;
+	DevBuf<NmRegion> d_reg;
+	DevBuf<InvCheck> d_chk;
+	Event e0, e1;
+};
+
+int inv_checks_run(cvx_handle h, cvx_genome g, const std::vector<uint8_t> &seq, const std::vector<TileIn> &tin, const std::vector<WindowDesc> &win,
+		const std::vector<ResultRec> &rec, const std::vector<unsigned long long> &off, const cvx_nm_region *regions, uint64_t total,
+		cvx_inv_check *checks, double *kernel_ms, InvChecksBufs &b) {
+	const size_t n1 = tin.size();
+	RC_TRY(b.d_seq.ensure(seq.size()));
+	RC_TRY(b.d_tin.ensure(n1));
+	RC_TRY(b.d_win.ensure(n1));
+	RC_TRY(b.d_rec.ensure(n1));
+	RC_TRY(b.d_off.ensure(n1 + 1));
+	RC_TRY(b.d_reg.ensure((size_t) total));
+	RC_TRY(b.d_chk.ensure((size_t) total));
+	HIP_TRY(b.e0.make());
+	HIP_TRY(b.e1.make());
+	hipStream_t st = h->s_main;
+	HIP_TRY(hipMemcpyAsync(b.d_seq.p, seq.data(), seq.size(), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(b.d_tin.p, tin.data(), n1 * sizeof(TileIn), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(b.d_win.p, win.data(), n1 * sizeof(WindowDesc), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(b.d_rec.p, rec.data(), n1 * sizeof(ResultRec), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(b.d_off.p, off.data(), (n1 + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(b.d_reg.p, regions, (size_t) total * sizeof(NmRegion), hipMemcpyHostToDevice, st));
+	InvCheckArgs a;
+	memset(&a, 0, sizeof(a));
+	a.bin = g->d_bin.p; a.L = score_windows_concat_len(g->n_nibbles);
+	a.seq = b.d_seq.p; a.tin = b.d_tin.p; a.win = b.d_win.p; a.rec = b.d_rec.p;
+	a.off = b.d_off.p; a.regions = b.d_reg.p; a.checks = b.d_chk.p;
+	a.cap = total; a.n_tiles = (int32_t) n1;
+	HIP_TRY(hipEventRecord(b.e0, st));
+	HIP_TRY(launch_inv_checks(a, total, st));
+	HIP_TRY(hipEventRecord(b.e1, st));
+	HIP_TRY(hipMemcpyAsync(checks, b.d_chk.p, (size_t) total * sizeof(InvCheck), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	if (kernel_ms) *kernel_ms = (double) ev_ms(b.e0, b.e1);
+	return CVX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -79,50 +126,9 @@ int cvx_inv_checks(cvx_handle h, cvx_genome g, int32_t n_tiles, const char *cons
 	std::vector<uint8_t> seq((size_t) seq_bytes + 4, 0);
 	for (size_t i = 0; i < n1; ++i)
 		if (qry_len[i] > 0) memcpy(seq.data() + tin[i].qry_off, qrys[i], (size_t) qry_len[i]);
-	DevBuf<uint8_t> d_seq;
-	DevBuf<TileIn> d_tin;
-	DevBuf<WindowDesc> d_win;
-	DevBuf<ResultRec> d_rec;
-	DevBuf<unsigned long long> d_off;
-	DevBuf<NmRegion> d_reg;
-	DevBuf<InvCheck> d_chk;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	auto body = [&]() -> int {
-		RC_TRY(d_seq.ensure(seq.size()));
-		RC_TRY(d_tin.ensure(n1));
-		RC_TRY(d_win.ensure(n1));
-		RC_TRY(d_rec.ensure(n1));
-		RC_TRY(d_off.ensure(n1 + 1));
-		RC_TRY(d_reg.ensure((size_t) total));
-		RC_TRY(d_chk.ensure((size_t) total));
-		HIP_TRY(hipEventCreate(&e0));
-		HIP_TRY(hipEventCreate(&e1));
-		hipStream_t st = h->s_main;
-		HIP_TRY(hipMemcpyAsync(d_seq.p, seq.data(), seq.size(), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_tin.p, tin.data(), n1 * sizeof(TileIn), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_win.p, win.data(), n1 * sizeof(WindowDesc), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_rec.p, rec.data(), n1 * sizeof(ResultRec), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), (n1 + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_reg.p, regions, (size_t) total * sizeof(NmRegion), hipMemcpyHostToDevice, st));
-		InvCheckArgs a;
-		memset(&a, 0, sizeof(a));
-		a.bin = g->d_bin.p; a.L = score_windows_concat_len(g->n_nibbles);
-		a.seq = d_seq.p; a.tin = d_tin.p; a.win = d_win.p; a.rec = d_rec.p;
-		a.off = d_off.p; a.regions = d_reg.p; a.checks = d_chk.p;
-		a.cap = total; a.n_tiles = n_tiles;
-		HIP_TRY(hipEventRecord(e0, st));
-		HIP_TRY(launch_inv_checks(a, total, st));
-		HIP_TRY(hipEventRecord(e1, st));
-		HIP_TRY(hipMemcpyAsync(checks, d_chk.p, (size_t) total * sizeof(InvCheck), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (kernel_ms) *kernel_ms = (double) ev_ms(e0, e1);
-		return CVX_OK;
-	};
-	const int rc = body();
+	InvChecksBufs b;
+	const int rc = inv_checks_run(h, g, seq, tin, win, rec, off, regions, total, checks, kernel_ms, b);
 	if (rc != CVX_OK) (void) hipDeviceSynchronize();      /* nothing may still read the call's buffers when they go */
-	if (e0) (void) hipEventDestroy(e0);
-	if (e1) (void) hipEventDestroy(e1);
-	d_seq.release(); d_tin.release(); d_win.release(); d_rec.release(); d_off.release(); d_reg.release(); d_chk.release();
 	return rc;
 	ABI_GUARD_END
 }

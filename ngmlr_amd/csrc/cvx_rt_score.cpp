@@ -30,7 +30,7 @@ struct cvx_score_job_s {
 	ScoreWinPlan plan;
 	DevBuf<uint8_t> reads;
 	DevBuf<ScoreWinDesc> desc;
-	hipEvent_t ev_st = nullptr;
+	Event ev_st;
 	std::vector<size_t> rl, ql;      /* per pair: bytes of the reference and of the query, NULs included */
 	std::vector<int> cls;            /* ... and its shape class */
 	std::vector<int32_t> order;
@@ -38,17 +38,7 @@ struct cvx_score_job_s {
 	DevBuf<ScorePair> pairs;
 	DevBuf<int32_t> rows;
 	DevBuf<float> out;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr, done = nullptr;
-	void release() {
-		hseq.release(); hpairs.release(); hout.release(); hreads.release(); hdesc.release();
-		seq.release(); pairs.release(); rows.release(); out.release(); reads.release(); desc.release();
-		if (ev_st) (void) hipEventDestroy(ev_st);
-		ev_st = nullptr;
-		if (ev0) (void) hipEventDestroy(ev0);
-		if (ev1) (void) hipEventDestroy(ev1);
-		if (done) (void) hipEventDestroy(done);
-		ev0 = ev1 = done = nullptr;
-	}
+	Event ev0, ev1, done;
 };
 
 /* a handle's scoring jobs: the ones waited for, kept for reuse, and the ones in flight (cvx_destroy frees both) */
@@ -61,8 +51,8 @@ struct cvx_score_state {
 namespace cvx {
 void score_state_free(cvx_score_state *ss) {
 	if (!ss) return;
-	for (cvx_score_job_s *j : ss->free) { j->release(); delete j; }
-	for (cvx_score_job_s *j : ss->live) { j->release(); delete j; }
+	for (cvx_score_job_s *j : ss->free) delete j;
+	for (cvx_score_job_s *j : ss->live) delete j;
 	delete ss;
 }
 }  // namespace cvx
@@ -110,12 +100,10 @@ int score_launch_classes(cvx_score_job_s *j, const size_t *first, bool whole_cal
 }
 
 int score_job_events(cvx_score_job_s *j) {
-	if (!j->ev0) {
-		HIP_TRY(hipEventCreate(&j->ev0));
-		HIP_TRY(hipEventCreate(&j->ev1));
-		HIP_TRY(hipEventCreate(&j->ev_st));
-		HIP_TRY(hipEventCreateWithFlags(&j->done, hipEventBlockingSync | hipEventDisableTiming));
-	}
+	HIP_TRY(j->ev0.make());
+	HIP_TRY(j->ev1.make());
+	HIP_TRY(j->ev_st.make());
+	HIP_TRY(j->done.make(hipEventBlockingSync | hipEventDisableTiming));
 	return CVX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -34,10 +35,10 @@ struct cvx_search_state {
 	size_t tables_clean_words = 0;     /* this much of d_keys is known to hold nothing but empty slots (search_wave_hbm_kernel's tables) */
 	DevBuf<SearchCandidate> d_cand, d_dense;
 	DevBuf<uint64_t> d_keys;
-	hipEvent_t done = nullptr;
+	Event done;
 	/* kernel time of the last call (cvx_stage_kernel_ms): an event pair around every kernel launch of the call, summed when it ends */
 	std::vector<int32_t> attempts;     /* per read of the last call: table sizes tried (cvx_search_last_attempts) */
-	std::vector<hipEvent_t> kev;
+	std::vector<Event> kev;
 	size_t kev_used = 0;
 	float kernel_ms = 0.0f;
 	/* cvx_search_score_arena: one descriptor, pair, score and status per candidate, the strings of all of them, and the scores and
@@ -48,23 +49,12 @@ struct cvx_search_state {
 	DevBuf<float> d_fout;
 	DevBuf<int32_t> d_fstatus;
 	PinBuf h_fout;
-	hipEvent_t ev_f0 = nullptr, ev_f1 = nullptr;
+	Event ev_f0, ev_f1;
 	float fused_ms = 0.0f;
 	int kmark(hipStream_t st) {
-		if (kev_used == kev.size()) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); kev.push_back(e); }
+		if (kev_used == kev.size()) { Event e; HIP_TRY(e.make()); kev.push_back(std::move(e)); }
 		HIP_TRY(hipEventRecord(kev[kev_used++], st));
 		return CVX_OK;
-	}
-	void release() {
-		for (hipEvent_t e : kev) (void) hipEventDestroy(e);
-		kev.clear(); kev_used = 0;
-		h_seq.release(); h_meta.release(); h_out.release();
-		d_seq.release(); d_off.release(); d_listoff.release(); d_begin.release(); d_srcoff.release(); h_srcoff.release(); d_len.release(); d_ncand.release(); d_work.release(); d_miss.release();
-		d_events.release(); d_maxhit.release(); d_scores.release(); d_rlist.release(); d_undo.release(); d_ticket.release(); d_cand.release(); d_dense.release(); d_keys.release();
-		d_fdesc.release(); d_fpairs.release(); d_fseq.release(); d_fout.release(); d_fstatus.release(); h_fout.release();
-		if (ev_f0) { (void) hipEventDestroy(ev_f0); ev_f0 = nullptr; }
-		if (ev_f1) { (void) hipEventDestroy(ev_f1); ev_f1 = nullptr; }
-		if (done) { (void) hipEventDestroy(done); done = nullptr; }
 	}
 };
 
@@ -80,7 +70,7 @@ struct SearchScoreArgs {
 namespace {
 /* everything queued on `st` so far is done; the calling thread sleeps meanwhile (hipStreamSynchronize spins) */
 int search_wait(cvx_search_state *ss, hipStream_t st) {
-	if (!ss->done) HIP_TRY(hipEventCreateWithFlags(&ss->done, hipEventBlockingSync | hipEventDisableTiming));
+	HIP_TRY(ss->done.make(hipEventBlockingSync | hipEventDisableTiming));
 	HIP_TRY(hipEventRecord(ss->done, st));
 	HIP_TRY(hipEventSynchronize(ss->done));
 	return CVX_OK;
@@ -88,11 +78,7 @@ int search_wait(cvx_search_state *ss, hipStream_t st) {
 }  // namespace
 
 namespace cvx {
-void search_state_free(cvx_search_state *ss) {
-	if (!ss) return;
-	ss->release();
-	delete ss;
-}
+void search_state_free(cvx_search_state *ss) { delete ss; }
 
 float search_kernel_ms(const cvx_search_state *ss) { return ss ? ss->kernel_ms : 0.0f; }
 float search_score_kernel_ms(const cvx_search_state *ss) { return ss ? ss->fused_ms : 0.0f; }
@@ -109,25 +95,19 @@ int cvx_genome_upload(cvx_handle h, const uint8_t *bin_ref, uint64_t n_nibbles, 
 	for (int32_t i = 1; i < n_starts; ++i)
 		if (start_table[i] <= start_table[i - 1]) { set_err("cvx_genome_upload: start table not ascending at %d", i); return CVX_ERR_ARG; }
 	HIP_TRY(hipSetDevice(h->device));
-	cvx_genome_s *g = new (std::nothrow) cvx_genome_s();
+	std::unique_ptr<cvx_genome_s> g(new (std::nothrow) cvx_genome_s());
 	if (!g) return CVX_ERR_OOM;
 	g->device = h->device;
 	g->n_nibbles = n_nibbles;
 	g->n_starts = n_starts;
 	/* a window may start or end in the last spacer: decode() reads up to a byte past the last nibble pair */
 	const size_t bytes = (size_t) ((n_nibbles + 1) / 2);
-	int rc = g->d_bin.ensure(bytes + 64);
-	if (rc == CVX_OK) rc = g->d_starts.ensure((size_t) n_starts);
-	if (rc != CVX_OK) { g->d_bin.release(); g->d_starts.release(); delete g; return rc; }
-	hipError_t e = hipMemset(g->d_bin.p, 0x44, g->d_bin.cap);        /* beyond the genome: N */
-	if (e == hipSuccess) e = hipMemcpy(g->d_bin.p, bin_ref, bytes, hipMemcpyHostToDevice);
-	if (e == hipSuccess) e = hipMemcpy(g->d_starts.p, start_table, (size_t) n_starts * sizeof(uint64_t), hipMemcpyHostToDevice);
-	if (e != hipSuccess) {
-		set_err("cvx_genome_upload: %s", hipGetErrorString(e));
-		g->d_bin.release(); g->d_starts.release(); delete g;
-		return CVX_ERR_HIP;
-	}
-	*out = g;
+	RC_TRY(g->d_bin.ensure(bytes + 64));
+	RC_TRY(g->d_starts.ensure((size_t) n_starts));
+	HIP_TRY_IN("cvx_genome_upload", hipMemset(g->d_bin.p, 0x44, g->d_bin.cap));        /* beyond the genome: N */
+	HIP_TRY_IN("cvx_genome_upload", hipMemcpy(g->d_bin.p, bin_ref, bytes, hipMemcpyHostToDevice));
+	HIP_TRY_IN("cvx_genome_upload", hipMemcpy(g->d_starts.p, start_table, (size_t) n_starts * sizeof(uint64_t), hipMemcpyHostToDevice));
+	*out = g.release();      /* (the unique_ptr's: the caller owns the genome from here) */
 	return CVX_OK;
 	ABI_GUARD_END
 }
@@ -136,8 +116,6 @@ void cvx_genome_free(cvx_handle h, cvx_genome g) {
 	ABI_GUARD_BEGIN
 	if (!g) return;
 	if (h) { (void) hipSetDevice(h->device); (void) hipDeviceSynchronize(); }
-	g->d_bin.release();
-	g->d_starts.release();
 	delete g;
 	ABI_GUARD_END_VOID
 }
@@ -157,29 +135,24 @@ int cvx_genome_decode(cvx_handle h, cvx_genome g, int32_t n, const uint64_t *pos
 		win[(size_t) i].n_chars = (int64_t) length[i] - 1;           /* the reference's last byte is the NUL */
 		total += (uint64_t) length[i];
 	}
+	static const char who[] = "cvx_genome_decode";
+	std::vector<uint8_t> host((size_t) total);      /* (in front of the device buffers: they wait for the device as they go, and then nothing copies into it any more) */
 	DevBuf<uint8_t> d_out;
 	DevBuf<WindowDesc> d_win;
+	Event k0, k1;                    /* the kernel alone, on its own stream */
 	RC_TRY(d_out.ensure((size_t) total + 64));
-	int rc = d_win.ensure((size_t) n);
-	if (rc != CVX_OK) { d_out.release(); return rc; }
-	std::vector<uint8_t> host((size_t) total);
+	RC_TRY(d_win.ensure((size_t) n));
 	hipStream_t st = h->s_main;
-	hipError_t e = hipMemsetAsync(d_out.p, 0, (size_t) total, st);   /* the NUL that ends every window */
-	if (e == hipSuccess) e = hipMemcpyAsync(d_win.p, win.data(), (size_t) n * sizeof(WindowDesc), hipMemcpyHostToDevice, st);
-	hipEvent_t k0 = nullptr, k1 = nullptr;      /* the kernel alone, on its own stream */
-	if (e == hipSuccess) e = hipEventCreate(&k0);
-	if (e == hipSuccess) e = hipEventCreate(&k1);
-	if (e == hipSuccess) e = hipEventRecord(k0, st);
-	if (e == hipSuccess) e = launch_decode_windows(g->d_bin.p, g->d_starts.p, g->n_starts, d_win.p, n, d_out.p, st);
-	if (e == hipSuccess) e = hipEventRecord(k1, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out.p, (size_t) total, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e == hipSuccess) h->decode_kernel_ms = ev_ms(k0, k1);
-	if (k0) (void) hipEventDestroy(k0);
-	if (k1) (void) hipEventDestroy(k1);
-	d_out.release();
-	d_win.release();
-	if (e != hipSuccess) { set_err("cvx_genome_decode: %s", hipGetErrorString(e)); return CVX_ERR_HIP; }
+	HIP_TRY_IN(who, hipMemsetAsync(d_out.p, 0, (size_t) total, st));   /* the NUL that ends every window */
+	HIP_TRY_IN(who, hipMemcpyAsync(d_win.p, win.data(), (size_t) n * sizeof(WindowDesc), hipMemcpyHostToDevice, st));
+	HIP_TRY_IN(who, k0.make());
+	HIP_TRY_IN(who, k1.make());
+	HIP_TRY_IN(who, hipEventRecord(k0, st));
+	HIP_TRY_IN(who, launch_decode_windows(g->d_bin.p, g->d_starts.p, g->n_starts, d_win.p, n, d_out.p, st));
+	HIP_TRY_IN(who, hipEventRecord(k1, st));
+	HIP_TRY_IN(who, hipMemcpyAsync(host.data(), d_out.p, (size_t) total, hipMemcpyDeviceToHost, st));
+	HIP_TRY_IN(who, hipStreamSynchronize(st));
+	h->decode_kernel_ms = ev_ms(k0, k1);
 	for (int i = 0; i < n; ++i) memcpy(out + out_offset[i], host.data() + win[(size_t) i].dst_off, (size_t) length[i]);
 	return CVX_OK;
 	ABI_GUARD_END
@@ -250,22 +223,14 @@ int cvx_index_upload(cvx_handle h, int32_t k, const void *index, const uint32_t 
 		}
 		rows[(size_t) i] = make_uint2(used ? t0 - 1u : 0u, used ? ((t1 - t0) | 0x80000000u) : 0u);
 	}
-	cvx_index_s *ix = new (std::nothrow) cvx_index_s();
+	std::unique_ptr<cvx_index_s> ix(new (std::nothrow) cvx_index_s());
 	if (!ix) return CVX_ERR_OOM;
 	ix->device = h->device; ix->k = k; ix->n_index = n_index; ix->unit_offset = unit_offset; ix->n_locs = n_locs;
-	int rc = ix->d_rows.ensure(rows.size());
-	if (rc == CVX_OK) rc = ix->d_locs.ensure((size_t) n_locs + 1);
-	hipError_t e = hipSuccess;
-	if (rc == CVX_OK) {
-		e = hipMemcpy(ix->d_rows.p, rows.data(), rows.size() * sizeof(uint2), hipMemcpyHostToDevice);
-		if (e == hipSuccess && n_locs) e = hipMemcpy(ix->d_locs.p, locs, (size_t) n_locs * 4, hipMemcpyHostToDevice);
-	}
-	if (rc != CVX_OK || e != hipSuccess) {
-		if (e != hipSuccess) { set_err("cvx_index_upload: %s", hipGetErrorString(e)); rc = CVX_ERR_HIP; }
-		ix->d_rows.release(); ix->d_locs.release(); delete ix;
-		return rc;
-	}
-	*out = ix;
+	RC_TRY(ix->d_rows.ensure(rows.size()));
+	RC_TRY(ix->d_locs.ensure((size_t) n_locs + 1));
+	HIP_TRY_IN("cvx_index_upload", hipMemcpy(ix->d_rows.p, rows.data(), rows.size() * sizeof(uint2), hipMemcpyHostToDevice));
+	if (n_locs) HIP_TRY_IN("cvx_index_upload", hipMemcpy(ix->d_locs.p, locs, (size_t) n_locs * 4, hipMemcpyHostToDevice));
+	*out = ix.release();      /* (the unique_ptr's: the caller owns the table from here) */
 	return CVX_OK;
 	ABI_GUARD_END
 }
@@ -312,7 +277,6 @@ void cvx_index_free(cvx_handle h, cvx_index ix) {
 	ABI_GUARD_BEGIN
 	if (!ix) return;
 	if (h) { (void) hipSetDevice(h->device); (void) hipDeviceSynchronize(); }
-	ix->d_rows.release(); ix->d_locs.release();
 	delete ix;
 	ABI_GUARD_END_VOID
 }
@@ -475,13 +439,9 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 		if (ss->d_cand.cap < (size_t) (fixed_total + 2 * total) + 64) {
 			DevBuf<SearchCandidate> bigger;
 			RC_TRY(bigger.ensure((size_t) (fixed_total + 2 * total) + (size_t) total / 2 + 64));
-			hipError_t e = hipMemcpyAsync(bigger.p, ss->d_cand.p, ss->d_cand.cap * sizeof(SearchCandidate), hipMemcpyDeviceToDevice, st);
-			int rc = CVX_OK;
-			if (e != hipSuccess) { set_err("cvx_search_batch: %s", hipGetErrorString(e)); rc = CVX_ERR_HIP; }
-			if (rc == CVX_OK) rc = search_wait(ss, st);
-			if (rc != CVX_OK) { bigger.release(); return rc; }      /* (this buffer leaked on the error paths) */
-			ss->d_cand.release();
-			ss->d_cand = bigger;
+			HIP_TRY_IN("cvx_search_batch", hipMemcpyAsync(bigger.p, ss->d_cand.p, ss->d_cand.cap * sizeof(SearchCandidate), hipMemcpyDeviceToDevice, st));
+			RC_TRY(search_wait(ss, st));
+			ss->d_cand = std::move(bigger);      /* (frees the old arena: the copy out of it is done) */
 		}
 		HIP_TRY(hipMemcpyAsync(ss->d_listoff.p, h_listoff, n1 * 8, hipMemcpyHostToDevice, st));
 		return CVX_OK;
@@ -626,7 +586,8 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 			RC_TRY(ss->d_fout.ensure((size_t) need)); RC_TRY(ss->d_fstatus.ensure((size_t) need));
 			RC_TRY(ss->d_fseq.ensure((size_t) slots.seq_bytes + 256));
 			RC_TRY(ss->h_fout.ensure((size_t) need * 8));
-			if (!ss->ev_f0) { HIP_TRY(hipEventCreate(&ss->ev_f0)); HIP_TRY(hipEventCreate(&ss->ev_f1)); }
+			HIP_TRY(ss->ev_f0.make());
+			HIP_TRY(ss->ev_f1.make());
 			HIP_TRY(hipEventRecord(ss->ev_f0, st));
 			HIP_TRY(launch_plan_candidate_windows(ss->d_dense.p, ss->d_begin.p, ss->d_ncand.p, ss->d_off.p, ss->d_len.p, n, need,
 					score_windows_concat_len(fs->g->n_nibbles), fs->buffer_len, fs->window_lead, fs->max_cmrs, slots, ss->d_fdesc.p, ss->d_fstatus.p, st));

@@ -154,8 +154,8 @@ static int nm_profile_common(cvx_handle h, cvx_job j, int32_t first, int32_t cou
 	const size_t c1 = (size_t) count;
 	RC_TRY(j->d_nmoff.ensure(2 * c1 + 8));
 	RC_TRY(j->h_nmoff.ensure((c1 + 1) * sizeof(unsigned long long)));
-	if (!j->ev_nm0) HIP_TRY(hipEventCreate(&j->ev_nm0));
-	if (!j->ev_nm1) HIP_TRY(hipEventCreate(&j->ev_nm1));
+	HIP_TRY(j->ev_nm0.make());
+	HIP_TRY(j->ev_nm1.make());
 	TextArgs a;
 	memset(&a, 0, sizeof(a));
 	a.seq = j->d_seq.p; a.tin = j->d_tin.p; a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
@@ -253,29 +253,23 @@ int cvx_nm_profile_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 	DevBuf<TileOut> d_tout;
 	DevBuf<TileRun> d_trun;
 	DevBuf<unsigned long long> d_off;
-	int rc = CVX_OK;
-	auto body = [&]() -> int {
-		RC_TRY(d_ops.ensure((size_t) ops_total + 16));
-		RC_TRY(d_tri.ensure(3 * (size_t) total + 16));
-		RC_TRY(d_tout.ensure(n1));
-		RC_TRY(d_trun.ensure(n1));
-		RC_TRY(d_off.ensure(n1 + 1));
-		hipStream_t st = h->s_text;
-		if (ops_total) HIP_TRY(hipMemcpyAsync(d_ops.p, ops_arena, (size_t) ops_total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_tout.p, tout.data(), n1 * sizeof(TileOut), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_trun.p, trun.data(), n1 * sizeof(TileRun), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), (n1 + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-		TextArgs a;
-		memset(&a, 0, sizeof(a));
-		a.tout = d_tout.p; a.trun = d_trun.p; a.ops = d_ops.p; a.n_tiles = n;
-		HIP_TRY(launch_nm_profile(a, 0, n, d_off.p, d_tri.p, st));
-		if (total) HIP_TRY(hipMemcpyAsync(triples, d_tri.p, 3 * (size_t) total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return CVX_OK;
-	};
-	rc = body();
-	d_ops.release(); d_tri.release(); d_tout.release(); d_trun.release(); d_off.release();
-	return rc;
+	RC_TRY(d_ops.ensure((size_t) ops_total + 16));
+	RC_TRY(d_tri.ensure(3 * (size_t) total + 16));
+	RC_TRY(d_tout.ensure(n1));
+	RC_TRY(d_trun.ensure(n1));
+	RC_TRY(d_off.ensure(n1 + 1));
+	hipStream_t st = h->s_text;
+	if (ops_total) HIP_TRY(hipMemcpyAsync(d_ops.p, ops_arena, (size_t) ops_total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_tout.p, tout.data(), n1 * sizeof(TileOut), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_trun.p, trun.data(), n1 * sizeof(TileRun), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), (n1 + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.tout = d_tout.p; a.trun = d_trun.p; a.ops = d_ops.p; a.n_tiles = n;
+	HIP_TRY(launch_nm_profile(a, 0, n, d_off.p, d_tri.p, st));
+	if (total) HIP_TRY(hipMemcpyAsync(triples, d_tri.p, 3 * (size_t) total * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return CVX_OK;
 	ABI_GUARD_END
 }
 
@@ -300,8 +294,8 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 	RC_TRY(j->d_nmstage.ensure(c1 * (size_t) kNmStage));
 	RC_TRY(j->h_nmroff.ensure((c1 + 1) * sizeof(unsigned long long)));
 	if (open) RC_TRY(j->h_nmopen.ensure(c1 * sizeof(NmOpen)));
-	if (!j->ev_nm0) HIP_TRY(hipEventCreate(&j->ev_nm0));
-	if (!j->ev_nm1) HIP_TRY(hipEventCreate(&j->ev_nm1));
+	HIP_TRY(j->ev_nm0.make());
+	HIP_TRY(j->ev_nm1.make());
 	TextArgs a;
 	memset(&a, 0, sizeof(a));
 	a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
@@ -428,46 +422,41 @@ int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 			if (type != CVX_OP_EQ && type != CVX_OP_X && type != CVX_OP_D && type != CVX_OP_I) { set_err("cvx_nm_regions_ops: op code %d in tile %zu", type, i); return CVX_ERR_ARG; }
 		}
 	}
+	std::vector<unsigned long long> off(n1 + 1, 0ull);      /* (in front of the device buffers: they wait for the device as they go, and then nothing copies into it any more) */
 	DevBuf<int32_t> d_ops;
 	DevBuf<TileOut> d_tout;
 	DevBuf<TileRun> d_trun;
 	DevBuf<unsigned long long> d_off;
 	DevBuf<NmOpen> d_open;
 	DevBuf<NmRegion> d_stage, d_reg;
-	std::vector<unsigned long long> off(n1 + 1, 0ull);
-	auto body = [&]() -> int {
-		RC_TRY(d_ops.ensure((size_t) ops_total + 16));
-		RC_TRY(d_tout.ensure(n1));
-		RC_TRY(d_trun.ensure(n1));
-		RC_TRY(d_off.ensure(2 * n1 + 8));
-		RC_TRY(d_open.ensure(n1));
-		RC_TRY(d_stage.ensure(n1 * (size_t) kNmStage));
-		hipStream_t st = h->s_text;
-		if (ops_total) HIP_TRY(hipMemcpyAsync(d_ops.p, ops_arena, (size_t) ops_total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_tout.p, tout.data(), n1 * sizeof(TileOut), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(d_trun.p, trun.data(), n1 * sizeof(TileRun), hipMemcpyHostToDevice, st));
-		TextArgs a;
-		memset(&a, 0, sizeof(a));
-		a.tout = d_tout.p; a.trun = d_trun.p; a.ops = d_ops.p; a.n_tiles = n;
-		unsigned long long *d_len = d_off.p, *d_o = d_off.p + n1;
-		HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_o, d_o + n1, d_open.p, d_stage.p, st));
-		HIP_TRY(hipMemcpyAsync(off.data(), d_o, (n1 + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		if (open) HIP_TRY(hipMemcpyAsync(open, d_open.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		for (size_t i = 0; i <= n1; ++i) region_off[i] = off[i];
-		const unsigned long long total = off[n1];
-		if (!regions) return CVX_OK;                      /* sizes only */
-		if (total > cap_regions) { set_err("cvx_nm_regions_ops: %llu regions, room for %llu", total, (unsigned long long) cap_regions); return CVX_ERR_CAPACITY; }
-		if (total == 0) return CVX_OK;
-		RC_TRY(d_reg.ensure((size_t) total + 4));
-		HIP_TRY(launch_nm_regions_write(a, 0, n, d_len, d_o, d_stage.p, d_reg.p, st));
-		HIP_TRY(hipMemcpyAsync(regions, d_reg.p, (size_t) total * sizeof(NmRegion), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		return CVX_OK;
-	};
-	const int rc = body();
-	d_ops.release(); d_tout.release(); d_trun.release(); d_off.release(); d_open.release(); d_stage.release(); d_reg.release();
-	return rc;
+	RC_TRY(d_ops.ensure((size_t) ops_total + 16));
+	RC_TRY(d_tout.ensure(n1));
+	RC_TRY(d_trun.ensure(n1));
+	RC_TRY(d_off.ensure(2 * n1 + 8));
+	RC_TRY(d_open.ensure(n1));
+	RC_TRY(d_stage.ensure(n1 * (size_t) kNmStage));
+	hipStream_t st = h->s_text;
+	if (ops_total) HIP_TRY(hipMemcpyAsync(d_ops.p, ops_arena, (size_t) ops_total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_tout.p, tout.data(), n1 * sizeof(TileOut), hipMemcpyHostToDevice, st));
+	HIP_TRY(hipMemcpyAsync(d_trun.p, trun.data(), n1 * sizeof(TileRun), hipMemcpyHostToDevice, st));
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.tout = d_tout.p; a.trun = d_trun.p; a.ops = d_ops.p; a.n_tiles = n;
+	unsigned long long *d_len = d_off.p, *d_o = d_off.p + n1;
+	HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_o, d_o + n1, d_open.p, d_stage.p, st));
+	HIP_TRY(hipMemcpyAsync(off.data(), d_o, (n1 + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	if (open) HIP_TRY(hipMemcpyAsync(open, d_open.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	for (size_t i = 0; i <= n1; ++i) region_off[i] = off[i];
+	const unsigned long long total = off[n1];
+	if (!regions) return CVX_OK;                      /* sizes only */
+	if (total > cap_regions) { set_err("cvx_nm_regions_ops: %llu regions, room for %llu", total, (unsigned long long) cap_regions); return CVX_ERR_CAPACITY; }
+	if (total == 0) return CVX_OK;
+	RC_TRY(d_reg.ensure((size_t) total + 4));
+	HIP_TRY(launch_nm_regions_write(a, 0, n, d_len, d_o, d_stage.p, d_reg.p, st));
+	HIP_TRY(hipMemcpyAsync(regions, d_reg.p, (size_t) total * sizeof(NmRegion), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	return CVX_OK;
 	ABI_GUARD_END
 }
 

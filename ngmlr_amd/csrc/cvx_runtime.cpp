@@ -417,11 +417,11 @@ void cvx_destroy(cvx_handle h) {
 	if (h->s_post2) (void) hipStreamDestroy(h->s_post2);
 	for (auto &a : h->aux2) if (a) (void) hipStreamDestroy(a);
 	if (h->s_tail) (void) hipStreamDestroy(h->s_tail);
-	for (cvx_batch_s *b : h->pool) { b->release(); delete b; }
+	for (cvx_batch_s *b : h->pool) delete b;
 	h->pool.clear();
 	/* jobs the caller never released (submitted, maybe waited for): the device is idle, free them too --
 	 * their handles are dead from here on, like everything else that belonged to this context */
-	for (cvx_batch_s *b : h->live) { b->release(); delete b; }
+	for (cvx_batch_s *b : h->live) delete b;
 	h->live.clear();
 	h->pending.clear();
 	h->climbing.clear();
