@@ -504,7 +504,23 @@ int cvx_stage_segments_host(int32_t n_reads, const uint8_t *arena, const uint64_
  *                     result block and ops on the host, and cvx_wait merges them there.  The text and profile calls for finished
  *                     jobs (cvx_job_text*, cvx_job_nm_*) refuse a ladder job.
  *                     Default and CVX_CREATE_SCALAR_TWIN handles; a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS
- *                     or _SERVICE refuses the call with CVX_ERR_ARG (running those stages behind the final rung is a follow-up).
+ *                     or _SERVICE refuses the call with CVX_ERR_ARG: cvx_submit_ladder_ex is the form for the first three.
+ *   cvx_submit_ladder_ex  the same job on any handle but a CVX_CREATE_SERVICE one (CVX_ERR_ARG), with the queries as strings
+ *                     (qry NULL, and then n_reads 0, arena NULL, offsets NULL: anything else is CVX_ERR_ARG) or as segments
+ *                     of a read block by cvx_submit_segments' rules, with or without g.  The segments are written once, into
+ *                     rung 1's sequence arena; every later rung reads them there (seq_bytes_after_submit stays 0).
+ *                     On a handle with CVX_CREATE_NM_REGIONS / _INV_CHECKS / _JOB_TEXT every rung runs those stages behind its
+ *                     own compaction -- a later rung reads rung 1's sequences, and ladder_next_kernel gathers the climbing
+ *                     tiles' window descriptors for its checks -- and cvx_wait merges them on the host beside the ops: after it,
+ *                     cvx_job_regions / _regions_info, cvx_job_checks and cvx_job_texts / _texts_info answer as for any job,
+ *                     without a device call, valid until cvx_job_release, in the ordinary layout and in tile order.  Per tile
+ *                     all of it belongs to the rung cvx_job_ladder reports, byte for byte what an ordinary job on a handle with
+ *                     the same flags returns for that tile submitted with cvx_ladder_rung's form of that rung; a tile whose last
+ *                     attempt failed has no regions, and the end state and text record the ordinary job gives such a tile.
+ *                     cvx_job_checks gives NULL without a genome or without a region.  The _info calls: the merged total, the
+ *                     rewrites summed over the rungs, rung 1's first capacity.  The genome has to outlive cvx_wait for a job
+ *                     with checks.  The decision kernel and the next rung's plan are queued in front of the finished rung's
+ *                     stages: the climb reads result statuses only.
  *   cvx_job_ladder    after cvx_wait, valid until cvx_job_release: per tile the rung reported (1-based), the attempts made and
  *                     that rung's corridor width.
  *   cvx_job_ladder_info  after cvx_wait: rungs the job ran, tiles[r] = tiles that took part in rung r + 1, and the sequence
@@ -520,6 +536,10 @@ typedef struct { int32_t rungs_run; int32_t tiles[5]; uint64_t seq_bytes_after_s
 int cvx_ladder_rung(const cvx_tile *tile, const cvx_ladder *l, int32_t m, cvx_tile *form);
 int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n_tiles, const cvx_tile *tiles,
 		const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out);
+int cvx_submit_ladder_ex(cvx_handle h, cvx_genome g, int32_t n_tiles, const cvx_tile *tiles,
+		const uint64_t *ref_position, const cvx_ladder *ladders,
+		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, const cvx_read_segment *qry,
+		cvx_job *out);
 int cvx_job_ladder(cvx_handle h, cvx_job job, const cvx_ladder_result **out);
 int cvx_job_ladder_info(cvx_job job, cvx_ladder_info *out);
 

@@ -181,6 +181,31 @@ class ConvexAlignHip:
                                               pos.ctypes.data if pos is not None else None, lad.ctypes.data, C.byref(j)))
         return Job(self, j, len(tiles), (keep, lad, pos))
 
+    def submit_ladder_ex(self, tiles: Sequence, ladders, genome: "Genome" = None, ref_positions=None, reads=None, segments=None) -> "Job":
+        """cvx_submit_ladder_ex: submit_ladder on any handle but a service one -- on a ConvexAlignHip(nm_regions / inv_checks /
+        job_text) handle Job.regions(), .checks(), .texts() and .texts_raw() answer for the ladder job as for any job, per tile
+        from the rung Job.ladder() reports.  reads / segments (both or neither): the queries as segments of a read block, as
+        submit_segments takes them; of tile.qry only the length is used then."""
+        assert (reads is None) == (segments is None), "reads and segments come together"
+        arr, keep = self._pack(tiles, closed_form=True)
+        lad = _ladders(ladders)
+        assert len(lad) == len(tiles), "one ladder per tile"
+        pos = np.ascontiguousarray(ref_positions, dtype=np.uint64) if genome is not None else None
+        arena = offsets = seg = None
+        n_reads = 0
+        if segments is not None:
+            for i in range(len(tiles)):
+                arr[i].qry = None
+            arena, offsets, n_reads = _window_reads(reads)
+            seg = _segments(segments)
+            assert len(seg) == len(tiles), "one segment per tile"
+        j = C.c_void_p()
+        capi.check(self.lib.cvx_submit_ladder_ex(self.h, genome.g if genome is not None else None, len(tiles), arr,
+                                                 pos.ctypes.data if pos is not None else None, lad.ctypes.data, n_reads,
+                                                 arena.ctypes.data if arena is not None else None, offsets.ctypes.data if offsets is not None else None,
+                                                 seg.ctypes.data if seg is not None else None, C.byref(j)))
+        return Job(self, j, len(tiles), (keep, lad, pos, arena, offsets, seg))
+
     def stage_segments(self, reads, segments, lengths) -> List[bytes]:
         """cvx_stage_segments: the strings stage_segments_kernel builds for (read, start, flags) + length, back on the host."""
         arena, offsets, n_reads = _window_reads(reads)

@@ -42,7 +42,7 @@ EXPORTS = ("cvx_last_error", "cvx_abi_version", "cvx_source_id", "cvx_device_cou
            "cvx_search_score_arena", "cvx_submit_segments", "cvx_stage_segments", "cvx_stage_segments_host", "cvx_job_zero_copy_bytes",
            "cvx_handle_pen_table", "cvx_job_regions", "cvx_job_regions_info", "cvx_job_texts", "cvx_job_texts_info", "cvx_text_reclip",
            "cvx_job_checks", "cvx_inv_checks", "cvx_inv_checks_host",
-           "cvx_ladder_rung", "cvx_submit_ladder", "cvx_job_ladder", "cvx_job_ladder_info")
+           "cvx_ladder_rung", "cvx_submit_ladder", "cvx_submit_ladder_ex", "cvx_job_ladder", "cvx_job_ladder_info")
 
 
 class CvxParams(C.Structure):
@@ -304,6 +304,8 @@ def load(path: str = None) -> C.CDLL:
     lib.cvx_job_zero_copy_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     lib.cvx_ladder_rung.argtypes = [C.POINTER(CvxTile), C.POINTER(CvxLadder), C.c_int32, C.POINTER(CvxTile)]
     lib.cvx_submit_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CvxTile), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.cvx_submit_ladder_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CvxTile), C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.cvx_job_ladder.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
     lib.cvx_job_ladder_info.argtypes = [C.c_void_p, C.POINTER(CvxLadderInfo)]
     lib.cvx_genome_concat_len.argtypes = [C.c_uint64, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]

@@ -256,12 +256,9 @@ int ConvexAlignHip::SingleAlign(int const mode, CorridorLine * corridor, int con
 	return t.ret;
 }
 
-void ConvexAlignHip::Prepare(Tile & t, bool const scalarTwin) {
-	Align & a = *t.result;
-	if (!scalarTwin) a.svType = 0;      /* ConvexAlignFast reads it as a debug id, then clears it; the scalar twin only reads it */
-	a.Score = -1.0f;
-	t.ret = -1;
-	t.failed = false;
+/* what the two strings of a request stand for: themselves, or -- a binding's placeholders -- a window of the resident genome and a
+ * segment of a read; refLen / qryLen either way */
+void ConvexAlignHip::resolveSequences(Tile & t) {
 	t.window = false;
 	t.refPosition = 0;
 	int windowLength = 0;
@@ -281,6 +278,15 @@ void ConvexAlignHip::Prepare(Tile & t, bool const scalarTwin) {
 	} else {
 		t.qryLen = (int) strlen(t.qrySeq);
 	}
+}
+
+void ConvexAlignHip::Prepare(Tile & t, bool const scalarTwin) {
+	Align & a = *t.result;
+	if (!scalarTwin) a.svType = 0;      /* ConvexAlignFast reads it as a debug id, then clears it; the scalar twin only reads it */
+	a.Score = -1.0f;
+	t.ret = -1;
+	t.failed = false;
+	resolveSequences(t);
 	if (t.corridorHeight != t.qryLen) {
 		/* every reference caller passes corridorHeight == strlen(qry); anything else
 		 * indexes the corridor out of bounds in the reference itself */
@@ -331,6 +337,13 @@ cvx_job ConvexAlignHip::Submit(Tile const * tiles, int n) {
 		c.corridor_offset = t.corridorOffset; c.corridor_width = t.corridorWidth;
 		c.reserved = 0;
 	}
+	return submitPacked(tiles, n, 0);
+}
+
+/* packed[0 .. n) hold the tiles' strings, lengths and corridors: the launch in the form its sequences allow -- every reference a
+ * window of the resident genome, every query a segment of a read, or characters -- as an ordinary job, or (ladders given) as a
+ * ladder job whose tiles carry ladders[i] in place of packed[i]'s corridor */
+cvx_job ConvexAlignHip::submitPacked(Tile const * tiles, int n, cvx_ladder const * ladders) {
 	int nWindows = 0, nSegments = 0;
 	for (int i = 0; i < n; ++i) { nWindows += tiles[i].window ? 1 : 0; nSegments += tiles[i].segment ? 1 : 0; }
 	cvx_job job = 0;
@@ -372,14 +385,20 @@ cvx_job ConvexAlignHip::Submit(Tile const * tiles, int n) {
 		 * straight into the launch's sequence arena (the reference: src/AlignmentBuffer.cpp:199-223 on the worker's core) */
 		positions.resize((size_t) n);
 		for (int i = 0; i < n; ++i) { positions[(size_t) i] = tiles[i].refPosition; packed[(size_t) i].ref = 0; }
-		if (noted) rc = cvx_submit_segments(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), (int32_t) readOffsets.size() - 1,
+		if (ladders) rc = cvx_submit_ladder_ex(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), ladders, noted ? (int32_t) readOffsets.size() - 1 : 0,
+				noted ? readArena.data() : 0, noted ? readOffsets.data() : 0, noted ? segments.data() : 0, &job);
+		else if (noted) rc = cvx_submit_segments(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), (int32_t) readOffsets.size() - 1,
 				readArena.data(), readOffsets.data(), segments.data(), &job);
 		else rc = cvx_submit_windows(handle, genome, n, packed.data(), (uint64_t const *) positions.data(), &job);
 		g_windowLaunches.fetch_add(1, std::memory_order_relaxed);
 		g_windowTiles.fetch_add(n, std::memory_order_relaxed);
 	} else {
 		if (nWindows > 0) materialiseWindows(tiles, n);      /* a launch that mixes both forms (no ngmlr path builds one) */
-		if (noted) rc = cvx_submit_segments(handle, 0, n, packed.data(), 0, (int32_t) readOffsets.size() - 1, readArena.data(), readOffsets.data(), segments.data(), &job);
+		/* (a plain aligner's ladders of plain strings go where they always went) */
+		if (ladders && !noted && !regions && !jobText) rc = cvx_submit_ladder(handle, 0, n, packed.data(), 0, ladders, &job);
+		else if (ladders) rc = cvx_submit_ladder_ex(handle, 0, n, packed.data(), 0, ladders, noted ? (int32_t) readOffsets.size() - 1 : 0,
+				noted ? readArena.data() : 0, noted ? readOffsets.data() : 0, noted ? segments.data() : 0, &job);
+		else if (noted) rc = cvx_submit_segments(handle, 0, n, packed.data(), 0, (int32_t) readOffsets.size() - 1, readArena.data(), readOffsets.data(), segments.data(), &job);
 		else rc = cvx_submit(handle, n, packed.data(), &job);
 	}
 	if (rc != CVX_OK) {
@@ -537,42 +556,51 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 
 void ConvexAlignHip::AlignLadders(LadderTile * tiles, int n) {
 	if (n <= 0) return;
-	std::vector<cvx_tile> ct((size_t) n);
+	/* the requests as Tiles without a corridor: the strings resolved the way Prepare resolves them (windows and read placeholders
+	 * of a binding included), so that the launch takes Submit's forms and the tiles finish the way AlignTiles finishes them */
+	std::vector<Tile> ts((size_t) n);
 	std::vector<cvx_ladder> lad((size_t) n);
+	packed.resize((size_t) n);
 	for (int i = 0; i < n; ++i) {
-		cvx_tile & c = ct[(size_t) i];
+		Tile & t = ts[(size_t) i];
+		memset(&t, 0, sizeof(t));
+		t.refSeq = tiles[i].refSeq; t.qrySeq = tiles[i].qrySeq; t.result = tiles[i].result;
+		t.externalQStart = tiles[i].externalQStart; t.externalQEnd = tiles[i].externalQEnd;
+		t.ret = -1;
+		resolveSequences(t);
+		t.corridorHeight = t.qryLen;
+		cvx_tile & c = packed[(size_t) i];
 		memset(&c, 0, sizeof(c));
-		c.ref = tiles[i].refSeq; c.qry = tiles[i].qrySeq;
-		c.ref_len = (int32_t) strlen(tiles[i].refSeq); c.qry_len = (int32_t) strlen(tiles[i].qrySeq);
+		c.ref = t.refSeq; c.qry = t.qrySeq;
+		c.ref_len = t.refLen; c.qry_len = t.qryLen;
 		c.row_stride_bytes = 4;
 		lad[(size_t) i] = tiles[i].ladder;
 		tiles[i].ret = -1; tiles[i].failed = false; tiles[i].rung = tiles[i].attempts = tiles[i].width = 0;
 	}
-	cvx_job job = 0;
-	if (cvx_submit_ladder(handle, 0, n, ct.data(), 0, lad.data(), &job) != CVX_OK) {
-		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
-		throw 1;
-	}
+	cvx_job job = submitPacked(ts.data(), n, lad.data());
 	cvx_result const * res = 0;
 	uint32_t const * ops = 0;
 	cvx_ladder_result const * lr = 0;
+	std::vector<Tile *> ptrs((size_t) n);
+	for (int i = 0; i < n; ++i) ptrs[(size_t) i] = &ts[(size_t) i];
+	JobRegions jr;
+	JobTextView jx;
+	bool haveRegions = false, haveTexts = false;
 	try {
 		Wait(job, &res, &ops);
 		if (cvx_job_ladder(handle, job, &lr) != CVX_OK) { fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error()); throw 1; }
+		(void) WindowRefs(job, ptrs.data(), n);      /* windows decoded on the device: the host text stage reads what came back */
+		haveRegions = Regions(job, jr);
+		haveTexts = JobTexts(job, jx);
 	} catch (...) {
 		Release(job);
 		throw;
 	}
 	for (int i = 0; i < n; ++i) {
-		Tile t;
-		memset(&t, 0, sizeof(t));
-		t.refSeq = tiles[i].refSeq; t.qrySeq = tiles[i].qrySeq; t.result = tiles[i].result;
-		t.externalQStart = tiles[i].externalQStart; t.externalQEnd = tiles[i].externalQEnd;
-		t.refLen = ct[(size_t) i].ref_len; t.qryLen = ct[(size_t) i].qry_len; t.corridorHeight = t.qryLen;
-		t.ret = -1;
+		Tile & t = ts[(size_t) i];
 		tiles[i].rung = lr[i].rung; tiles[i].attempts = lr[i].attempts; tiles[i].width = lr[i].width;
 		try {
-			Finish(t, res[i], ops);
+			Finish(t, res[i], ops, haveRegions ? &jr : 0, i, haveTexts ? &jx : 0);
 			tiles[i].ret = t.ret;
 		} catch (...) {
 			tiles[i].failed = true;

@@ -109,9 +109,14 @@ public:
 		bool failed;           /* out: this tile hit a hard error */
 		int rung, attempts, width;      /* out: the rung reported (1-based), the attempts made, that rung's corridor width */
 	};
-	/* n retry ladders in one device job (cvx_submit_ladder): every tile's corridor is rebuilt at multiplier 2, 3, ... and aligned
-	 * again on the device while its attempt is invalid and a further rung exists; `result` is filled the way SingleAlign fills it
-	 * for the rung reported.  Hard errors as for AlignTiles; a handle created with nmRegions or jobText refuses (throws 1). */
+	/* n retry ladders in one device job (cvx_submit_ladder; cvx_submit_ladder_ex on an aligner constructed with nmRegions and / or
+	 * jobText, and for the placeholder forms below): every tile's corridor is rebuilt at multiplier 2, 3, ... and aligned again on
+	 * the device while its attempt is invalid and a further rung exists; `result` is filled the way SingleAlign fills it for the
+	 * rung reported -- on an aligner with nmRegions a request in Align::nmPerPosition is answered with a note of that rung's
+	 * regions, with jobText such a tile takes its CIGAR and MD from the job's text (FinishJobText + cvx_text_reclip), every other
+	 * tile the host form, exactly as AlignTiles finishes them.  The input forms are Submit's: every refSeq a DeviceWindows
+	 * placeholder -- the genome form; every qrySeq a DeviceReads placeholder -- the segments form, distinct reads sent once; a
+	 * mix is materialised on the host.  Hard errors as for AlignTiles. */
 	void AlignLadders(LadderTile * tiles, int n);
 
 	/* The same in stages, for a driver that keeps launches in flight.  Prepare / Finish may run on any thread (they
@@ -184,6 +189,8 @@ public:
 	void FinishText(Tile & t, cvx_result const & r, JobText const & jt, int index) const;
 
 private:
+	static void resolveSequences(Tile & t);      /* Prepare's first half: placeholders recognised, refLen / qryLen */
+	cvx_job submitPacked(Tile const * tiles, int n, cvx_ladder const * ladders);      /* Submit's second half, shared with AlignLadders */
 	void fillAlign(Tile & t, cvx_alignment_text const & txt) const;
 	bool noAlignment(Tile & t, cvx_result const & r) const;
 	cvx_handle handle;

@@ -20,11 +20,13 @@ struct LadderNextArgs {
 	const cvx_ladder *lad;     /* by job tile */
 	int32_t n_prev;
 	int32_t m;                 /* the rung that has finished (1-based); the records written are rung m + 1's */
+	const WindowDesc *win0;    /* rung 1's window descriptors, by job tile; NULL: the job's rungs run no inversion checks */
 	/* out, each with room for n_prev entries: the climbing tiles in the finished rung's order, then empty tiles (H = W = 0)
 	 * up to n_prev, so that a plan launch over all n_prev entries reads defined records */
 	RowSrc *rsrc;
 	TileIn *tin;
 	int32_t *head;             /* head[0] = tiles that climb, head[1 + j] = job tile of entry j (j < head[0]) */
+	WindowDesc *win;           /* with win0: the window descriptor of entry j's job tile (zeros behind the climbing tiles) */
 };
 hipError_t launch_ladder_next(const LadderNextArgs &a, hipStream_t st);
 

@@ -4,6 +4,8 @@
  * rule (cvx_ladder_logic.h: the retry loop of AlignmentBuffer::computeAlignment, reference src/AlignmentBuffer.cpp:259-425)
  * and writes the next rung's corridor and tile records, compacted in the finished rung's order, with the list of the job
  * tiles they belong to and their count.  A climbing tile keeps the sequence offsets of rung 1: nothing of its sequences moves.
+ * A job submitted with a genome on a handle that scores inversion checks also gets every climbing tile's window descriptor
+ * gathered beside its tile record (inv_checks_kernel indexes them by the rung's own tile index); no window is decoded again.
  *
  * One workgroup for the whole rung: the list is an ordered compaction of a few thousand 4-byte decisions, a block scan per
  * 256 tiles, microseconds beside the fills on either side of it.  The kernel neither waits nor polls: the rung it reads is
@@ -56,6 +58,7 @@ ladder_next_kernel(const LadderNextArgs a) {
 			ti.reserved = 0;
 			a.tin[at] = ti;
 			a.head[1 + at] = tile;
+			if (a.win0) a.win[at] = a.win0[tile];      /* the tile's window descriptor, for the rung's inversion checks */
 		}
 		__syncthreads();
 		if (tid == kLadderBlock - 1) s_base = base + s_scan[tid];
@@ -72,6 +75,11 @@ ladder_next_kernel(const LadderNextArgs a) {
 		a.rsrc[at] = f;
 		a.tin[at] = ti;
 		a.head[1 + at] = -1;
+		if (a.win0) {
+			WindowDesc w;
+			w.position = 0; w.dst_off = 0; w.n_chars = 0;
+			a.win[at] = w;
+		}
 	}
 }
 

@@ -250,6 +250,7 @@ struct cvx_batch_s {
 	Event ev_bt0, ev_bt1;   /* fork / join of the long-read backtrack launch */
 	Event ev_in;      /* upload + plan records on the host */
 	Event ev_res;     /* result records on the host */
+	Event ev_rec;     /* result records final on the device, dense ops compacted: in front of the job's regions / checks / text stages */
 	Event ev[5];   /* timing: plan begin/end, fills done, all done, fills may start */
 	std::vector<Event> lev;     /* kLevPerLaunch events per fill launch (LaunchEvent) */
 	std::vector<cvx_launch_info> launches;
@@ -278,7 +279,7 @@ struct cvx_batch_s {
 		static_assert(11 + 17 + 4 + 4 <= kSharedMarks, "marks");
 	}
 	int make_events() {
-		for (Event *e : { &ev_in, &ev_res, &ev_bt0, &ev_bt1 }) HIP_TRY(e->make(hipEventDisableTiming));
+		for (Event *e : { &ev_in, &ev_res, &ev_rec, &ev_bt0, &ev_bt1 }) HIP_TRY(e->make(hipEventDisableTiming));
 		for (Event &e : ev) HIP_TRY(e.make());
 		return CVX_OK;
 	}
@@ -298,6 +299,18 @@ struct LadderState {
 	uint64_t seq_bytes_after_submit = 0;   /* sequence bytes queued for upload, copy or decode by a later rung: nothing adds to it */
 	cvx_timing timing;               /* summed over the rungs */
 	std::vector<cvx_launch_info> launches; /* the rungs' launches, in order */
+	/* a handle with CVX_CREATE_NM_REGIONS / _INV_CHECKS / _JOB_TEXT (cvx_submit_ladder_ex): every rung runs those stages behind its
+	 * own compaction, and cvx_wait merges what they brought back -- per tile the reporting rung's, in tile order, offsets rebased
+	 * (cvx_ladder_merge.h).  What cvx_job_regions / _checks / _texts hand out for the job, in an ordinary job's layout */
+	std::vector<uint64_t> jr_off;          /* region_off[n + 1] */
+	std::vector<NmRegion> jr_reg;
+	std::vector<NmOpen> jr_open;
+	std::vector<InvCheck> jr_chk;          /* parallel to jr_reg (a job with a genome on a checks handle) */
+	int jr_rewrites = 0;                   /* summed over the rungs */
+	std::vector<TextRec> jt_rec;
+	std::vector<uint64_t> jt_off;          /* text_off[n + 1] */
+	std::vector<char> jt_text;
+	int jt_rewrites = 0;
 };
 
 struct cvx_context {

@@ -32,6 +32,7 @@
 
 #include "cvx_ladder.h"
 #include "cvx_ladder_logic.h"
+#include "cvx_ladder_merge.h"
 #include "cvx_qry_stage.h"
 #include "cvx_rt.h"
 
@@ -314,9 +315,14 @@ int stage_plan(cvx_context *h, cvx_batch_s *b, hipStream_t st) {
 }
 
 /* ---- stage 3's helpers */
+/* the sequence arena a batch's kernels read: a later rung of a ladder job reads rung 1's sequences where they lie */
+const uint8_t *batch_seq(const cvx_batch_s *b) { return b->ladder_root ? b->ladder_root->d_seq.p : b->d_seq.p; }
+
+int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m, bool inline_);
+
 /* the kernels' arguments of a batch; a fill launch adds its own list, chain fields and priority */
 void kernel_args(const cvx_context *h, const cvx_batch_s *b, const ChainBlk *chain_blk, FillArgs &a, BacktrackArgs &ba) {
-	a.seq = ba.seq = b->ladder_root ? b->ladder_root->d_seq.p : b->d_seq.p;      /* (a later rung of a ladder job reads rung 1's sequences where they lie) */
+	a.seq = ba.seq = batch_seq(b);
 	a.rows = ba.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
 	a.rsrc = ba.rsrc = b->d_rsrc.p;
 	a.tin = ba.tin = b->d_tin.p;
@@ -415,7 +421,7 @@ int queue_job_regions(cvx_batch_s *b, hipStream_t st, bool rewrite) {
 		InvCheckArgs c;
 		memset(&c, 0, sizeof(c));
 		c.bin = b->jc_bin; c.L = b->jc_L;
-		c.seq = b->d_seq.p; c.tin = b->d_tin.p; c.win = b->d_win.p;
+		c.seq = batch_seq(b); c.tin = b->d_tin.p; c.win = b->d_win.p;      /* (a later rung's d_win: gathered by ladder_next_kernel) */
 		c.rec = reinterpret_cast<const ResultRec *>(b->d_res.p);
 		c.off = d_off; c.regions = b->d_jrreg.p; c.checks = b->d_jrchk.p;
 		c.cap = b->jr_cap; c.n_tiles = n;
@@ -447,7 +453,7 @@ int queue_job_text(cvx_batch_s *b, hipStream_t st, bool rewrite, uint64_t tune =
 	}
 	TextArgs a;
 	memset(&a, 0, sizeof(a));
-	a.seq = b->d_seq.p; a.tin = b->d_tin.p; a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
+	a.seq = batch_seq(b); a.tin = b->d_tin.p; a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
 	a.recs = b->d_jtrec.p;
 	a.text_len = b->d_jtoff.p; a.text_off = b->d_jtoff.p + n1; a.text_total = b->d_jtoff.p + 2 * n1;
 	a.text = b->d_jtext.p;
@@ -675,6 +681,16 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	BatchSummary *d_sum = reinterpret_cast<BatchSummary *>(b->d_res.p + (size_t) n * sizeof(ResultRec));
 	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, b->d_dstoff.p + n, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
 	HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, n, b->dense_cap, st));
+	if (b->jr_on || b->jt_on) {
+		/* A rung of a ladder job whose handle runs stages behind the compaction: the climb reads result statuses only, so the
+		 * decision kernel, the next rung's plan and their read-back go in FRONT of this rung's regions, checks and text -- the
+		 * host has the next rung's plan in hand while the device still writes this rung's strings. */
+		cvx_batch_s *root = b->ladder ? b : b->ladder_root;
+		if (root && root->ladder && !root->ladder->next && !root->ladder->done) {
+			HIP_TRY(hipEventRecord(b->ev_rec, st));
+			RC_TRY(ladder_queue_next(h, root, b, (int) root->ladder->rungs.size(), true));
+		}
+	}
 	if (b->jr_on) RC_TRY(queue_job_regions(b, st, false));      /* (inside the compute stage's timing: ev[3] below) */
 	if (b->jt_on) RC_TRY(queue_job_text(b, st, false, h->tune_job_text_cap));      /* (as is this) */
 	HIP_TRY(hipEventRecord(b->ev[3], st));
@@ -815,7 +831,7 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 
 /* behind rung `prev` (rung m, computed) of `root`: the decision kernel, the plan of the tiles it lists, and list, tile records,
  * corridors and plan records on their way to the host; L->next is the batch they belong to */
-int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m) {
+int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m, bool inline_) {
 	LadderState *L = root->ladder;
 	const int np = prev->n;
 	if (np <= 0 || m >= L->max_rungs) { L->done = true; return CVX_OK; }
@@ -823,7 +839,8 @@ int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int 
 	if (!c) { set_err("cvx_submit_ladder: no memory for rung %d", m + 1); return CVX_ERR_OOM; }
 	c->bind(h->marks);
 	c->n = 0; c->state = kEmpty; c->in_flight = false; c->have_ops = false; c->have_refs = false; c->text_done = false;
-	c->jr_on = c->jc_on = c->jt_on = false; c->jc_bin = nullptr; c->jc_L = 0;
+	c->jr_on = c->jc_on = c->jt_on = false;      /* (the rung's compute stage sets them from the handle, like any job's) */
+	c->jc_bin = root->jc_bin; c->jc_L = root->jc_L;      /* the job's genome: the rung's regions get their checks */
 	c->ops_total = 0; c->seq_total = 0; c->n_rows = 0; c->n_rowsx = 0; c->zero_copy_bytes = 0;
 	memset(&c->timing, 0, sizeof(c->timing));
 	c->ladder_root = root;
@@ -849,8 +866,11 @@ int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int 
 		HIP_TRY(hipMemset(c->d_counters.p, 0, c->d_counters.cap * sizeof(int32_t)));
 	}
 	RC_TRY(c->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	if (c->jc_bin) RC_TRY(c->d_win.ensure(n1));
 	hipStream_t st = h->s_main;
-	HIP_TRY(hipStreamWaitEvent(st, prev->ev_res, 0));      /* rung m's records are final */
+	/* rung m's records are final: behind their copy to the host, or (queued from inside rung m's compute stage, in front of its
+	 * stages) behind the event right behind the records and the compaction */
+	HIP_TRY(hipStreamWaitEvent(st, inline_ ? prev->ev_rec : prev->ev_res, 0));
 	LadderNextArgs a;
 	a.res = reinterpret_cast<const ResultRec *>(prev->d_res.p);
 	a.prev_idx = prev == root ? nullptr : prev->d_lhead.p + 1;
@@ -859,6 +879,8 @@ int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int 
 	a.n_prev = np;
 	a.m = m;
 	a.rsrc = c->d_rsrc.p; a.tin = c->d_tin.p; a.head = c->d_lhead.p;
+	a.win0 = c->jc_bin ? root->d_win.p : nullptr;
+	a.win = c->jc_bin ? c->d_win.p : nullptr;
 	HIP_TRY(launch_ladder_next(a, st));
 	HIP_TRY(hipEventRecord(c->ev[0], st));
 	HIP_TRY(launch_plan(c->d_rows.p, c->d_rsrc.p, c->d_tin.p, c->d_plan.p, np, root->n ? root->n_rows / (uint64_t) root->n : 0, h->max_matrix_mb, st));
@@ -878,7 +900,7 @@ void ladder_advance(cvx_context *h, cvx_batch_s *root, bool block) {
 	while (root->state != kFailed && !L->done) {
 		int rc = CVX_OK;
 		if (!L->next) {
-			rc = ladder_queue_next(h, root, L->rungs.back(), (int) L->rungs.size());
+			rc = ladder_queue_next(h, root, L->rungs.back(), (int) L->rungs.size(), false);
 			if (rc != CVX_OK) { (void) fail_job(root, rc); break; }
 			continue;
 		}
@@ -918,6 +940,68 @@ void ladder_advance(cvx_context *h, cvx_batch_s *root, bool block) {
 void ladder_pump(cvx_context *h) {
 	const std::vector<cvx_batch_s *> jobs = h->climbing;      /* (ladder_advance takes finished ladders off the list) */
 	for (cvx_batch_s *root : jobs) ladder_advance(h, root, false);
+}
+
+/* What the rungs' stages brought back (regions with their end states and checks, text records and strings; every rung's own
+ * stage_results / stage_ops have run), merged for the job: per tile the reporting rung's, in tile order, offsets rebased into
+ * one dense arena each (ladder_merge_plan, cvx_ladder_merge.h).  A twin handle's CVX_NOT_WRITTEN fields are already in every
+ * rung's records (stage_results) and travel with them. */
+int ladder_merge_stages(cvx_batch_s *root, const std::vector<int32_t> &rung_of, const std::vector<int32_t> &at) {
+	LadderState *L = root->ladder;
+	const int n = root->n;
+	const int32_t n_rungs = (int32_t) L->rungs.size();
+	std::vector<const uint64_t *> off((size_t) n_rungs);
+	std::vector<const void *> rec((size_t) n_rungs);
+	std::vector<int32_t> rn((size_t) n_rungs);
+	std::vector<LadderSpan> spans;
+	for (int32_t r = 0; r < n_rungs; ++r) rn[(size_t) r] = L->rungs[(size_t) r]->n;
+	L->jr_rewrites = L->jt_rewrites = 0;
+	if (root->jr_on) {
+		for (int32_t r = 0; r < n_rungs; ++r) {
+			const cvx_batch_s *c = L->rungs[(size_t) r];
+			if (!c->jr_on) { set_err("internal: rung %d of a regions job ran without the finder", r + 1); return CVX_ERR_HIP; }
+			off[(size_t) r] = c->h_jroff.as<uint64_t>();
+			rec[(size_t) r] = c->h_jropen.p;
+			L->jr_rewrites += c->jr_rewrites;
+		}
+		L->jr_off.assign((size_t) n + 1, 0);
+		if (!ladder_merge_plan(n, rung_of.data(), at.data(), n_rungs, off.data(), rn.data(), L->jr_off.data(), spans)) {
+			set_err("internal: the region offsets of a ladder job's rungs do not merge");
+			return CVX_ERR_HIP;
+		}
+		const uint64_t total = L->jr_off[(size_t) n];
+		L->jr_reg.resize((size_t) total);
+		L->jr_chk.resize(root->jc_on ? (size_t) total : 0);
+		for (const LadderSpan &s : spans) {
+			const cvx_batch_s *c = L->rungs[(size_t) s.rung];
+			memcpy(L->jr_reg.data() + s.dst, c->h_jrreg.as<NmRegion>() + s.src, (size_t) s.len * sizeof(NmRegion));
+			if (root->jc_on) {
+				if (!c->jc_on) { set_err("internal: rung %d of a checks job ran without the checks", s.rung + 1); return CVX_ERR_HIP; }
+				memcpy(L->jr_chk.data() + s.dst, c->h_jrchk.as<InvCheck>() + s.src, (size_t) s.len * sizeof(InvCheck));
+			}
+		}
+		L->jr_open.resize((size_t) n);
+		ladder_merge_records(n, rung_of.data(), at.data(), rec.data(), sizeof(NmOpen), L->jr_open.data());
+	}
+	if (root->jt_on) {
+		for (int32_t r = 0; r < n_rungs; ++r) {
+			const cvx_batch_s *c = L->rungs[(size_t) r];
+			if (!c->jt_on) { set_err("internal: rung %d of a text job ran without the text stage", r + 1); return CVX_ERR_HIP; }
+			off[(size_t) r] = c->h_jtoff.as<uint64_t>();
+			rec[(size_t) r] = c->h_jtrec.p;
+			L->jt_rewrites += c->jt_rewrites;
+		}
+		L->jt_off.assign((size_t) n + 1, 0);
+		if (!ladder_merge_plan(n, rung_of.data(), at.data(), n_rungs, off.data(), rn.data(), L->jt_off.data(), spans)) {
+			set_err("internal: the text offsets of a ladder job's rungs do not merge");
+			return CVX_ERR_HIP;
+		}
+		L->jt_text.assign((size_t) L->jt_off[(size_t) n] + 1, '\0');
+		for (const LadderSpan &s : spans) memcpy(L->jt_text.data() + s.dst, L->rungs[(size_t) s.rung]->h_jtext.as<char>() + s.src, (size_t) s.len);
+		L->jt_rec.resize((size_t) n);
+		ladder_merge_records(n, rung_of.data(), at.data(), rec.data(), sizeof(TextRec), L->jt_rec.data());
+	}
+	return CVX_OK;
 }
 
 /* the job's answer, once its ladder is done: every rung's records and ops waited for, then merged on the host -- per tile the
@@ -969,6 +1053,7 @@ int ladder_finish(cvx_context *h, cvx_batch_s *root) {
 		out[i].reserved = 0;
 	}
 	L->ops_total = used;
+	RC_TRY(ladder_merge_stages(root, rung_of, at));
 	memset(&L->timing, 0, sizeof(L->timing));
 	L->launches.clear();
 	for (const cvx_batch_s *c : L->rungs) {
@@ -1257,13 +1342,10 @@ int cvx_submit_segments(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *t
 	ABI_GUARD_END
 }
 
-int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out) {
-	ABI_GUARD_BEGIN
-	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("cvx_submit_ladder: bad argument"); return CVX_ERR_ARG; }
-	if (h->nm_regions || h->job_text || h->inv_checks || h->service) {
-		set_err("cvx_submit_ladder: not on a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS or _SERVICE");
-		return CVX_ERR_ARG;
-	}
+/* what cvx_submit_ladder and cvx_submit_ladder_ex share behind their own refusals: the ladders checked, rung 1's form written
+ * into a copy of the tiles, the job submitted (segs: its queries are segments of a read block, cvx_submit_segments' rules) */
+static int submit_ladder_common(const char *who, cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position,
+		const cvx_ladder *ladders, const SegmentsIn *segs, cvx_job *out) {
 	/* rung 1's corridor from the ladder, like every later rung's; every rung a tile can reach checked here, on the host,
 	 * so that the kernel writes none the device would refuse */
 	std::vector<cvx_tile> forms(tiles, tiles + n);
@@ -1272,7 +1354,7 @@ int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *til
 		cvx_tile &t = forms[(size_t) i];
 		const cvx_ladder &l = ladders[i];
 		if (!ladder_args_ok(l, t.ref_len, t.qry_len)) {
-			set_err("cvx_submit_ladder: tile %d: corridor %d, left %g, right %g, flags %d, ref_len %d, qry_len %d", i, l.corridor, (double) l.left, (double) l.right, l.flags, t.ref_len, t.qry_len);
+			set_err("%s: tile %d: corridor %d, left %g, right %g, flags %d, ref_len %d, qry_len %d", who, i, l.corridor, (double) l.left, (double) l.right, l.flags, t.ref_len, t.qry_len);
 			return CVX_ERR_ARG;
 		}
 		const int len = ladder_length(l.corridor, l.flags, t.ref_len);
@@ -1281,7 +1363,7 @@ int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *til
 			RowSrc f;
 			ladder_form(l.corridor, l.left, l.right, l.flags, t.ref_len, t.qry_len, m, f);
 			if (f.width < 0 || (f.fmt == kRowsAffine && !affine_form_ok(f.k, f.d, f.right, t.qry_len))) {
-				set_err("cvx_submit_ladder: tile %d: the corridor of rung %d is out of range", i, m);
+				set_err("%s: tile %d: the corridor of rung %d is out of range", who, i, m);
 				return CVX_ERR_ARG;
 			}
 			t.corridor_kind = f.fmt == kRowsConst ? CVX_CORRIDOR_CONST : CVX_CORRIDOR_AFFINE;
@@ -1291,7 +1373,35 @@ int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *til
 		t.row_offset = nullptr; t.row_length = nullptr; t.row_stride_bytes = 4;
 	}
 	static const cvx_ladder none = { 0, 0.0f, 0.0f, 0 };      /* (an empty job is a ladder job too) */
-	return submit_common(h, n, forms.data(), g, ref_position, out, nullptr, ladders ? ladders : &none, max_rungs);
+	return submit_common(h, n, forms.data(), g, ref_position, out, segs, ladders ? ladders : &none, max_rungs);
+}
+
+int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out) {
+	ABI_GUARD_BEGIN
+	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("cvx_submit_ladder: bad argument"); return CVX_ERR_ARG; }
+	if (h->nm_regions || h->job_text || h->inv_checks || h->service) {
+		set_err("cvx_submit_ladder: not on a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS or _SERVICE (the first three: cvx_submit_ladder_ex)");
+		return CVX_ERR_ARG;
+	}
+	return submit_ladder_common("cvx_submit_ladder", h, g, n, tiles, ref_position, ladders, nullptr, out);
+	ABI_GUARD_END
+}
+
+int cvx_submit_ladder_ex(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders,
+		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, const cvx_read_segment *qry, cvx_job *out) {
+	ABI_GUARD_BEGIN
+	static const char who[] = "cvx_submit_ladder_ex";
+	if (out) *out = nullptr;
+	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("%s: bad argument", who); return CVX_ERR_ARG; }
+	if (h->service) { set_err("%s: not on a CVX_CREATE_SERVICE handle", who); return CVX_ERR_ARG; }
+	if (!qry) {
+		/* the string form: nothing of a read block may come with it */
+		if (n_reads != 0 || arena || offsets) { set_err("%s: a read block (n_reads %d, arena, offsets) without segments", who, n_reads); return CVX_ERR_ARG; }
+		return submit_ladder_common(who, h, g, n, tiles, ref_position, ladders, nullptr, out);
+	}
+	if (n_reads < 0 || !offsets || (n_reads > 0 && !arena)) { set_err("%s: segments without their read block (n_reads %d)", who, n_reads); return CVX_ERR_ARG; }
+	const SegmentsIn segs = { n_reads, arena, offsets, qry };
+	return submit_ladder_common(who, h, g, n, tiles, ref_position, ladders, &segs, out);
 	ABI_GUARD_END
 }
 

@@ -83,7 +83,11 @@ int cvx_job_checks(cvx_handle h, cvx_job j, const cvx_inv_check **checks) {
 	if (checks) *checks = nullptr;
 	if (!h || !j || !checks) { set_err("cvx_job_checks: NULL argument"); return CVX_ERR_ARG; }
 	if (!h->inv_checks) { set_err("cvx_job_checks: the handle was created without CVX_CREATE_INV_CHECKS"); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jr_on) { set_err("cvx_job_checks: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->state < kFinished || !j->have_ops || !j->jr_on || (j->ladder && !j->ladder->merged)) { set_err("cvx_job_checks: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
+	if (j->ladder) {      /* a ladder job: the checks cvx_wait merged beside its regions */
+		if (j->jc_on && !j->ladder->jr_chk.empty()) *checks = reinterpret_cast<const cvx_inv_check *>(j->ladder->jr_chk.data());
+		return CVX_OK;
+	}
 	/* nothing is launched, copied or waited for here: the records came with the regions (stage_ops) */
 	if (j->jc_on && j->jr_total) *checks = j->h_jrchk.as<cvx_inv_check>();
 	return CVX_OK;

@@ -336,7 +336,7 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 static int job_regions_ready(const char *who, cvx_handle h, cvx_job j) {
 	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
 	if (!h->nm_regions) { set_err("%s: the handle was created without CVX_CREATE_NM_REGIONS", who); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jr_on) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
+	if (j->state < kFinished || !j->have_ops || !j->jr_on || (j->ladder && !j->ladder->merged)) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
 	return CVX_OK;
 }
 
@@ -347,6 +347,13 @@ int cvx_job_regions(cvx_handle h, cvx_job j, const uint64_t **region_off, const 
 	if (regions) *regions = nullptr;
 	if (open) *open = nullptr;
 	RC_TRY(job_regions_ready("cvx_job_regions", h, j));
+	if (j->ladder) {      /* a ladder job: what cvx_wait merged from its rungs, in the same layout */
+		const LadderState *L = j->ladder;
+		if (region_off) *region_off = L->jr_off.data();
+		if (regions) *regions = L->jr_reg.empty() ? nullptr : reinterpret_cast<const cvx_nm_region *>(L->jr_reg.data());
+		if (open) *open = j->n > 0 ? reinterpret_cast<const cvx_nm_open *>(L->jr_open.data()) : nullptr;
+		return CVX_OK;
+	}
 	if (region_off) *region_off = j->h_jroff.as<uint64_t>();
 	if (regions) *regions = j->h_jrreg.as<cvx_nm_region>();      /* (NULL for a job that never had a region: nothing to point at) */
 	if (open) *open = j->n > 0 ? j->h_jropen.as<cvx_nm_open>() : nullptr;
@@ -357,6 +364,12 @@ int cvx_job_regions(cvx_handle h, cvx_job j, const uint64_t **region_off, const 
 int cvx_job_regions_info(cvx_handle h, cvx_job j, uint64_t *total, uint64_t *first_capacity, int32_t *rewrites) {
 	ABI_GUARD_BEGIN
 	RC_TRY(job_regions_ready("cvx_job_regions_info", h, j));
+	if (j->ladder) {      /* the merged total, the rungs' rewrites summed, rung 1's first capacity */
+		if (total) *total = j->ladder->jr_off[(size_t) j->n];
+		if (first_capacity) *first_capacity = j->n > 0 ? j->h_jroff.as<uint64_t>()[(size_t) j->n + 1] : 0;
+		if (rewrites) *rewrites = j->ladder->jr_rewrites;
+		return CVX_OK;
+	}
 	if (total) *total = j->jr_total;
 	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jroff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
 	if (rewrites) *rewrites = j->jr_rewrites;
@@ -368,7 +381,7 @@ int cvx_job_regions_info(cvx_handle h, cvx_job j, uint64_t *total, uint64_t *fir
 static int job_texts_ready(const char *who, cvx_handle h, cvx_job j) {
 	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
 	if (!h->job_text) { set_err("%s: the handle was created without CVX_CREATE_JOB_TEXT", who); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jt_on) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
+	if (j->state < kFinished || !j->have_ops || !j->jt_on || (j->ladder && !j->ladder->merged)) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
 	return CVX_OK;
 }
 
@@ -380,6 +393,13 @@ int cvx_job_texts(cvx_handle h, cvx_job j, const cvx_alignment_text **recs, cons
 	if (text_off) *text_off = nullptr;
 	if (text) *text = nullptr;
 	RC_TRY(job_texts_ready("cvx_job_texts", h, j));
+	if (j->ladder) {      /* a ladder job: what cvx_wait merged from its rungs, in the same layout */
+		const LadderState *L = j->ladder;
+		if (recs) *recs = j->n > 0 ? reinterpret_cast<const cvx_alignment_text *>(L->jt_rec.data()) : nullptr;
+		if (text_off) *text_off = L->jt_off.data();
+		if (text) *text = j->n > 0 ? L->jt_text.data() : "";
+		return CVX_OK;
+	}
 	if (recs) *recs = j->n > 0 ? j->h_jtrec.as<cvx_alignment_text>() : nullptr;
 	if (text_off) *text_off = j->h_jtoff.as<uint64_t>();
 	if (text) *text = j->n > 0 ? j->h_jtext.as<char>() : "";
@@ -390,6 +410,12 @@ int cvx_job_texts(cvx_handle h, cvx_job j, const cvx_alignment_text **recs, cons
 int cvx_job_texts_info(cvx_handle h, cvx_job j, uint64_t *total_bytes, uint64_t *first_capacity, int32_t *rewrites) {
 	ABI_GUARD_BEGIN
 	RC_TRY(job_texts_ready("cvx_job_texts_info", h, j));
+	if (j->ladder) {
+		if (total_bytes) *total_bytes = j->ladder->jt_off[(size_t) j->n];
+		if (first_capacity) *first_capacity = j->n > 0 ? j->h_jtoff.as<uint64_t>()[(size_t) j->n + 1] : 0;
+		if (rewrites) *rewrites = j->ladder->jt_rewrites;
+		return CVX_OK;
+	}
 	if (total_bytes) *total_bytes = j->jt_total;
 	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jtoff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
 	if (rewrites) *rewrites = j->jt_rewrites;
