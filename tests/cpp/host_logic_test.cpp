@@ -611,6 +611,95 @@ int main() {
 		CHECK(hl.n_chained == 1 && hl.trun[0].mnw == 2 && hl.trun[0].ring == 128);   // forced block height
 		CHECK(chain_class_for(175, true) == 0 && chain_class_for(4000, false) == 0); // 64-row blocks for every batch
 	}
+	// ---------------------------------------------------------------- chained tiles: block starts and boundary spans at their edges
+	// (the row geometries of tests/chain_cases.py's phase and clip families, written out)
+	{
+		const int L = 200;
+		// plans one tile of rows (off[y], L) in a window of W columns and checks what holds for every chained tile; -> its tasks
+		auto plan_rows = [&](const std::vector<int> &off, int W, int N, std::vector<ChainTask> &tk, HostPlan &hc, int &r0) {
+			const int H = (int) off.size();
+			std::vector<RowDesc> rows((size_t) H);
+			std::vector<long long> lo((size_t) H), hi((size_t) H);
+			long long r0min = 0x7fffffff, rend = -0x7fffffff;
+			for (int y = 0; y < H; ++y) {
+				rows[(size_t) y].off = off[(size_t) y]; rows[(size_t) y].len = L;
+				lo[(size_t) y] = std::max(off[(size_t) y], 0);
+				hi[(size_t) y] = std::max<long long>(std::min<long long>((long long) off[(size_t) y] + L, W), lo[(size_t) y]);
+				r0min = std::min(r0min, lo[(size_t) y] + y); rend = std::max(rend, hi[(size_t) y] + y);      // (plan_row_common: every row, empty ones too)
+			}
+			TilePlan p; memset(&p, 0, sizeof(p));
+			p.r0 = (int) r0min; p.rend = (int) rend; p.need = 100;
+			TileIn in; memset(&in, 0, sizeof(in));
+			in.H = H; in.W = W;
+			TileRun r; memset(&r, 0, sizeof(r));
+			hc = HostPlan();
+			tk.clear();
+			plan_chain_tile(0, N / 64, p, in, rows.data(), hc, r, tk);
+			r0 = p.r0;
+			CHECK((int) tk.size() == (H + N - 1) / N && r.chain_nblk == (int) tk.size() && r.ring == N);
+			uint64_t bnd = 0;
+			for (int g = 0; g < (int) tk.size(); ++g) {
+				const ChainTask &t = tk[(size_t) g];
+				const int y0 = g * N, y1 = std::min(H, y0 + N);
+				long long first = 0x7fffffff, end = -0x7fffffff;
+				for (int y = y0; y < y1; ++y) if (hi[(size_t) y] > lo[(size_t) y]) { first = std::min(first, lo[(size_t) y] + y); end = std::max(end, hi[(size_t) y] + y); }
+				CHECK(t.y0 == y0 && t.rows == y1 - y0 && ((t.r0 - p.r0) & 31) == 0 && t.r0 >= p.r0);
+				if (end > first) {
+					// the block begins on a multiple of 32 steps, its first cell 1 ... 32 steps behind (0 ... 31 in block 0), its last cell inside
+					CHECK(first - t.r0 >= (g > 0 ? 1 : 0) && first - t.r0 <= (g > 0 ? 32 : 31) && end == (long long) t.r0 + t.nsteps);
+				} else {
+					CHECK(t.nsteps == 0);
+				}
+				if (g > 0) CHECK(t.bnd_lo == lo[(size_t) y0 - 1] && t.bnd_len == hi[(size_t) y0 - 1] - lo[(size_t) y0 - 1] && t.bnd_in_off == tk[(size_t) g - 1].bnd_out_off);
+				CHECK(t.bnd_out_off == bnd);
+				if (t.has_next) bnd += (uint64_t) (hi[(size_t) y1 - 1] - lo[(size_t) y1 - 1]);
+				if (t.nsteps == 0) CHECK(bnd == t.bnd_out_off);      // a block without cells adds no record
+			}
+			CHECK(bnd == hc.bnd_recs);
+		};
+		for (int N : {64, 128, 256}) {
+			// phase: =56 D d =max(100, N + 20), the path at column 100, 0 or 1 of its row: row N's first cell 2 N + d steps behind r0
+			const int tail = std::max(100, N + 20);
+			bool seen[32] = {false};
+			for (int d = 0; d <= 32; ++d)
+				for (int col : {100, 0, 1}) {
+					std::vector<int> off((size_t) (56 + tail));
+					for (int y = 0; y < (int) off.size(); ++y) off[(size_t) y] = 201 + y + (y >= 56 ? d : 0) - col;
+					std::vector<ChainTask> tk; HostPlan hc; int r0;
+					plan_rows(off, 402 + 56 + d + tail, N, tk, hc, r0);
+					const int first = off[(size_t) N] + N - r0;
+					CHECK(first == 2 * N + d && tk.size() >= 2);
+					const ChainTask &t = tk[1];
+					CHECK((t.r0 - r0) % 32 == 0 && first - (t.r0 - r0) >= 1 && first - (t.r0 - r0) <= 32);
+					if (first % 32 == 0) CHECK(t.r0 - r0 == first - 32);      // the first cell on a multiple of 32: the block begins a whole word before it
+					CHECK(t.bnd_lo == off[(size_t) N - 1] && t.bnd_len == L);
+					seen[first % 32] = true;
+				}
+			for (bool s : seen) CHECK(s);
+			// clip: =(N - 4) D3 =70 I4 =(N + 56), the path at column 100, the window cut from the left or the right
+			const int H = 2 * N + 126, Wfull = 2 * N + 527;
+			std::vector<int> base((size_t) H);
+			for (int y = 0; y < H; ++y) base[(size_t) y] = 101 + (y < N - 4 ? y : y < N + 66 ? y + 3 : y < N + 70 ? N + 68 : y - 1);
+			const int last0 = (H - 1) / N * N;
+			const int left[] = {base[(size_t) N - 1] + 40, base[(size_t) N - 1], base[(size_t) N], base[(size_t) N - 1] + L, base[(size_t) N - 1] + L - 1};
+			const int right[] = {base[(size_t) N - 1] + L - 1, base[(size_t) last0]};
+			for (int c = 0; c < 7; ++c) {
+				std::vector<int> off = base;
+				int W = Wfull;
+				if (c < 5) { for (int &o : off) o -= left[c]; W -= left[c]; } else W = right[c - 5];
+				std::vector<ChainTask> tk; HostPlan hc; int r0;
+				plan_rows(off, W, N, tk, hc, r0);
+				const ChainTask &t = tk[1];
+				if (c == 0) CHECK(t.bnd_lo == 0 && t.bnd_len == L - 40);
+				if (c == 1) CHECK(t.bnd_lo == 0 && t.bnd_len == L);
+				if (c == 2) CHECK(t.bnd_lo == 0 && t.bnd_len == L - 1);
+				if (c == 3) CHECK(tk[0].nsteps == 0 && t.bnd_len == 0 && tk[1].bnd_out_off == 0 && t.nsteps > 0);
+				if (c == 4) CHECK(tk[0].r0 + tk[0].nsteps == N && t.bnd_lo == 0 && t.bnd_len == 1 && tk[1].bnd_out_off == 1);      // one cell, at step N - 1
+				if (c == 5) CHECK(t.bnd_lo == off[(size_t) N - 1] && t.bnd_len == L - 1);
+				if (c == 6) CHECK(tk.back().nsteps == 0 && tk.back().bnd_len > 0 && tk[tk.size() - 2].nsteps > 0);
+			}
+		}
+	}
 	// ---------------------------------------------------------------- the compute stage's launch schedule
 	{
 		struct Batch {
