@@ -13,7 +13,7 @@
 namespace cvx {
 
 /* The regions lie dense and in tile order; tile t owns regions [off[t], off[t + 1]) and off[n_tiles] is their total -- the layout
- * of a job's offsets (queue_job_regions: the scan's total right behind the n offsets) and of cvx_inv_checks' region_off.  The
+ * of a job's offsets (JobRegions::queue: the scan's total right behind the n offsets) and of cvx_inv_checks' region_off.  The
  * kernel looks at min(off[n_tiles], cap) regions: a job's arena may hold fewer than the job has (the write is bounded), and the
  * launch covers the arena, since only the device knows the total when it is queued. */
 struct InvCheckArgs {

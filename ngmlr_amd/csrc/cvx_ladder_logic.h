@@ -1,7 +1,7 @@
 /*
  * cvx_ladder_logic.h -- the corridor retry ladder of AlignmentBuffer::computeAlignment (reference
  * src/AlignmentBuffer.cpp:259-425) as plain functions compiled for the device and for the host, free of HIP calls, so that
- * ladder_next_kernel (cvx_ladder.hip), cvx_ladder_rung (cvx_corridor.cpp), cvx_submit_ladder (cvx_rt_align.cpp) and the CPU suite
+ * ladder_next_kernel (cvx_ladder.hip), cvx_ladder_rung (cvx_corridor.cpp), cvx_submit_ladder (cvx_rt_ladder.cpp) and the CPU suite
  * (tests/test_ladder_logic_cpu.py, through cvx_ladder_rung) run one rule.
  *
  * An attempt that is not valid rebuilds the corridor at multiplier 2, 3, ... and aligns again:

@@ -1,7 +1,7 @@
 /*
  * cvx_ladder_merge.h -- how cvx_wait strings the per-rung stage outputs of a ladder job (cvx_submit_ladder_ex on a handle with
  * CVX_CREATE_NM_REGIONS / _INV_CHECKS / _JOB_TEXT) into the one dense arena an ordinary job hands out, as plain host code free
- * of HIP calls, so that ladder_finish (cvx_rt_align.cpp) and the CPU suite (tests/cpp/ladder_merge_test.cpp) run one rule.
+ * of HIP calls, so that ladder_finish (cvx_rt_ladder.cpp) and the CPU suite (tests/cpp/ladder_merge_test.cpp) run one rule.
  *
  * Every rung's batch keeps its own offsets (an exclusive scan over ITS tiles, the total behind them) and its own arena -- regions
  * and their checks in records, the two strings of a tile in bytes.  Tile i of the job is reported by rung rung_of[i], where it

@@ -1,15 +1,19 @@
 /*
  * cvx_rt.h -- what the files of the host runtime share (cvx_runtime.cpp and the cvx_rt_*.cpp of its subsystems): the HIP error
- * macro, the grow-only device and page-locked buffers, the handle, job and genome structures, and the helpers more than one of
- * those files calls.  Internal; the public boundary is include/cvx_align.h.
+ * macro, the grow-only device and page-locked buffers, the handle, job and genome structures -- a job's two result stages
+ * (JobRegions, JobText: cvx_rt_stages.cpp) and the definition of a fresh job (cvx_batch_s::begin_job) among them -- and the helpers
+ * more than one of those files calls.  What only the pipeline (cvx_rt_align.cpp) and the ladder jobs (cvx_rt_ladder.cpp) call of
+ * each other: cvx_rt_align.h.  Internal; the public boundary is include/cvx_align.h.
  */
 #ifndef CVX_RT_H
 #define CVX_RT_H
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -114,6 +118,7 @@ struct Event {
 
 bool in_pinned_block(const void *p, uint64_t bytes);      /* [p, p + bytes) lies inside one block of cvx_host_alloc */
 float ev_ms(hipEvent_t a, hipEvent_t b);
+int event_fired(hipEvent_t e);      /* 1: fired; 0: not yet (the query's error is cleared); -1: the query failed (set_err done) */
 int ensure_streams(cvx_context *c);
 /* the per-handle state of the search and of the scoring, owned by their files (cvx_destroy) */
 void search_state_free(cvx_search_state *ss);
@@ -136,7 +141,61 @@ enum LaunchEvent { kLevStart = 0, kLevTwoPhase = 1, kLevExact = 2, kLevWalked = 
 enum BatchState { kFailed = -1, kEmpty = 0, kUploaded = 1, kPlanned = 2, kComputed = 3, kFinished = 4 };
 
 struct LadderState;              /* below: what the first rung of a ladder job (cvx_submit_ladder) carries */
-void ladder_drop(struct cvx_batch_s *root);      /* frees it and the later rungs' batches (cvx_rt_align.cpp); the device is idle, or has nothing of them queued */
+void ladder_drop(struct cvx_batch_s *root);      /* frees it and the later rungs' batches (cvx_rt_ladder.cpp); the device is idle, or has nothing of them queued */
+
+/* The two result stages a handle can run behind every job's compaction (cvx_rt_stages.cpp: what queues them, and the getters that
+ * hand their data out).  Both write into an arena sized by an estimate, the way finalize and compact treat the dense ops, and both
+ * have one life, a call per step from the pipeline:
+ *   queue       (stage_compute) the first pass on the batch's stream, with no host step in front: sizes, the offset scan, the write
+ *               into the estimated arena; the offsets -- the total and the capacity the write ran with behind them -- and the per-tile
+ *               records travel in copies queued here, in front of the event stage_results waits for
+ *   set_empty   (stage_compute, a job without tiles) one offset, 0
+ *   take_total  (stage_results) the total, from the slot behind the n offsets
+ *   fetch       (stage_ops) the total exceeds the capacity: the arena grows and the write alone runs again on the batch's stream,
+ *               waited for; then the arena to the host on `io`, in front of the dense ops and under their wait
+ * reset() is the stage's part of cvx_batch_s::begin_run.  Buffers of their own, so that a stage of the finished job on the text
+ * stream (cvx_job_nm_regions, cvx_job_text) never meets them. */
+
+/* the low-identity regions of the job's tiles (a CVX_CREATE_NM_REGIONS handle; cvx_job_regions), and riding with them the inversion
+ * check of every region (a CVX_CREATE_INV_CHECKS handle, a job submitted with a genome: inv_checks_kernel behind the finder's write;
+ * cvx_job_checks): one record per region of the arena, to the host with the regions */
+struct JobRegions {
+	DevBuf<unsigned long long> d_off;    /* counts[n], offsets[n], the total, the capacity the write ran with */
+	DevBuf<NmOpen> d_open;
+	DevBuf<NmRegion> d_stage, d_reg;
+	DevBuf<InvCheck> d_chk;
+	PinBuf h_off, h_open, h_reg, h_chk;  /* offsets[n] + total + capacity and the end states arrive with the result records, the regions and checks with the dense ops */
+	bool on = false;                 /* this run of the compute stage queued the finder */
+	bool checks_on = false;          /* ... and the checks */
+	uint64_t cap = 0, total = 0;     /* regions the arena holds; regions of the job (after stage_results) */
+	int rewrites = 0;                /* times the write ran again over a larger arena (stage_ops) */
+	const uint8_t *bin = nullptr;    /* the genome the job was submitted with (its owner keeps it alive until cvx_wait), NULL: none, or no flag */
+	uint64_t L = 0;                  /* its GetConcatRefLen() */
+
+	void reset() { on = checks_on = false; cap = total = 0; rewrites = 0; }
+	int queue(struct cvx_batch_s *b, hipStream_t st, bool rewrite = false);
+	int set_empty();
+	void take_total(int n) { if (on) total = h_off.as<unsigned long long>()[(size_t) n]; }
+	int fetch(struct cvx_context *h, struct cvx_batch_s *b);
+};
+
+/* the device text stage over the job's op lists and its sequences in HBM, external clips zero (a CVX_CREATE_JOB_TEXT handle;
+ * cvx_job_texts) */
+struct JobText {
+	DevBuf<TextRec> d_rec;
+	DevBuf<unsigned long long> d_off;    /* lengths[n], offsets[n], the total, the capacity the write ran with */
+	DevBuf<uint8_t> d_text;
+	PinBuf h_rec, h_off, h_text;         /* records and offsets[n] + total + capacity arrive with the result records, the strings with the dense ops */
+	bool on = false;                 /* this run of the compute stage queued the text stage */
+	uint64_t cap = 0, total = 0;     /* bytes the arena holds; bytes of the job's text (after stage_results) */
+	int rewrites = 0;                /* times the write ran again over a larger arena (stage_ops) */
+
+	void reset() { on = false; cap = total = 0; rewrites = 0; }
+	int queue(struct cvx_batch_s *b, hipStream_t st, bool rewrite = false, uint64_t tune = 0);
+	int set_empty();
+	void take_total(int n, bool twin);
+	int fetch(struct cvx_context *h, struct cvx_batch_s *b);
+};
 
 struct cvx_batch_s {
 	int n = 0;
@@ -199,32 +258,9 @@ struct cvx_batch_s {
 	DevBuf<NmRegion> d_nmreg;        /* ... and the regions, dense */
 	PinBuf h_nmroff, h_nmopen;
 	PinBuf h_nmreg;                  /* the regions on the host: what cvx_job_nm_regions hands out */
-	/* the same regions found with the job's results (a CVX_CREATE_NM_REGIONS handle: queue_job_regions in stage_compute, cvx_job_regions);
-	 * buffers of their own, so that a cvx_job_nm_regions call on the text stream never meets them */
-	DevBuf<unsigned long long> d_jroff;  /* counts[n], offsets[n], the total, the capacity the write ran with */
-	DevBuf<NmOpen> d_jropen;
-	DevBuf<NmRegion> d_jrstage, d_jrreg;
-	PinBuf h_jroff, h_jropen, h_jrreg;   /* offsets[n] + total + capacity and the end states arrive with the result records, the regions with the dense ops */
-	bool jr_on = false;              /* this run of the compute stage queued the finder */
-	uint64_t jr_cap = 0, jr_total = 0;      /* regions the arena holds; regions of the job (after stage_results) */
-	int jr_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
-	/* the inversion checks of those regions (a CVX_CREATE_INV_CHECKS handle, a job submitted with a genome: inv_checks_kernel behind the
-	 * finder's write in queue_job_regions, cvx_job_checks): one record per region of the arena, to the host with the regions */
-	DevBuf<InvCheck> d_jrchk;
-	PinBuf h_jrchk;
-	const uint8_t *jc_bin = nullptr; /* the genome the job was submitted with (its owner keeps it alive until cvx_wait), NULL: none, or no flag */
-	uint64_t jc_L = 0;               /* its GetConcatRefLen() */
-	bool jc_on = false;              /* this run of the compute stage queued the checks */
-	/* the device text stage run with the job's results (a CVX_CREATE_JOB_TEXT handle: queue_job_text in stage_compute, cvx_job_texts);
-	 * buffers of their own, so that a cvx_job_text call on the text stream never meets them */
-	DevBuf<TextRec> d_jtrec;
-	DevBuf<unsigned long long> d_jtoff;  /* lengths[n], offsets[n], the total, the capacity the write ran with */
-	DevBuf<uint8_t> d_jtext;
-	PinBuf h_jtrec, h_jtoff, h_jtext;    /* records and offsets[n] + total + capacity arrive with the result records, the strings with the dense ops */
-	bool jt_on = false;              /* this run of the compute stage queued the text stage */
-	uint64_t jt_cap = 0, jt_total = 0;      /* bytes the arena holds; bytes of the job's text (after stage_results) */
-	int jt_rewrites = 0;             /* times the write ran again over a larger arena (stage_ops) */
-	PinBuf h_win;                    /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
+	JobRegions jr;                   /* the same regions, and their inversion checks, found with the job's results */
+	JobText jt;                      /* the text stage run with the job's results */
+	PinBuf h_win;                   /* WindowDesc[n]: reference windows decoded on the device (cvx_submit_windows) */
 	PinBuf h_refs;                   /* ... and the decoded windows back on the host (cvx_job_window_refs): the reference part of d_seq */
 	uint64_t refs_base = 0;          /* offset of that part in the sequence arena */
 	bool have_refs = false;
@@ -282,6 +318,41 @@ struct cvx_batch_s {
 		for (Event *e : { &ev_in, &ev_res, &ev_rec, &ev_bt0, &ev_bt1 }) HIP_TRY(e->make(hipEventDisableTiming));
 		for (Event &e : ev) HIP_TRY(e.make());
 		return CVX_OK;
+	}
+	/* the sequence arena the batch's kernels read: a later rung of a ladder job reads rung 1's sequences where they lie */
+	const uint8_t *seq() const { return ladder_root ? ladder_root->d_seq.p : d_seq.p; }
+
+	/* What a run of the compute stage starts from.  Apart from begin_job: stage_compute itself, since a staged batch can be run
+	 * again without a new upload (cvx_batch_upload, then cvx_batch_run twice). */
+	void begin_run() {
+		launches.clear();
+		launch_tail.clear();
+		ops_total = 0;
+		have_ops = false;
+		jr.reset();
+		jt.reset();
+	}
+	/* THE definition of a fresh job: every per-job member in the state a job starts from.  For a slot that goes back to the pool
+	 * (recycle_batch), one that takes a job's upload (stage_upload) and one that becomes a later rung of a ladder job
+	 * (ladder_queue_next); each then sets what is particular to it.  A failed job's fail_rc / fail_msg live until cvx_job_release:
+	 * none of the three is reached with a job the caller still holds (the last two take their slot from acquire_batch).
+	 * Not here, on purpose: what belongs to the slot's buffers and outlives a job (zero_cap, bnd_epoch, the d_counters' once-only
+	 * clearing, the capacities), and the links between the batches of a ladder job (ladder, ladder_root), which
+	 * ladder_release / ladder_queue_next cut and tie. */
+	void begin_job() {
+		begin_run();
+		n = 0;
+		state = kEmpty;
+		in_flight = false;
+		fail_rc = CVX_OK;
+		fail_msg.clear();
+		seq_total = n_rows = n_rowsx = 0;
+		zero_copy_bytes = 0;
+		have_refs = false;
+		text_done = false;
+		jr.bin = nullptr;
+		jr.L = 0;
+		memset(&timing, 0, sizeof(timing));
 	}
 	~cvx_batch_s() { if (ladder) ladder_drop(this); }      /* a ladder job's later rungs go with it; the buffers and events free themselves */
 };
@@ -396,6 +467,49 @@ struct cvx_context {
 	struct cvx_score_state *score = nullptr;   /* sub-read scoring (cvx_score_batch, cvx_score_submit): jobs kept for reuse once waited for */
 	struct cvx_search_state *search = nullptr;   /* candidate search (cvx_search_batch): persistent staging and device buffers */
 };
+
+/* the job off the handle's lists (any of the three it is on); h may be NULL: a batch that is freed without its handle */
+enum JobList { kListPending = 1, kListLive = 2, kListClimbing = 4 };
+inline void unlist_job(cvx_context *h, const cvx_batch_s *b, int lists) {
+	if (!h) return;
+	std::vector<cvx_batch_s *> *const of[] = { &h->pending, &h->live, &h->climbing };      /* (in JobList's bit order) */
+	for (int k = 0; k < 3; ++k) {
+		const auto it = std::find(of[k]->begin(), of[k]->end(), b);
+		if ((lists >> k & 1) && it != of[k]->end()) of[k]->erase(it);
+	}
+}
+
+/* the buffers that hold one record per tile of a batch of n, for an uploaded job and for a later rung of a ladder job alike; the
+ * counters with them, cleared once when they are allocated (why never again: stage_compute) */
+inline int ensure_tile_records(cvx_batch_s *b, int n) {
+	const size_t n1 = (size_t) std::max(n, 1);
+	RC_TRY(b->h_rsrc.ensure(n1 * sizeof(RowSrc)));
+	RC_TRY(b->h_tin.ensure(n1 * sizeof(TileIn)));
+	RC_TRY(b->h_plan.ensure(n1 * sizeof(TilePlan)));
+	RC_TRY(b->h_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	RC_TRY(b->d_rsrc.ensure(n1));
+	RC_TRY(b->d_tin.ensure(n1));
+	RC_TRY(b->d_plan.ensure(n1));
+	RC_TRY(b->d_trun.ensure(n1));
+	RC_TRY(b->d_tout.ensure(n1));
+	RC_TRY(b->d_dstoff.ensure(n1 + 2 * (size_t) finalize_blocks(n)));      /* ... + launch_finalize's per-block sums behind the n offsets */
+	RC_TRY(b->d_lists.ensure(2 * n1));             /* fill lists + backtrack order */
+	if (b->d_counters.cap < 64) {
+		RC_TRY(b->d_counters.ensure(64));
+		HIP_TRY(hipMemset(b->d_counters.p, 0, b->d_counters.cap * sizeof(int32_t)));
+	}
+	RC_TRY(b->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	return CVX_OK;
+}
+
+/* the TextArgs of the text stage's kernels over a job's arenas; the caller adds the outputs of its own pass */
+inline TextArgs job_text_args(const cvx_batch_s *b) {
+	TextArgs a;
+	memset(&a, 0, sizeof(a));
+	a.seq = b->seq(); a.tin = b->d_tin.p; a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
+	a.n_tiles = b->n;
+	return a;
+}
 
 struct cvx_genome_s {            /* an encoded reference genome resident in HBM (cvx_genome.hip) */
 	int device = 0;

@@ -19,6 +19,11 @@
  * under the kernels of batch k, and the only host waits are on events of work that was queued a
  * whole batch earlier.  The staged entry points (cvx_batch_*) and cvx_align_batch run the same
  * stages back to back.
+ *
+ * Beside this file: the result stages a handle runs with every job -- regions, inversion checks, text -- are called from the
+ * compute, results and ops stages, a line each, and live in cvx_rt_stages.cpp; ladder jobs, whose rungs are batches that go
+ * through the stages here, in cvx_rt_ladder.cpp (cvx_rt_align.h: what the two files call of each other).  What a fresh job
+ * is: cvx_batch_s::begin_job (cvx_rt.h).
  */
 #include <algorithm>
 #include <atomic>
@@ -30,21 +35,8 @@
 #include <string>
 #include <vector>
 
-#include "cvx_ladder.h"
-#include "cvx_ladder_logic.h"
-#include "cvx_ladder_merge.h"
 #include "cvx_qry_stage.h"
-#include "cvx_rt.h"
-
-namespace {
-
-/* the queries of a job of cvx_submit_segments: the call's read block and one segment per tile (cvx_segments.h) */
-struct SegmentsIn {
-	int32_t n_reads;
-	const uint8_t *arena;
-	const uint64_t *offsets;
-	const cvx_read_segment *qry;
-};
+#include "cvx_rt_align.h"
 
 static const size_t kPoolBatches = 8;      /* (4 until the text stage of a finished job got its own thread: a launch in the fill, one uploading, two in the text stage and those the workers still copy from) */
 
@@ -57,61 +49,13 @@ cvx_batch_s *acquire_batch(cvx_context *h) {
 	return new (std::nothrow) cvx_batch_s();
 }
 
-void recycle_batch(cvx_context *h, cvx_batch_s *b);
-
-/* a ladder job leaves: its later rungs' batches go where the job goes (the pool, with their arenas, or the allocator) */
-void ladder_release(cvx_context *h, cvx_batch_s *root) {
-	LadderState *L = root->ladder;
-	if (!L) return;
-	if (h) {
-		auto it = std::find(h->climbing.begin(), h->climbing.end(), root);
-		if (it != h->climbing.end()) h->climbing.erase(it);
-	}
-	root->ladder = nullptr;
-	if (L->next) L->rungs.push_back(L->next);
-	for (size_t r = 1; r < L->rungs.size(); ++r) {
-		cvx_batch_s *c = L->rungs[r];
-		c->ladder_root = nullptr;
-		if (root->state == kFailed) c->state = kFailed;
-		recycle_batch(h, c);
-	}
-	delete L;
-}
-
 void recycle_batch(cvx_context *h, cvx_batch_s *b) {
 	if (b->ladder) ladder_release(h, b);
 	const bool failed = b->state == kFailed;
-	b->state = kEmpty;
-	b->in_flight = false;
-	b->have_ops = false;
-	b->have_refs = false;
-	b->text_done = false;
-	b->jr_on = false;
-	b->jc_on = false;
-	b->jt_on = false;
-	b->fail_rc = CVX_OK;
-	b->fail_msg.clear();
-	if (h) {
-		auto it = std::find(h->live.begin(), h->live.end(), b);
-		if (it != h->live.end()) h->live.erase(it);
-	}
+	b->begin_job();      /* (the caller has let go of the job: a failed one's error ends here) */
+	unlist_job(h, b, kListLive);
 	/* (a job that failed half-way keeps nothing worth pooling: its arenas go back to the allocator) */
 	if (h && !failed && h->pool.size() < kPoolBatches) { h->pool.push_back(b); return; }
-	delete b;
-}
-
-/* something failed after work was queued: nothing may still be running on the arenas when they
- * go back to the allocator (or to the pool) */
-void discard_batch(cvx_context *h, cvx_batch_s *b) {
-	(void) hipDeviceSynchronize();
-	if (h) {
-		auto it = std::find(h->pending.begin(), h->pending.end(), b);
-		if (it != h->pending.end()) h->pending.erase(it);
-		it = std::find(h->live.begin(), h->live.end(), b);
-		if (it != h->live.end()) h->live.erase(it);
-		it = std::find(h->climbing.begin(), h->climbing.end(), b);
-		if (it != h->climbing.end()) h->climbing.erase(it);
-	}
 	delete b;
 }
 
@@ -123,6 +67,16 @@ int fail_job(cvx_batch_s *b, int rc) {
 	b->fail_rc = rc;
 	b->fail_msg = g_err;
 	return rc;
+}
+
+namespace {
+
+/* something failed after work was queued: nothing may still be running on the arenas when they
+ * go back to the allocator (or to the pool) */
+void discard_batch(cvx_context *h, cvx_batch_s *b) {
+	(void) hipDeviceSynchronize();
+	unlist_job(h, b, kListPending | kListLive | kListClimbing);
+	delete b;
 }
 
 /* ---- stage 1: pack into pinned staging and copy to the device, piece by piece (stream `io`) */
@@ -139,20 +93,12 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 		set_err("%llu sequence bytes exceed one batch (4 GiB); split the batch", (unsigned long long) L.seq_total);
 		return CVX_ERR_ARG;
 	}
+	b->begin_job();
 	b->n = n;
-	b->state = kEmpty;
-	b->have_ops = false;
-	b->have_refs = false;
-	b->text_done = false;
-	b->jr_on = false;
-	b->jc_on = false;
-	b->jc_bin = (h->inv_checks && genome && n > 0) ? genome->d_bin.p : nullptr;      /* (then d_win holds every tile's ref_position) */
-	b->jc_L = genome ? score_windows_concat_len(genome->n_nibbles) : 0;
-	b->jt_on = false;
-	b->ops_total = 0;
+	b->jr.bin = (h->inv_checks && genome && n > 0) ? genome->d_bin.p : nullptr;      /* (then d_win holds every tile's ref_position) */
+	b->jr.L = genome ? score_windows_concat_len(genome->n_nibbles) : 0;
 	b->seq_total = L.seq_total;
 	b->n_rows = L.n_rows;
-	memset(&b->timing, 0, sizeof(b->timing));
 	/* segments: every tile's query checked against the read block and cut into the stage kernel's chunks, before anything is queued */
 	SegPlan sp;
 	if (segments) {
@@ -166,28 +112,12 @@ int stage_upload(cvx_context *h, cvx_batch_s *b, int32_t n, const cvx_tile *tile
 		}
 	}
 	RC_TRY(b->make_events());
-	const size_t n1 = (size_t) std::max(n, 1);
 	const size_t rows1 = (size_t) std::max<uint64_t>(L.arena_rows, 1);      /* closed-form corridors own no rows (RowView, cvx_types.h) */
 	RC_TRY(b->h_delta.ensure((size_t) L.delta_total + 256));
-	RC_TRY(b->h_rsrc.ensure(n1 * sizeof(RowSrc)));
 	RC_TRY(b->d_delta.ensure((size_t) L.delta_total + 256));
-	RC_TRY(b->d_rsrc.ensure(n1));
-	RC_TRY(b->h_tin.ensure(n1 * sizeof(TileIn)));
-	RC_TRY(b->h_plan.ensure(n1 * sizeof(TilePlan)));
-	RC_TRY(b->h_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
 	RC_TRY(b->d_seq.ensure((size_t) L.seq_total + 256));
 	RC_TRY(b->d_rows.ensure(rows1));
-	RC_TRY(b->d_tin.ensure(n1));
-	RC_TRY(b->d_plan.ensure(n1));
-	RC_TRY(b->d_trun.ensure(n1));
-	RC_TRY(b->d_tout.ensure(n1));
-	RC_TRY(b->d_dstoff.ensure(n1 + 2 * (size_t) finalize_blocks(n)));      /* ... + launch_finalize's per-block sums behind the n offsets */
-	RC_TRY(b->d_lists.ensure(2 * n1));             /* fill lists + backtrack order */
-	if (b->d_counters.cap < 64) {
-		RC_TRY(b->d_counters.ensure(64));
-		HIP_TRY(hipMemset(b->d_counters.p, 0, b->d_counters.cap * sizeof(int32_t)));
-	}
-	RC_TRY(b->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
+	RC_TRY(ensure_tile_records(b, n));
 	if (n) memcpy(b->h_tin.p, tin.data(), (size_t) n * sizeof(TileIn));
 
 	/* which bytes travel when, and from where: build_upload_schedule (cvx_host_logic.h); here only its questions to the
@@ -315,14 +245,9 @@ int stage_plan(cvx_context *h, cvx_batch_s *b, hipStream_t st) {
 }
 
 /* ---- stage 3's helpers */
-/* the sequence arena a batch's kernels read: a later rung of a ladder job reads rung 1's sequences where they lie */
-const uint8_t *batch_seq(const cvx_batch_s *b) { return b->ladder_root ? b->ladder_root->d_seq.p : b->d_seq.p; }
-
-int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m, bool inline_);
-
 /* the kernels' arguments of a batch; a fill launch adds its own list, chain fields and priority */
 void kernel_args(const cvx_context *h, const cvx_batch_s *b, const ChainBlk *chain_blk, FillArgs &a, BacktrackArgs &ba) {
-	a.seq = ba.seq = batch_seq(b);
+	a.seq = ba.seq = b->seq();
 	a.rows = ba.rows = reinterpret_cast<const RowDesc2 *>(b->d_rows.p);
 	a.rsrc = ba.rsrc = b->d_rsrc.p;
 	a.tin = ba.tin = b->d_tin.p;
@@ -385,159 +310,31 @@ int upload_chain(cvx_batch_s *b, const HostPlan &hp, const ComputeSchedule &sch,
 	return CVX_OK;
 }
 
-/* regions the dense arena of a job's low-identity regions is first sized for: a 10 kb PacBio tile has four or five */
-static const uint64_t kJobRegionsPerTile = 8;
-
-/* A CVX_CREATE_NM_REGIONS handle: the peak finder of detectMisalignment over the batch's op lists (cvx_text.hip), queued on `st`
- * behind the compaction with no host step in between -- count + stage per tile, the offset scan, then the write into an arena
- * sized by an estimate, the way finalize and compact treat the dense ops.  Offsets, total, the capacity the write ran with and
- * the end states travel in the copies queued here, in front of the event stage_results waits for; the regions themselves with
- * the dense ops (stage_ops).  rewrite: the arena has grown, only the write runs again. */
-int queue_job_regions(cvx_batch_s *b, hipStream_t st, bool rewrite) {
-	const int n = b->n;
-	const size_t n1 = (size_t) n;
-	TextArgs a;
-	memset(&a, 0, sizeof(a));
-	a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
-	a.n_tiles = n;
-	if (!rewrite) {
-		RC_TRY(b->d_jroff.ensure(2 * n1 + 8));
-		RC_TRY(b->d_jropen.ensure(n1));
-		RC_TRY(b->d_jrstage.ensure(n1 * (size_t) kNmStage));
-		RC_TRY(b->d_jrreg.ensure((size_t) (kJobRegionsPerTile * n1) + 64));
-		RC_TRY(b->h_jroff.ensure((n1 + 2) * sizeof(unsigned long long)));
-		RC_TRY(b->h_jropen.ensure(n1 * sizeof(NmOpen)));
-		b->jr_cap = b->d_jrreg.cap;
-		b->jr_rewrites = 0;
-	}
-	unsigned long long *d_len = b->d_jroff.p, *d_off = b->d_jroff.p + n1, *d_total = d_off + n1;
-	if (!rewrite) HIP_TRY(launch_nm_regions_count(a, 0, n, d_len, d_off, d_total, b->d_jropen.p, b->d_jrstage.p, st));
-	HIP_TRY(launch_nm_regions_bounded(a, n, d_len, d_off, d_total, b->d_jrstage.p, b->d_jrreg.p, b->jr_cap, st));
-	if (b->jc_on) {
-		/* the checks of whatever the write has just put into the arena, behind it on the same stream: the total is the device's
-		 * (d_off[n], right behind the offsets), so the first launch covers the arena; a rewrite knows it and runs over the grown
-		 * arena again, all records */
-		RC_TRY(b->d_jrchk.ensure((size_t) b->jr_cap));
-		InvCheckArgs c;
-		memset(&c, 0, sizeof(c));
-		c.bin = b->jc_bin; c.L = b->jc_L;
-		c.seq = batch_seq(b); c.tin = b->d_tin.p; c.win = b->d_win.p;      /* (a later rung's d_win: gathered by ladder_next_kernel) */
-		c.rec = reinterpret_cast<const ResultRec *>(b->d_res.p);
-		c.off = d_off; c.regions = b->d_jrreg.p; c.checks = b->d_jrchk.p;
-		c.cap = b->jr_cap; c.n_tiles = n;
-		HIP_TRY(launch_inv_checks(c, rewrite ? std::min<unsigned long long>(b->jr_total, b->jr_cap) : b->jr_cap, st));
-	}
-	if (!rewrite) {
-		HIP_TRY(hipMemcpyAsync(b->h_jroff.p, d_off, (n1 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(b->h_jropen.p, b->d_jropen.p, n1 * sizeof(NmOpen), hipMemcpyDeviceToHost, st));
-	}
+/* a job without tiles: one zero offset per result stage, and the stage's events on the streams a job's kernels would have run on */
+int compute_empty(cvx_context *h, cvx_batch_s *b, hipStream_t S_main, hipStream_t S_post) {
+	if (b->jt.on) RC_TRY(b->jt.set_empty());
+	if (b->jr.on) RC_TRY(b->jr.set_empty());
+	HIP_TRY(hipEventRecord(b->ev[4], S_main));
+	hipStream_t ps = h->overlap_post ? S_post : S_main;
+	HIP_TRY(hipStreamWaitEvent(ps, b->ev[4], 0));
+	HIP_TRY(hipEventRecord(b->ev[2], ps));
+	HIP_TRY(hipEventRecord(b->ev[3], ps));
+	HIP_TRY(hipEventRecord(b->ev_res, ps));
+	b->state = kComputed;
 	return CVX_OK;
 }
 
-/* A CVX_CREATE_JOB_TEXT handle: the device text stage over the batch's op lists and its sequences in HBM (cvx_text.hip), external
- * clips zero, queued on `st` behind the compaction with no host step in between -- the size pass, the offset scan, then the write
- * into an arena sized by an estimate (job_text_first_capacity over the job's read rows; tune: CVX_TUNE_JOB_TEXT_CAP).  Records,
- * offsets, total and the capacity the write ran with travel in the copies queued here, in front of the event stage_results
- * waits for; the strings themselves with the dense ops (stage_ops).  rewrite: the arena has grown, only the write runs again. */
-int queue_job_text(cvx_batch_s *b, hipStream_t st, bool rewrite, uint64_t tune = 0) {
-	const int n = b->n;
-	const size_t n1 = (size_t) n;
-	if (!rewrite) {
-		RC_TRY(b->d_jtrec.ensure(n1));
-		RC_TRY(b->d_jtoff.ensure(2 * n1 + 8));
-		RC_TRY(b->d_jtext.ensure((size_t) job_text_first_capacity(b->n_rows, (uint64_t) n, tune)));
-		RC_TRY(b->h_jtrec.ensure(n1 * sizeof(TextRec)));
-		RC_TRY(b->h_jtoff.ensure((n1 + 2) * sizeof(unsigned long long)));
-		b->jt_cap = b->d_jtext.cap;      /* (a slot's arena never shrinks: a job the arena already holds needs no estimate) */
-		b->jt_rewrites = 0;
-	}
-	TextArgs a;
-	memset(&a, 0, sizeof(a));
-	a.seq = batch_seq(b); a.tin = b->d_tin.p; a.trun = b->d_trun.p; a.tout = b->d_tout.p; a.ops = b->d_regions.p;
-	a.recs = b->d_jtrec.p;
-	a.text_len = b->d_jtoff.p; a.text_off = b->d_jtoff.p + n1; a.text_total = b->d_jtoff.p + 2 * n1;
-	a.text = b->d_jtext.p;
-	a.n_tiles = n;
-	if (!rewrite) HIP_TRY(launch_job_text_size(a, st));
-	HIP_TRY(launch_job_text_bounded(a, b->jt_cap, st));
-	if (!rewrite) {
-		HIP_TRY(hipMemcpyAsync(b->h_jtoff.p, a.text_off, (n1 + 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(b->h_jtrec.p, b->d_jtrec.p, n1 * sizeof(TextRec), hipMemcpyDeviceToHost, st));
-	}
-	return CVX_OK;
-}
-
-/* ---- stage 3: host planning, then every kernel of the batch on `main` (+ aux); nothing waits */
-int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
-	const int n = b->n;
-	if (h->test_fail_compute > 0 && --h->test_fail_compute == 0) {      /* test knob: this job fails before anything is queued for it */
-		set_err("stage_compute: failure injected by CVX_TUNE_FAIL_COMPUTE");
-		return CVX_ERR_OOM;
-	}
-	/* which stream set carries this batch's kernels (see cvx_context::s_main2) */
-	const bool second = streaming && n > 0 && n < kSmallJobTiles && !h->single_lane && ((h->small_jobs++ & 1u) != 0u);
-	hipStream_t const S_main = second ? h->s_main2 : h->s_main;
-	hipStream_t const S_post = second ? h->s_post2 : h->s_post;
-	hipStream_t const *S_aux = second ? h->aux2 : h->aux;
-	b->s_run = S_main;
-	hipStream_t st = S_main;
-	HIP_TRY(hipEventSynchronize(b->ev_in));        /* queued a whole batch ago in the streaming case */
-	b->launches.clear();
-	b->launch_tail.clear();
-	b->ops_total = 0;
-	b->have_ops = false;
-	b->jr_on = h->nm_regions;
-	b->jr_total = 0;
-	b->jc_on = b->jr_on && b->jc_bin != nullptr && n > 0;
-	b->jt_on = h->job_text;
-	b->jt_total = 0;
-	if (n == 0) {
-		if (b->jt_on) {      /* cvx_job_texts of an empty job: one offset, 0 */
-			RC_TRY(b->h_jtoff.ensure(2 * sizeof(unsigned long long)));
-			memset(b->h_jtoff.p, 0, 2 * sizeof(unsigned long long));
-			b->jt_cap = 0; b->jt_rewrites = 0;
-		}
-		if (b->jr_on) {      /* cvx_job_regions of an empty job: one offset, 0 */
-			RC_TRY(b->h_jroff.ensure(2 * sizeof(unsigned long long)));
-			memset(b->h_jroff.p, 0, 2 * sizeof(unsigned long long));
-		}
-		HIP_TRY(hipEventRecord(b->ev[4], st));
-		hipStream_t ps = h->overlap_post ? S_post : S_main;
-		HIP_TRY(hipStreamWaitEvent(ps, b->ev[4], 0));
-		HIP_TRY(hipEventRecord(b->ev[2], ps));
-		HIP_TRY(hipEventRecord(b->ev[3], ps));
-		HIP_TRY(hipEventRecord(b->ev_res, ps));
-		b->state = kComputed;
-		return CVX_OK;
-	}
-
-	/* host planning: kernel class, arena offsets, work lists, then the launch schedule (cvx_host_logic.h) */
-	HostPlan hp;
+/* the handle's knobs as the host planning (host_plan_rows) and the launch schedule (build_schedule) take them */
+PlanTuning plan_tuning(const cvx_context *h) {
 	PlanTuning tune;
 	tune.min_slots = h->tune_min_slots; tune.max_slots = h->tune_max_slots; tune.force_wrap = h->tune_force_wrap; tune.chain_m = h->tune_chain_m;
 	tune.force_generic = h->force_generic ? 1 : 0;
 	tune.long_steps = h->tune_long_steps; tune.small_batch = h->tune_small_batch; tune.long_need = h->tune_long_need;
 	tune.no_gangs = h->tune_gangs ? 0 : 1;
-	/* (a tile that gets chained needs its rows on the host: rebuilt from the step stream the batch still owns) */
-	const RowSrc *rsrc = b->h_rsrc.as<RowSrc>();
-	host_plan_rows(n, b->plan(), b->tin(), [&](int i, std::vector<RowDesc> &tmp) -> const RowDesc * {
-		tmp.resize((size_t) std::max(b->tin()[(size_t) i].H, 1));
-		expand_rows_host(rsrc[(size_t) i], b->tin()[(size_t) i].H, b->h_delta.as<uint8_t>(), b->h_rowsx.as<RowDesc>(), tmp.data());
-		return tmp.data();
-	}, true, tune, hp);
-	const std::vector<int32_t> &generic = hp.generic;
-	RC_TRY(b->d_dirs.ensure((size_t) hp.dir_dwords + 64));
-	RC_TRY(b->d_regions.ensure((size_t) hp.ops_ints + 64));
-	/* dense ops arena: an alignment of H read bases has far fewer than H run-length ops (about
-	 * 0.3 H at 15 % error); if a batch ever needs more, finalize reports it and stage_ops
-	 * compacts again into a larger arena */
-	b->dense_cap = std::min<uint64_t>(hp.ops_ints, hp.ops_ints / 3 + 64ull * (uint64_t) n);
-	RC_TRY(b->d_dense.ensure((size_t) b->dense_cap + 64));
-	b->dense_cap = std::max<uint64_t>(b->dense_cap, b->d_dense.cap - 64);
+	return tune;
+}
 
-	RC_TRY(b->h_trun.ensure((size_t) n * sizeof(TileRun)));
-	RC_TRY(b->h_tout.ensure((size_t) n * sizeof(TileOut)));
-	RC_TRY(b->h_lists.ensure((size_t) 2 * n * sizeof(int32_t) + 64));
+ScheduleTuning schedule_tuning(cvx_context *h, const HostPlan &hp) {
 	ScheduleTuning stune;
 	stune.exact_steps = h->tune_exact_steps; stune.bt_group = h->bt_group; stune.bt_per_class = h->bt_per_class; stune.overlap_post = h->overlap_post;
 	stune.wide_prio = h->tune_wide_prio; stune.gang_prio = h->tune_gang_prio; stune.chain_prio = h->tune_chain_prio; stune.chain_lds_kb = h->tune_chain_lds_kb;
@@ -552,20 +349,159 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 			stune.tail_waves_per_simd[c] = std::max(0, h->fill_waves[c]);
 		}
 	}
+	return stune;
+}
+
+/* the tiles the catch-all kernel takes: where each one's slot state lies in the scratch arena, on `st` */
+int upload_generic_scratch(cvx_batch_s *b, const HostPlan &hp, hipStream_t st) {
+	const std::vector<int32_t> &generic = hp.generic;
+	if (generic.empty()) return CVX_OK;
+	RC_TRY(b->h_goff.ensure((generic.size() + 1) * sizeof(uint64_t)));
+	uint64_t *goff = b->h_goff.as<uint64_t>();
+	goff[0] = 0;
+	for (size_t g = 0; g < generic.size(); ++g)
+		goff[g + 1] = goff[g] + (uint64_t) generic_scratch_bytes(hp.trun[(size_t) generic[g]].ring);
+	RC_TRY(b->d_gscratch.ensure((size_t) goff[generic.size()] + 256));
+	RC_TRY(b->d_gscratch_off.ensure(generic.size() + 1));
+	HIP_TRY(hipMemcpyAsync(b->d_gscratch_off.p, goff, (generic.size() + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+	return CVX_OK;
+}
+
+/* one fill launch of the schedule on its stream `ls`, between its events `le` (LaunchEvent): behind the input copies the kernels of
+ * its kind -- a split class's tail beside them on the handle's low-priority stream -- and, when every class is walked behind its own
+ * fill, its walk */
+int issue_fill_launch(cvx_context *h, cvx_batch_s *b, const ComputeSchedule &sch, const FillLaunch &L, const Event *le,
+		const FillArgs &fa, const BacktrackArgs &ba, hipStream_t ls) {
+	const bool wrap = L.wrap != 0;
+	HIP_TRY(hipStreamWaitEvent(ls, b->ev[4], 0));
+	HIP_TRY(hipEventRecord(le[kLevStart], ls));
+	FillArgs a = fa;
+	a.chain_prio = L.prio;
+	if (L.kind == CVX_LAUNCH_CHAINED) {
+		a.list_n = L.count;
+		a.tasks = reinterpret_cast<const ChainTask *>(b->d_chain.p + sch.chain_task_off[L.slot]);
+		a.chain_ticket = b->d_counters.p + 8 + L.slot;
+		a.bnd = b->d_bnd.p;
+		a.bnd_epoch = b->bnd_epoch;
+		a.chain_out = b->d_chain_out.p;
+		HIP_TRY(launch_fill(L.m, 1, wrap, kModeChain, a, L.pad_lds, ls));
+		HIP_TRY(launch_chain_reduce(reinterpret_cast<const int32_t *>(b->d_chain.p + sch.chain_tile_off[L.slot]), L.info.n_tiles,
+				b->d_trun.p, b->d_chain_out.p, b->d_tout.p, ls));
+		HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+	} else if (L.kind == CVX_LAUNCH_CATCH_ALL) {
+		a.list = b->d_lists.p + L.list_off;
+		a.list_n = L.count;
+		HIP_TRY(launch_fill_generic(a, h->sse_variant, b->d_gscratch.p, b->d_gscratch_off.p, ls));
+		HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+	} else {
+		/* the very long tiles of the class, exact from the first step (flagged kPadRedo), before everything else */
+		a.list = b->d_lists.p + L.list_off;
+		a.list_n = L.n_direct;
+		if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
+		a.list += L.n_direct;
+		a.list_n = L.count - L.n_direct - L.tail_count;      /* (a split class: the head; its tail follows below) */
+		if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, a, 0, ls));
+		HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
+		/* exact-tracking pass over the tiles the two-phase pass flagged (usually none) */
+		if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
+		if (L.tail_count > 0) {
+			/* The tail of a split class: the same two passes over the last tail_count entries of the class's list, on the low-priority
+			 * stream behind the input copies.  The device takes its workgroups where the head's launch leaves wave slots free -- from
+			 * the moment the head has nothing left to dispatch -- and while the tail drains, the head's walk (below, on `ls`) has
+			 * the issue slots the tail no longer uses.  Streams, events and queue priority order all of it; the kernels are the
+			 * head's and know nothing of the split.  (The flag the exact pass reads is per tile and redo_count is a statistic: the
+			 * head's exact pass may run beside the tail's two-phase pass.)
+			 * The tail waits for the head's START event, not just for the inputs: both streams would otherwise leave the same
+			 * barrier at the same moment, and in most batches the tail's workgroups -- exactly one resident round -- were then
+			 * dispatched first and the head filled in behind them (the tail's start event 0.02 ms BEFORE the head's in two batches
+			 * of three, the step 116.3 ms instead of 114.6; profiles/r16_tail_split.txt).  Behind the start event the head's
+			 * dispatch is already under way when the low-priority queue is looked at, and the tail begins one tile's duration
+			 * before the head ends, every time.  CVX_TUNE_TAIL_GATE=0: the inputs only. */
+			FillArgs ta = a;
+			ta.list = a.list + a.list_n;
+			ta.list_n = L.tail_count;
+			HIP_TRY(hipStreamWaitEvent(h->s_tail, h->tail_gate ? le[kLevStart] : b->ev[4], 0));
+			HIP_TRY(hipEventRecord(le[kLevTailStart], h->s_tail));
+			HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, ta, 0, h->s_tail));
+			HIP_TRY(hipEventRecord(le[kLevTailTwoPhase], h->s_tail));
+			HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, ta, 0, h->s_tail));
+			HIP_TRY(hipEventRecord(le[kLevTailExact], h->s_tail));
+		}
+	}
+	HIP_TRY(hipEventRecord(le[kLevExact], ls));
+	if (sch.per_class) {
+		const int n_head = L.bt_count - L.bt_tail_count;
+		RC_TRY(issue_walk(b, ba, L.walk, L.bt_off, n_head, ls, nullptr));
+		if (L.tail_count > 0) {
+			/* the tail's walk behind the tail's fill, on `ls`: whatever is queued on `ls` after this launch -- the next batch's fill --
+			 * stays behind all of this batch's class */
+			HIP_TRY(hipStreamWaitEvent(ls, le[kLevTailExact], 0));
+			RC_TRY(issue_walk(b, ba, L.walk_tail, L.bt_off + (size_t) n_head, L.bt_tail_count, ls, nullptr));
+		}
+	}
+	HIP_TRY(hipEventRecord(le[kLevWalked], ls));      /* what everything after the fills waits for */
+	return CVX_OK;
+}
+
+}  // namespace
+
+/* ---- stage 3: host planning, then every kernel of the batch on `main` (+ aux); nothing waits.  In order:
+ *   the stream set, the wait for the plan records, the run's fresh state and the result stages the handle asks for
+ *   (an empty job ends here: compute_empty)
+ *   host planning and the launch schedule (cvx_host_logic.h), the arenas sized by them
+ *   the input copies on `main`: catch-all scratch offsets, chain tables, TileRun / TileOut, the lists; event 4
+ *   the fill launches as scheduled (issue_fill_launch), each with its own events
+ *   the join on `main` (or `post`); event 2
+ *   the walk (unless every class had its own), finalize, compaction
+ *   a ladder job's next rung, in front of the result stages when there are any; the regions and the text; event 3
+ *   the result records to the host; ev_res */
+int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming) {
+	const int n = b->n;
+	if (h->test_fail_compute > 0 && --h->test_fail_compute == 0) {      /* test knob: this job fails before anything is queued for it */
+		set_err("stage_compute: failure injected by CVX_TUNE_FAIL_COMPUTE");
+		return CVX_ERR_OOM;
+	}
+	/* which stream set carries this batch's kernels (see cvx_context::s_main2) */
+	const bool second = streaming && n > 0 && n < kSmallJobTiles && !h->single_lane && ((h->small_jobs++ & 1u) != 0u);
+	hipStream_t const S_main = second ? h->s_main2 : h->s_main;
+	hipStream_t const S_post = second ? h->s_post2 : h->s_post;
+	hipStream_t const *S_aux = second ? h->aux2 : h->aux;
+	b->s_run = S_main;
+	hipStream_t st = S_main;
+	HIP_TRY(hipEventSynchronize(b->ev_in));        /* queued a whole batch ago in the streaming case */
+	b->begin_run();
+	b->jr.on = h->nm_regions;
+	b->jr.checks_on = b->jr.on && b->jr.bin != nullptr && n > 0;
+	b->jt.on = h->job_text;
+	if (n == 0) return compute_empty(h, b, S_main, S_post);
+
+	/* host planning: kernel class, arena offsets, work lists, then the launch schedule (cvx_host_logic.h) */
+	HostPlan hp;
+	const PlanTuning tune = plan_tuning(h);
+	/* (a tile that gets chained needs its rows on the host: rebuilt from the step stream the batch still owns) */
+	const RowSrc *rsrc = b->h_rsrc.as<RowSrc>();
+	host_plan_rows(n, b->plan(), b->tin(), [&](int i, std::vector<RowDesc> &tmp) -> const RowDesc * {
+		tmp.resize((size_t) std::max(b->tin()[(size_t) i].H, 1));
+		expand_rows_host(rsrc[(size_t) i], b->tin()[(size_t) i].H, b->h_delta.as<uint8_t>(), b->h_rowsx.as<RowDesc>(), tmp.data());
+		return tmp.data();
+	}, true, tune, hp);
+	RC_TRY(b->d_dirs.ensure((size_t) hp.dir_dwords + 64));
+	RC_TRY(b->d_regions.ensure((size_t) hp.ops_ints + 64));
+	/* dense ops arena: an alignment of H read bases has far fewer than H run-length ops (about
+	 * 0.3 H at 15 % error); if a batch ever needs more, finalize reports it and stage_ops
+	 * compacts again into a larger arena */
+	b->dense_cap = std::min<uint64_t>(hp.ops_ints, hp.ops_ints / 3 + 64ull * (uint64_t) n);
+	RC_TRY(b->d_dense.ensure((size_t) b->dense_cap + 64));
+	b->dense_cap = std::max<uint64_t>(b->dense_cap, b->d_dense.cap - 64);
+
+	RC_TRY(b->h_trun.ensure((size_t) n * sizeof(TileRun)));
+	RC_TRY(b->h_tout.ensure((size_t) n * sizeof(TileOut)));
+	RC_TRY(b->h_lists.ensure((size_t) 2 * n * sizeof(int32_t) + 64));
 	ComputeSchedule sch;
-	build_schedule(hp, b->plan(), b->tin(), n, b->n_rows, h->num_cus, stune, b->h_lists.as<int32_t>(), sch);
+	build_schedule(hp, b->plan(), b->tin(), n, b->n_rows, h->num_cus, schedule_tuning(h, hp), b->h_lists.as<int32_t>(), sch);
 	memcpy(b->h_trun.p, hp.trun.data(), (size_t) n * sizeof(TileRun));
 	memcpy(b->h_tout.p, hp.tout.data(), (size_t) n * sizeof(TileOut));      /* (with the direct-exact tiles flagged kPadRedo) */
-	if (!generic.empty()) {
-		RC_TRY(b->h_goff.ensure((generic.size() + 1) * sizeof(uint64_t)));
-		uint64_t *goff = b->h_goff.as<uint64_t>();
-		goff[0] = 0;
-		for (size_t g = 0; g < generic.size(); ++g)
-			goff[g + 1] = goff[g] + (uint64_t) generic_scratch_bytes(hp.trun[(size_t) generic[g]].ring);
-		RC_TRY(b->d_gscratch.ensure((size_t) goff[generic.size()] + 256));
-		RC_TRY(b->d_gscratch_off.ensure(generic.size() + 1));
-		HIP_TRY(hipMemcpyAsync(b->d_gscratch_off.p, goff, (generic.size() + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-	}
+	RC_TRY(upload_generic_scratch(b, hp, st));
 	if (hp.n_chained) RC_TRY(upload_chain(b, hp, sch, st));
 	HIP_TRY(hipMemcpyAsync(b->d_trun.p, b->h_trun.p, (size_t) n * sizeof(TileRun), hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemcpyAsync(b->d_tout.p, b->h_tout.p, (size_t) n * sizeof(TileOut), hipMemcpyHostToDevice, st));
@@ -590,78 +526,9 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	}
 	for (int i = 0; i < launches; ++i) {
 		const FillLaunch &L = sch.launches[(size_t) i];
-		const hipStream_t ls = fill_streams[L.stream];
-		const Event *le = &b->lev[(size_t) i * kLevPerLaunch];
-		const bool wrap = L.wrap != 0;
 		b->launches.push_back(L.info);
 		b->launch_tail.push_back(L.tail_count);
-		HIP_TRY(hipStreamWaitEvent(ls, b->ev[4], 0));
-		HIP_TRY(hipEventRecord(le[kLevStart], ls));
-		FillArgs a = fa;
-		a.chain_prio = L.prio;
-		if (L.kind == CVX_LAUNCH_CHAINED) {
-			a.list_n = L.count;
-			a.tasks = reinterpret_cast<const ChainTask *>(b->d_chain.p + sch.chain_task_off[L.slot]);
-			a.chain_ticket = b->d_counters.p + 8 + L.slot;
-			a.bnd = b->d_bnd.p;
-			a.bnd_epoch = b->bnd_epoch;
-			a.chain_out = b->d_chain_out.p;
-			HIP_TRY(launch_fill(L.m, 1, wrap, kModeChain, a, L.pad_lds, ls));
-			HIP_TRY(launch_chain_reduce(reinterpret_cast<const int32_t *>(b->d_chain.p + sch.chain_tile_off[L.slot]), L.info.n_tiles,
-					b->d_trun.p, b->d_chain_out.p, b->d_tout.p, ls));
-			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
-		} else if (L.kind == CVX_LAUNCH_CATCH_ALL) {
-			a.list = b->d_lists.p + L.list_off;
-			a.list_n = L.count;
-			HIP_TRY(launch_fill_generic(a, h->sse_variant, b->d_gscratch.p, b->d_gscratch_off.p, ls));
-			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
-		} else {
-			/* the very long tiles of the class, exact from the first step (flagged kPadRedo), before everything else */
-			a.list = b->d_lists.p + L.list_off;
-			a.list_n = L.n_direct;
-			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
-			a.list += L.n_direct;
-			a.list_n = L.count - L.n_direct - L.tail_count;      /* (a split class: the head; its tail follows below) */
-			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, a, 0, ls));
-			HIP_TRY(hipEventRecord(le[kLevTwoPhase], ls));
-			/* exact-tracking pass over the tiles the two-phase pass flagged (usually none) */
-			if (a.list_n > 0) HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, a, 0, ls));
-			if (L.tail_count > 0) {
-				/* The tail of a split class: the same two passes over the last tail_count entries of the class's list, on the low-priority
-				 * stream behind the input copies.  The device takes its workgroups where the head's launch leaves wave slots free -- from
-				 * the moment the head has nothing left to dispatch -- and while the tail drains, the head's walk (below, on `ls`) has
-				 * the issue slots the tail no longer uses.  Streams, events and queue priority order all of it; the kernels are the
-				 * head's and know nothing of the split.  (The flag the exact pass reads is per tile and redo_count is a statistic: the
-				 * head's exact pass may run beside the tail's two-phase pass.)
-				 * The tail waits for the head's START event, not just for the inputs: both streams would otherwise leave the same
-				 * barrier at the same moment, and in most batches the tail's workgroups -- exactly one resident round -- were then
-				 * dispatched first and the head filled in behind them (the tail's start event 0.02 ms BEFORE the head's in two batches
-				 * of three, the step 116.3 ms instead of 114.6; profiles/r16_tail_split.txt).  Behind the start event the head's
-				 * dispatch is already under way when the low-priority queue is looked at, and the tail begins one tile's duration
-				 * before the head ends, every time.  CVX_TUNE_TAIL_GATE=0: the inputs only. */
-				FillArgs ta = a;
-				ta.list = a.list + a.list_n;
-				ta.list_n = L.tail_count;
-				HIP_TRY(hipStreamWaitEvent(h->s_tail, h->tail_gate ? le[kLevStart] : b->ev[4], 0));
-				HIP_TRY(hipEventRecord(le[kLevTailStart], h->s_tail));
-				HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeTwoPhase, ta, 0, h->s_tail));
-				HIP_TRY(hipEventRecord(le[kLevTailTwoPhase], h->s_tail));
-				HIP_TRY(launch_fill(L.m, L.gang, wrap, kModeExact, ta, 0, h->s_tail));
-				HIP_TRY(hipEventRecord(le[kLevTailExact], h->s_tail));
-			}
-		}
-		HIP_TRY(hipEventRecord(le[kLevExact], ls));
-		if (sch.per_class) {
-			const int n_head = L.bt_count - L.bt_tail_count;
-			RC_TRY(issue_walk(b, ba, L.walk, L.bt_off, n_head, ls, nullptr));
-			if (L.tail_count > 0) {
-				/* the tail's walk behind the tail's fill, on `ls`: whatever is queued on `ls` after this launch -- the next batch's fill --
-				 * stays behind all of this batch's class */
-				HIP_TRY(hipStreamWaitEvent(ls, le[kLevTailExact], 0));
-				RC_TRY(issue_walk(b, ba, L.walk_tail, L.bt_off + (size_t) n_head, L.bt_tail_count, ls, nullptr));
-			}
-		}
-		HIP_TRY(hipEventRecord(le[kLevWalked], ls));      /* what everything after the fills waits for */
+		RC_TRY(issue_fill_launch(h, b, sch, L, &b->lev[(size_t) i * kLevPerLaunch], fa, ba, fill_streams[L.stream]));
 	}
 	/* Everything after the fills CAN run on its own stream, so that `main` goes straight on to the next
 	 * batch's fills while this batch's backtrack (one wave per tile) and small kernels run beside them. */
@@ -681,7 +548,7 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 	BatchSummary *d_sum = reinterpret_cast<BatchSummary *>(b->d_res.p + (size_t) n * sizeof(ResultRec));
 	HIP_TRY(launch_finalize(b->d_tout.p, b->d_plan.p, b->d_dstoff.p, b->d_dstoff.p + n, d_rec, d_sum, b->d_counters.p, n, b->dense_cap, st));
 	HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, n, b->dense_cap, st));
-	if (b->jr_on || b->jt_on) {
+	if (b->jr.on || b->jt.on) {
 		/* A rung of a ladder job whose handle runs stages behind the compaction: the climb reads result statuses only, so the
 		 * decision kernel, the next rung's plan and their read-back go in FRONT of this rung's regions, checks and text -- the
 		 * host has the next rung's plan in hand while the device still writes this rung's strings. */
@@ -691,8 +558,8 @@ int stage_compute(cvx_context *h, cvx_batch_s *b, bool streaming = false) {
 			RC_TRY(ladder_queue_next(h, root, b, (int) root->ladder->rungs.size(), true));
 		}
 	}
-	if (b->jr_on) RC_TRY(queue_job_regions(b, st, false));      /* (inside the compute stage's timing: ev[3] below) */
-	if (b->jt_on) RC_TRY(queue_job_text(b, st, false, h->tune_job_text_cap));      /* (as is this) */
+	if (b->jr.on) RC_TRY(b->jr.queue(b, st));      /* (inside the compute stage's timing: ev[3] below) */
+	if (b->jt.on) RC_TRY(b->jt.queue(b, st, false, h->tune_job_text_cap));      /* (as is this) */
 	HIP_TRY(hipEventRecord(b->ev[3], st));
 	HIP_TRY(hipMemcpyAsync(b->h_res.p, b->d_res.p, (size_t) n * sizeof(ResultRec) + sizeof(BatchSummary), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipEventRecord(b->ev_res, st));
@@ -714,14 +581,8 @@ int stage_results(cvx_context *h, cvx_batch_s *b) {
 	if (b->n == 0) { b->ops_total = 0; b->state = kFinished; return CVX_OK; }
 	const BatchSummary *s = b->summary();
 	b->ops_total = s->ops_total;
-	if (b->jr_on) b->jr_total = b->h_jroff.as<unsigned long long>()[(size_t) b->n];      /* (the total sits behind the n offsets) */
-	if (b->jt_on) {
-		b->jt_total = b->h_jtoff.as<unsigned long long>()[(size_t) b->n];
-		if (h->scalar_twin) {      /* Convex::ConvexAlign stores neither field (cvx_job_text does the same to its copy) */
-			TextRec *rec = b->h_jtrec.as<TextRec>();
-			for (int i = 0; i < b->n; ++i) { rec[i].cigar_op_count = CVX_NOT_WRITTEN; rec[i].sv_type = CVX_NOT_WRITTEN; }
-		}
-	}
+	b->jr.take_total(b->n);
+	b->jt.take_total(b->n, h->scalar_twin);
 	const int launches = b->timing.n_fill_launches;
 	for (int i = 0; i < launches; ++i) {
 		const Event *le = &b->lev[(size_t) i * kLevPerLaunch];
@@ -768,42 +629,9 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 		HIP_TRY(launch_compact(b->d_regions.p, b->d_trun.p, b->d_tout.p, b->d_dstoff.p, b->d_dense.p, b->n, b->dense_cap, ps));
 		HIP_TRY(hipStreamSynchronize(ps));
 	}
-	if (b->jr_on && b->jr_total > b->jr_cap) {
-		/* as rare: more regions than eight per tile -- a larger arena, and the write alone runs again (counts, offsets and the
-		 * staged regions are still the job's) */
-		RC_TRY(b->d_jrreg.ensure((size_t) b->jr_total + 64));
-		b->jr_cap = b->d_jrreg.cap;
-		b->jr_rewrites += 1;
-		hipStream_t ps = b->s_run ? b->s_run : h->s_main;
-		RC_TRY(queue_job_regions(b, ps, true));
-		HIP_TRY(hipStreamSynchronize(ps));
-	}
-	if (b->jr_on && b->jr_total) {
-		/* the regions ride in front of the dense ops, under the one wait below (a job with regions has ops) */
-		RC_TRY(b->h_jrreg.ensure((size_t) b->jr_total * sizeof(NmRegion)));
-		HIP_TRY(hipMemcpyAsync(b->h_jrreg.p, b->d_jrreg.p, (size_t) b->jr_total * sizeof(NmRegion), hipMemcpyDeviceToHost, h->s_io));
-		if (b->jc_on) {      /* ... and their checks beside them */
-			RC_TRY(b->h_jrchk.ensure((size_t) b->jr_total * sizeof(InvCheck)));
-			HIP_TRY(hipMemcpyAsync(b->h_jrchk.p, b->d_jrchk.p, (size_t) b->jr_total * sizeof(InvCheck), hipMemcpyDeviceToHost, h->s_io));
-		}
-		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
-	}
-	if (b->jt_on && b->jt_total > b->jt_cap) {
-		/* more text than the estimate (sane reads stay below it: CVX_TUNE_JOB_TEXT_CAP reaches this) -- a larger arena, and the
-		 * write alone runs again: records, lengths and offsets are still the job's */
-		RC_TRY(b->d_jtext.ensure((size_t) b->jt_total));
-		b->jt_cap = b->d_jtext.cap;
-		b->jt_rewrites += 1;
-		hipStream_t ps = b->s_run ? b->s_run : h->s_main;
-		RC_TRY(queue_job_text(b, ps, true));
-		HIP_TRY(hipStreamSynchronize(ps));
-	}
-	if (b->jt_on && b->jt_total) {
-		/* the strings ride in front of the dense ops, under the one wait below (only a job without a valid tile has text and no ops) */
-		RC_TRY(b->h_jtext.ensure((size_t) b->jt_total));
-		HIP_TRY(hipMemcpyAsync(b->h_jtext.p, b->d_jtext.p, (size_t) b->jt_total, hipMemcpyDeviceToHost, h->s_io));
-		if (!b->ops_total) HIP_TRY(hipStreamSynchronize(h->s_io));
-	}
+	/* the result stages' arenas ride in front of the dense ops, under the one wait below */
+	RC_TRY(b->jr.fetch(h, b));
+	RC_TRY(b->jt.fetch(h, b));
 	if (b->ops_total) {
 		RC_TRY(b->h_ops.ensure((size_t) b->ops_total * sizeof(uint32_t)));
 		/* The wait below is for the whole io stream, on purpose: it already carries the upload and corridor analysis of the
@@ -822,252 +650,7 @@ int stage_ops(cvx_context *h, cvx_batch_s *b) {
 	return CVX_OK;
 }
 
-/* ---- ladder jobs (cvx_submit_ladder): a rung is the plan -> schedule -> fill -> walk -> records cycle of a job run again,
- * over the tiles ladder_next_kernel found climbing.  Rung r + 1 is a batch of its own from the handle's pool (its own plan,
- * lists, direction words, result block, ops: nothing of rung r is overwritten, so nothing has to wait for rung r's readers)
- * that reads rung 1's sequence arena.  Order: the kernel waits, on the device, for the event behind rung r's result records;
- * the host waits for nothing but the event behind the next rung's list and plan records -- queried from pump, blocking only
- * inside cvx_wait. */
-
-/* behind rung `prev` (rung m, computed) of `root`: the decision kernel, the plan of the tiles it lists, and list, tile records,
- * corridors and plan records on their way to the host; L->next is the batch they belong to */
-int ladder_queue_next(cvx_context *h, cvx_batch_s *root, cvx_batch_s *prev, int m, bool inline_) {
-	LadderState *L = root->ladder;
-	const int np = prev->n;
-	if (np <= 0 || m >= L->max_rungs) { L->done = true; return CVX_OK; }
-	cvx_batch_s *c = acquire_batch(h);
-	if (!c) { set_err("cvx_submit_ladder: no memory for rung %d", m + 1); return CVX_ERR_OOM; }
-	c->bind(h->marks);
-	c->n = 0; c->state = kEmpty; c->in_flight = false; c->have_ops = false; c->have_refs = false; c->text_done = false;
-	c->jr_on = c->jc_on = c->jt_on = false;      /* (the rung's compute stage sets them from the handle, like any job's) */
-	c->jc_bin = root->jc_bin; c->jc_L = root->jc_L;      /* the job's genome: the rung's regions get their checks */
-	c->ops_total = 0; c->seq_total = 0; c->n_rows = 0; c->n_rowsx = 0; c->zero_copy_bytes = 0;
-	memset(&c->timing, 0, sizeof(c->timing));
-	c->ladder_root = root;
-	L->next = c;      /* (from here on the batch leaves with the job, whatever fails) */
-	RC_TRY(c->make_events());
-	const size_t n1 = (size_t) np;
-	RC_TRY(c->h_rsrc.ensure(n1 * sizeof(RowSrc)));
-	RC_TRY(c->h_tin.ensure(n1 * sizeof(TileIn)));
-	RC_TRY(c->h_plan.ensure(n1 * sizeof(TilePlan)));
-	RC_TRY(c->h_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
-	RC_TRY(c->h_lhead.ensure((n1 + 1) * sizeof(int32_t)));
-	RC_TRY(c->d_lhead.ensure(n1 + 1));
-	RC_TRY(c->d_rsrc.ensure(n1));
-	RC_TRY(c->d_rows.ensure(1));      /* closed forms own no rows */
-	RC_TRY(c->d_tin.ensure(n1));
-	RC_TRY(c->d_plan.ensure(n1));
-	RC_TRY(c->d_trun.ensure(n1));
-	RC_TRY(c->d_tout.ensure(n1));
-	RC_TRY(c->d_dstoff.ensure(n1 + 2 * (size_t) finalize_blocks(np)));
-	RC_TRY(c->d_lists.ensure(2 * n1));
-	if (c->d_counters.cap < 64) {
-		RC_TRY(c->d_counters.ensure(64));
-		HIP_TRY(hipMemset(c->d_counters.p, 0, c->d_counters.cap * sizeof(int32_t)));
-	}
-	RC_TRY(c->d_res.ensure(n1 * sizeof(ResultRec) + sizeof(BatchSummary)));
-	if (c->jc_bin) RC_TRY(c->d_win.ensure(n1));
-	hipStream_t st = h->s_main;
-	/* rung m's records are final: behind their copy to the host, or (queued from inside rung m's compute stage, in front of its
-	 * stages) behind the event right behind the records and the compaction */
-	HIP_TRY(hipStreamWaitEvent(st, inline_ ? prev->ev_rec : prev->ev_res, 0));
-	LadderNextArgs a;
-	a.res = reinterpret_cast<const ResultRec *>(prev->d_res.p);
-	a.prev_idx = prev == root ? nullptr : prev->d_lhead.p + 1;
-	a.tin0 = root->d_tin.p;
-	a.lad = root->d_lad.p;
-	a.n_prev = np;
-	a.m = m;
-	a.rsrc = c->d_rsrc.p; a.tin = c->d_tin.p; a.head = c->d_lhead.p;
-	a.win0 = c->jc_bin ? root->d_win.p : nullptr;
-	a.win = c->jc_bin ? c->d_win.p : nullptr;
-	HIP_TRY(launch_ladder_next(a, st));
-	HIP_TRY(hipEventRecord(c->ev[0], st));
-	HIP_TRY(launch_plan(c->d_rows.p, c->d_rsrc.p, c->d_tin.p, c->d_plan.p, np, root->n ? root->n_rows / (uint64_t) root->n : 0, h->max_matrix_mb, st));
-	HIP_TRY(hipMemcpyAsync(c->h_plan.p, c->d_plan.p, n1 * sizeof(TilePlan), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(c->ev[1], st));
-	HIP_TRY(hipMemcpyAsync(c->h_lhead.p, c->d_lhead.p, (n1 + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(c->h_tin.p, c->d_tin.p, n1 * sizeof(TileIn), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(c->h_rsrc.p, c->d_rsrc.p, n1 * sizeof(RowSrc), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(c->ev_in, st));
-	c->state = kPlanned;
-	return CVX_OK;
-}
-
-/* the ladder of `root` as far as the device has answered (block: to its end); a failure is the job's */
-void ladder_advance(cvx_context *h, cvx_batch_s *root, bool block) {
-	LadderState *L = root->ladder;
-	while (root->state != kFailed && !L->done) {
-		int rc = CVX_OK;
-		if (!L->next) {
-			rc = ladder_queue_next(h, root, L->rungs.back(), (int) L->rungs.size(), false);
-			if (rc != CVX_OK) { (void) fail_job(root, rc); break; }
-			continue;
-		}
-		cvx_batch_s *c = L->next;
-		if (!block) {
-			hipError_t q = hipEventQuery(c->ev_in);
-			if (q == hipErrorNotReady) { (void) hipGetLastError(); return; }
-			if (q != hipSuccess) { set_err("hipEventQuery: %s", hipGetErrorString(q)); (void) fail_job(root, CVX_ERR_HIP); break; }
-		} else {
-			hipError_t q = hipEventSynchronize(c->ev_in);
-			if (q != hipSuccess) { set_err("hipEventSynchronize: %s", hipGetErrorString(q)); (void) fail_job(root, CVX_ERR_HIP); break; }
-		}
-		const int count = c->h_lhead.as<int32_t>()[0];
-		L->next = nullptr;
-		if (count <= 0) {      /* nobody climbs: the job ends (what was queued for the batch has run: its event is behind all of it) */
-			c->ladder_root = nullptr;
-			recycle_batch(h, c);
-			L->done = true;
-			break;
-		}
-		c->n = count;
-		c->n_rows = 0;
-		for (int i = 0; i < count; ++i) c->n_rows += (uint64_t) c->tin()[(size_t) i].H;
-		L->rungs.push_back(c);
-		rc = stage_compute(h, c, true);
-		if (rc != CVX_OK) { (void) fail_job(root, rc); break; }
-		if ((int) L->rungs.size() >= kLadderMaxRungs) L->done = true;
-	}
-	if (root->state == kFailed) L->done = true;
-	if (L->done) {
-		auto it = std::find(h->climbing.begin(), h->climbing.end(), root);
-		if (it != h->climbing.end()) h->climbing.erase(it);
-	}
-}
-
-/* every climbing job as far as it has come, without waiting */
-void ladder_pump(cvx_context *h) {
-	const std::vector<cvx_batch_s *> jobs = h->climbing;      /* (ladder_advance takes finished ladders off the list) */
-	for (cvx_batch_s *root : jobs) ladder_advance(h, root, false);
-}
-
-/* What the rungs' stages brought back (regions with their end states and checks, text records and strings; every rung's own
- * stage_results / stage_ops have run), merged for the job: per tile the reporting rung's, in tile order, offsets rebased into
- * one dense arena each (ladder_merge_plan, cvx_ladder_merge.h).  A twin handle's CVX_NOT_WRITTEN fields are already in every
- * rung's records (stage_results) and travel with them. */
-int ladder_merge_stages(cvx_batch_s *root, const std::vector<int32_t> &rung_of, const std::vector<int32_t> &at) {
-	LadderState *L = root->ladder;
-	const int n = root->n;
-	const int32_t n_rungs = (int32_t) L->rungs.size();
-	std::vector<const uint64_t *> off((size_t) n_rungs);
-	std::vector<const void *> rec((size_t) n_rungs);
-	std::vector<int32_t> rn((size_t) n_rungs);
-	std::vector<LadderSpan> spans;
-	for (int32_t r = 0; r < n_rungs; ++r) rn[(size_t) r] = L->rungs[(size_t) r]->n;
-	L->jr_rewrites = L->jt_rewrites = 0;
-	if (root->jr_on) {
-		for (int32_t r = 0; r < n_rungs; ++r) {
-			const cvx_batch_s *c = L->rungs[(size_t) r];
-			if (!c->jr_on) { set_err("internal: rung %d of a regions job ran without the finder", r + 1); return CVX_ERR_HIP; }
-			off[(size_t) r] = c->h_jroff.as<uint64_t>();
-			rec[(size_t) r] = c->h_jropen.p;
-			L->jr_rewrites += c->jr_rewrites;
-		}
-		L->jr_off.assign((size_t) n + 1, 0);
-		if (!ladder_merge_plan(n, rung_of.data(), at.data(), n_rungs, off.data(), rn.data(), L->jr_off.data(), spans)) {
-			set_err("internal: the region offsets of a ladder job's rungs do not merge");
-			return CVX_ERR_HIP;
-		}
-		const uint64_t total = L->jr_off[(size_t) n];
-		L->jr_reg.resize((size_t) total);
-		L->jr_chk.resize(root->jc_on ? (size_t) total : 0);
-		for (const LadderSpan &s : spans) {
-			const cvx_batch_s *c = L->rungs[(size_t) s.rung];
-			memcpy(L->jr_reg.data() + s.dst, c->h_jrreg.as<NmRegion>() + s.src, (size_t) s.len * sizeof(NmRegion));
-			if (root->jc_on) {
-				if (!c->jc_on) { set_err("internal: rung %d of a checks job ran without the checks", s.rung + 1); return CVX_ERR_HIP; }
-				memcpy(L->jr_chk.data() + s.dst, c->h_jrchk.as<InvCheck>() + s.src, (size_t) s.len * sizeof(InvCheck));
-			}
-		}
-		L->jr_open.resize((size_t) n);
-		ladder_merge_records(n, rung_of.data(), at.data(), rec.data(), sizeof(NmOpen), L->jr_open.data());
-	}
-	if (root->jt_on) {
-		for (int32_t r = 0; r < n_rungs; ++r) {
-			const cvx_batch_s *c = L->rungs[(size_t) r];
-			if (!c->jt_on) { set_err("internal: rung %d of a text job ran without the text stage", r + 1); return CVX_ERR_HIP; }
-			off[(size_t) r] = c->h_jtoff.as<uint64_t>();
-			rec[(size_t) r] = c->h_jtrec.p;
-			L->jt_rewrites += c->jt_rewrites;
-		}
-		L->jt_off.assign((size_t) n + 1, 0);
-		if (!ladder_merge_plan(n, rung_of.data(), at.data(), n_rungs, off.data(), rn.data(), L->jt_off.data(), spans)) {
-			set_err("internal: the text offsets of a ladder job's rungs do not merge");
-			return CVX_ERR_HIP;
-		}
-		L->jt_text.assign((size_t) L->jt_off[(size_t) n] + 1, '\0');
-		for (const LadderSpan &s : spans) memcpy(L->jt_text.data() + s.dst, L->rungs[(size_t) s.rung]->h_jtext.as<char>() + s.src, (size_t) s.len);
-		L->jt_rec.resize((size_t) n);
-		ladder_merge_records(n, rung_of.data(), at.data(), rec.data(), sizeof(TextRec), L->jt_rec.data());
-	}
-	return CVX_OK;
-}
-
-/* the job's answer, once its ladder is done: every rung's records and ops waited for, then merged on the host -- per tile the
- * record of the last rung it took part in, its ops copied into one arena in tile order (ops_begin rebased), the ladder record
- * beside it; timing summed, launches strung together */
-int ladder_finish(cvx_context *h, cvx_batch_s *root) {
-	LadderState *L = root->ladder;
-	if (L->merged) return CVX_OK;
-	for (cvx_batch_s *c : L->rungs) {
-		if (c->state < kFinished) RC_TRY(stage_results(h, c));
-		RC_TRY(stage_ops(h, c));
-	}
-	const int n = root->n;
-	const size_t n1 = (size_t) std::max(n, 1);
-	std::vector<int32_t> rung_of((size_t) n, 0), at((size_t) n);
-	for (int i = 0; i < n; ++i) at[(size_t) i] = i;
-	for (size_t r = 1; r < L->rungs.size(); ++r) {
-		const cvx_batch_s *c = L->rungs[r];
-		const int32_t *head = c->h_lhead.as<int32_t>();
-		for (int j = 0; j < c->n; ++j) {
-			const int32_t i = head[1 + j];
-			if (i < 0 || i >= n) { set_err("internal: rung %zu lists tile %d of %d", r + 1, i, n); return CVX_ERR_HIP; }
-			rung_of[(size_t) i] = (int32_t) r;
-			at[(size_t) i] = j;
-		}
-	}
-	uint64_t total = 0;
-	for (int i = 0; i < n; ++i) total += (uint64_t) L->rungs[(size_t) rung_of[(size_t) i]]->res()[at[(size_t) i]].n_ops;
-	RC_TRY(root->h_lres.ensure(n1 * sizeof(ResultRec)));
-	RC_TRY(root->h_lout.ensure(n1 * sizeof(cvx_ladder_result)));
-	RC_TRY(root->h_lops.ensure((size_t) std::max<uint64_t>(total, 1) * sizeof(uint32_t)));
-	ResultRec *res = root->h_lres.as<ResultRec>();
-	cvx_ladder_result *out = root->h_lout.as<cvx_ladder_result>();
-	uint32_t *ops = root->h_lops.as<uint32_t>();
-	const cvx_ladder *lad = root->h_lad.as<cvx_ladder>();
-	uint64_t used = 0;
-	for (int i = 0; i < n; ++i) {
-		const cvx_batch_s *c = L->rungs[(size_t) rung_of[(size_t) i]];
-		ResultRec r = c->res()[at[(size_t) i]];
-		if (r.n_ops > 0) memcpy(ops + used, c->h_ops.as<uint32_t>() + r.ops_begin, (size_t) r.n_ops * sizeof(uint32_t));
-		r.ops_begin = used;
-		used += (uint64_t) std::max(r.n_ops, 0);
-		res[i] = r;
-		const TileIn &ti = root->tin()[(size_t) i];
-		RowSrc f;
-		ladder_form(lad[i].corridor, lad[i].left, lad[i].right, lad[i].flags, ti.W, ti.H, rung_of[(size_t) i] + 1, f);
-		out[i].rung = out[i].attempts = rung_of[(size_t) i] + 1;
-		out[i].width = f.width;
-		out[i].reserved = 0;
-	}
-	L->ops_total = used;
-	RC_TRY(ladder_merge_stages(root, rung_of, at));
-	memset(&L->timing, 0, sizeof(L->timing));
-	L->launches.clear();
-	for (const cvx_batch_s *c : L->rungs) {
-		const cvx_timing &t = c->timing;
-		L->timing.plan_ms += t.plan_ms; L->timing.fill_ms += t.fill_ms; L->timing.backtrack_ms += t.backtrack_ms; L->timing.total_ms += t.total_ms;
-		L->timing.cells += t.cells; L->timing.active_cells += t.active_cells; L->timing.dir_bytes += t.dir_bytes;
-		L->timing.n_fill_launches += t.n_fill_launches; L->timing.n_tiles_fast += t.n_tiles_fast; L->timing.n_tiles_redone += t.n_tiles_redone;
-		L->timing.n_tiles_chained += t.n_tiles_chained;
-		L->timing.chain_task_ticks += t.chain_task_ticks; L->timing.chain_poll_ticks += t.chain_poll_ticks;
-		L->launches.insert(L->launches.end(), c->launches.begin(), c->launches.end());
-	}
-	L->merged = true;
-	return CVX_OK;
-}
+namespace {
 
 /* queue the compute stage of every submitted batch whose plan records have arrived (all of them,
  * up to `upto`, when `block`): keeps the device one batch ahead of the host */
@@ -1075,12 +658,10 @@ int pump(cvx_context *h, bool block, const cvx_batch_s *upto) {
 	if (!h->climbing.empty()) ladder_pump(h);
 	while (!h->pending.empty()) {
 		cvx_batch_s *b = h->pending.front();
-		if (!block) {
-			hipError_t q = hipEventQuery(b->ev_in);
-			if (q == hipErrorNotReady) { (void) hipGetLastError(); break; }
-			if (q != hipSuccess) { set_err("hipEventQuery: %s", hipGetErrorString(q)); h->pending.erase(h->pending.begin()); (void) fail_job(b, CVX_ERR_HIP); continue; }
-		}
+		const int fired = block ? 1 : event_fired(b->ev_in);
+		if (fired == 0) break;
 		h->pending.erase(h->pending.begin());
+		if (fired < 0) { (void) fail_job(b, CVX_ERR_HIP); continue; }
 		/* a failure (say, the direction arena of a multi-GB batch does not fit beside the batches in flight) belongs
 		 * to THIS job: it is recorded on it and reported by its own cvx_wait, never against another job's call */
 		const int rc = stage_compute(h, b, true);
@@ -1118,16 +699,6 @@ int stage_segments_plan(const char *who, int32_t n_reads, const uint8_t *arena, 
 }
 
 }  // namespace
-
-/* a ladder job is deleted (cvx_destroy, a failed submit): the later rungs' batches go back to the allocator with it */
-void ladder_drop(cvx_batch_s *root) {
-	LadderState *L = root->ladder;
-	root->ladder = nullptr;
-	if (!L) return;
-	if (L->next) L->rungs.push_back(L->next);
-	for (size_t r = 1; r < L->rungs.size(); ++r) delete L->rungs[r];
-	delete L;
-}
 
 extern "C" {
 
@@ -1267,10 +838,12 @@ int cvx_align_batch(cvx_handle h, int32_t n, const cvx_tile *tiles, cvx_result *
 	ABI_GUARD_END
 }
 
+}  /* extern "C" */
+
 /* ------------------------------------------------------------------ streaming form */
 
-static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const cvx_genome_s *genome, const uint64_t *ref_position, cvx_job *out,
-		const SegmentsIn *segs = nullptr, const cvx_ladder *ladders = nullptr, int max_rungs = 0) {
+int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const cvx_genome_s *genome, const uint64_t *ref_position, cvx_job *out,
+		const SegmentsIn *segs, const cvx_ladder *ladders, int max_rungs) {
 	if (!h || !out || n < 0 || (n > 0 && !tiles) || (genome && n > 0 && !ref_position)) { set_err("cvx_submit: bad argument"); return CVX_ERR_ARG; }
 	*out = nullptr;
 	if (genome && genome->device != h->device) { set_err("cvx_submit_windows: the genome lives on device %d, the handle on %d", genome->device, h->device); return CVX_ERR_ARG; }
@@ -1322,6 +895,8 @@ static int submit_common(cvx_handle h, int32_t n, const cvx_tile *tiles, const c
 	return CVX_OK;
 }
 
+extern "C" {
+
 int cvx_submit(cvx_handle h, int32_t n, const cvx_tile *tiles, cvx_job *out) {
 	ABI_GUARD_BEGIN return submit_common(h, n, tiles, nullptr, nullptr, out); ABI_GUARD_END
 }
@@ -1339,89 +914,6 @@ int cvx_submit_segments(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *t
 	if (n_reads < 0 || !offsets || (n_reads > 0 && !arena) || (n > 0 && !qry) || (!g && ref_position)) { set_err("cvx_submit_segments: bad argument"); return CVX_ERR_ARG; }
 	const SegmentsIn segs = { n_reads, arena, offsets, qry };
 	return submit_common(h, n, tiles, g, ref_position, out, &segs);
-	ABI_GUARD_END
-}
-
-/* what cvx_submit_ladder and cvx_submit_ladder_ex share behind their own refusals: the ladders checked, rung 1's form written
- * into a copy of the tiles, the job submitted (segs: its queries are segments of a read block, cvx_submit_segments' rules) */
-static int submit_ladder_common(const char *who, cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position,
-		const cvx_ladder *ladders, const SegmentsIn *segs, cvx_job *out) {
-	/* rung 1's corridor from the ladder, like every later rung's; every rung a tile can reach checked here, on the host,
-	 * so that the kernel writes none the device would refuse */
-	std::vector<cvx_tile> forms(tiles, tiles + n);
-	int max_rungs = 0;
-	for (int32_t i = 0; i < n; ++i) {
-		cvx_tile &t = forms[(size_t) i];
-		const cvx_ladder &l = ladders[i];
-		if (!ladder_args_ok(l, t.ref_len, t.qry_len)) {
-			set_err("%s: tile %d: corridor %d, left %g, right %g, flags %d, ref_len %d, qry_len %d", who, i, l.corridor, (double) l.left, (double) l.right, l.flags, t.ref_len, t.qry_len);
-			return CVX_ERR_ARG;
-		}
-		const int len = ladder_length(l.corridor, l.flags, t.ref_len);
-		max_rungs = std::max(max_rungs, len);
-		for (int m = len; m >= 1; --m) {      /* (downwards: rung 1's form is the one left in the tile) */
-			RowSrc f;
-			ladder_form(l.corridor, l.left, l.right, l.flags, t.ref_len, t.qry_len, m, f);
-			if (f.width < 0 || (f.fmt == kRowsAffine && !affine_form_ok(f.k, f.d, f.right, t.qry_len))) {
-				set_err("%s: tile %d: the corridor of rung %d is out of range", who, i, m);
-				return CVX_ERR_ARG;
-			}
-			t.corridor_kind = f.fmt == kRowsConst ? CVX_CORRIDOR_CONST : CVX_CORRIDOR_AFFINE;
-			t.corridor_k = f.k; t.corridor_d = f.d; t.corridor_right = f.right;
-			t.corridor_offset = f.off0; t.corridor_width = f.width;
-		}
-		t.row_offset = nullptr; t.row_length = nullptr; t.row_stride_bytes = 4;
-	}
-	static const cvx_ladder none = { 0, 0.0f, 0.0f, 0 };      /* (an empty job is a ladder job too) */
-	return submit_common(h, n, forms.data(), g, ref_position, out, segs, ladders ? ladders : &none, max_rungs);
-}
-
-int cvx_submit_ladder(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders, cvx_job *out) {
-	ABI_GUARD_BEGIN
-	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("cvx_submit_ladder: bad argument"); return CVX_ERR_ARG; }
-	if (h->nm_regions || h->job_text || h->inv_checks || h->service) {
-		set_err("cvx_submit_ladder: not on a handle with CVX_CREATE_NM_REGIONS, _JOB_TEXT, _INV_CHECKS or _SERVICE (the first three: cvx_submit_ladder_ex)");
-		return CVX_ERR_ARG;
-	}
-	return submit_ladder_common("cvx_submit_ladder", h, g, n, tiles, ref_position, ladders, nullptr, out);
-	ABI_GUARD_END
-}
-
-int cvx_submit_ladder_ex(cvx_handle h, cvx_genome g, int32_t n, const cvx_tile *tiles, const uint64_t *ref_position, const cvx_ladder *ladders,
-		int32_t n_reads, const uint8_t *arena, const uint64_t *offsets, const cvx_read_segment *qry, cvx_job *out) {
-	ABI_GUARD_BEGIN
-	static const char who[] = "cvx_submit_ladder_ex";
-	if (out) *out = nullptr;
-	if (!h || !out || n < 0 || (n > 0 && (!tiles || !ladders)) || (!g && ref_position)) { set_err("%s: bad argument", who); return CVX_ERR_ARG; }
-	if (h->service) { set_err("%s: not on a CVX_CREATE_SERVICE handle", who); return CVX_ERR_ARG; }
-	if (!qry) {
-		/* the string form: nothing of a read block may come with it */
-		if (n_reads != 0 || arena || offsets) { set_err("%s: a read block (n_reads %d, arena, offsets) without segments", who, n_reads); return CVX_ERR_ARG; }
-		return submit_ladder_common(who, h, g, n, tiles, ref_position, ladders, nullptr, out);
-	}
-	if (n_reads < 0 || !offsets || (n_reads > 0 && !arena)) { set_err("%s: segments without their read block (n_reads %d)", who, n_reads); return CVX_ERR_ARG; }
-	const SegmentsIn segs = { n_reads, arena, offsets, qry };
-	return submit_ladder_common(who, h, g, n, tiles, ref_position, ladders, &segs, out);
-	ABI_GUARD_END
-}
-
-int cvx_job_ladder(cvx_handle h, cvx_job j, const cvx_ladder_result **out) {
-	ABI_GUARD_BEGIN
-	if (!h || !j || !out || !j->ladder || !j->ladder->merged) { set_err("cvx_job_ladder: not a finished ladder job (cvx_submit_ladder, then cvx_wait)"); return CVX_ERR_ARG; }
-	*out = j->h_lout.as<cvx_ladder_result>();
-	return CVX_OK;
-	ABI_GUARD_END
-}
-
-int cvx_job_ladder_info(cvx_job j, cvx_ladder_info *out) {
-	ABI_GUARD_BEGIN
-	if (!j || !out || !j->ladder || !j->ladder->merged) { set_err("cvx_job_ladder_info: not a finished ladder job (cvx_submit_ladder, then cvx_wait)"); return CVX_ERR_ARG; }
-	memset(out, 0, sizeof(*out));
-	const LadderState *L = j->ladder;
-	out->rungs_run = (int32_t) L->rungs.size();
-	for (size_t r = 0; r < L->rungs.size() && r < 5; ++r) out->tiles[r] = L->rungs[r]->n;
-	out->seq_bytes_after_submit = L->seq_bytes_after_submit;
-	return CVX_OK;
 	ABI_GUARD_END
 }
 
@@ -1526,20 +1018,12 @@ int cvx_job_poll(cvx_handle h, cvx_job j, int32_t *done) {
 	(void) pump(h, false, nullptr);          /* queue the kernels of whatever has its corridor plans back */
 	*done = 0;
 	if (j->state == kFailed || j->state >= kFinished) { *done = 1; return CVX_OK; }
-	if (j->ladder && j->state >= kComputed) {      /* done when no rung is to come and the last one's records are on the host */
-		if (!j->ladder->done) return CVX_OK;
-		hipError_t q = hipEventQuery(j->ladder->rungs.back()->ev_res);
-		if (q == hipSuccess) *done = 1;
-		else if (q == hipErrorNotReady) (void) hipGetLastError();
-		else { set_err("hipEventQuery: %s", hipGetErrorString(q)); return CVX_ERR_HIP; }
-		return CVX_OK;
-	}
-	if (j->state >= kComputed) {
-		hipError_t q = hipEventQuery(j->ev_res);
-		if (q == hipSuccess) *done = 1;
-		else if (q == hipErrorNotReady) (void) hipGetLastError();
-		else { set_err("hipEventQuery: %s", hipGetErrorString(q)); return CVX_ERR_HIP; }
-	}
+	if (j->state < kComputed) return CVX_OK;
+	/* a ladder job: done when no rung is to come and the last one's records are on the host */
+	if (j->ladder && !j->ladder->done) return CVX_OK;
+	const int fired = event_fired(j->ladder ? j->ladder->rungs.back()->ev_res : j->ev_res);
+	if (fired < 0) return CVX_ERR_HIP;
+	*done = fired;
 	return CVX_OK;
 	ABI_GUARD_END
 }
@@ -1552,8 +1036,7 @@ void cvx_job_release(cvx_handle h, cvx_job j) {
 	if (!j) return;
 	if (h) {
 		(void) hipSetDevice(h->device);
-		auto it = std::find(h->pending.begin(), h->pending.end(), j);
-		if (it != h->pending.end()) h->pending.erase(it);
+		unlist_job(h, j, kListPending);
 		if ((j->state >= kPlanned && j->state < kFinished) || j->state == kFailed) (void) hipDeviceSynchronize();   /* released without waiting */
 	}
 	recycle_batch(h, j);

@@ -1,7 +1,7 @@
 /*
- * cvx_rt_checks.cpp -- the inversion checks of low-identity regions (checkForSV's two scores, cvx_inv_checks.h): what a job of a
- * CVX_CREATE_INV_CHECKS handle brought back with its regions (cvx_job_checks; queued by queue_job_regions, cvx_rt_align.cpp), the
- * same kernel over regions the caller holds (cvx_inv_checks), and the rule on the host (cvx_inv_checks_host).
+ * cvx_rt_checks.cpp -- the inversion checks of low-identity regions (checkForSV's two scores, cvx_inv_checks.h) over regions the
+ * caller holds: the kernel (cvx_inv_checks) and the rule on the host (cvx_inv_checks_host).  What a job of a CVX_CREATE_INV_CHECKS
+ * handle brings back with its regions (cvx_job_checks) is queued and served by JobRegions, cvx_rt_stages.cpp.
  */
 #include <cstring>
 #include <vector>
@@ -76,23 +76,6 @@ int inv_checks_run(cvx_handle h, cvx_genome g, const std::vector<uint8_t> &seq, 
 }  // namespace
 
 extern "C" {
-
-int cvx_job_checks(cvx_handle h, cvx_job j, const cvx_inv_check **checks) {
-	ABI_GUARD_BEGIN
-	static_assert(sizeof(InvCheck) == sizeof(cvx_inv_check) && sizeof(cvx_inv_check) == 16, "InvCheck mirrors cvx_inv_check");
-	if (checks) *checks = nullptr;
-	if (!h || !j || !checks) { set_err("cvx_job_checks: NULL argument"); return CVX_ERR_ARG; }
-	if (!h->inv_checks) { set_err("cvx_job_checks: the handle was created without CVX_CREATE_INV_CHECKS"); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jr_on || (j->ladder && !j->ladder->merged)) { set_err("cvx_job_checks: job not finished (call cvx_wait first)"); return CVX_ERR_ARG; }
-	if (j->ladder) {      /* a ladder job: the checks cvx_wait merged beside its regions */
-		if (j->jc_on && !j->ladder->jr_chk.empty()) *checks = reinterpret_cast<const cvx_inv_check *>(j->ladder->jr_chk.data());
-		return CVX_OK;
-	}
-	/* nothing is launched, copied or waited for here: the records came with the regions (stage_ops) */
-	if (j->jc_on && j->jr_total) *checks = j->h_jrchk.as<cvx_inv_check>();
-	return CVX_OK;
-	ABI_GUARD_END
-}
 
 int cvx_inv_checks(cvx_handle h, cvx_genome g, int32_t n_tiles, const char *const *qrys, const int32_t *qry_len,
 		const uint64_t *ref_position, const int32_t *position_offset,

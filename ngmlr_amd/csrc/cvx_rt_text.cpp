@@ -16,7 +16,7 @@ namespace {
 int text_setup(cvx_batch_s *j, const int32_t *ext_qstart, const int32_t *ext_qend, hipStream_t st, TextArgs &a) {
 	const int n = j->n;
 	const size_t n1 = (size_t) n;
-	memset(&a, 0, sizeof(a));
+	a = job_text_args(j);
 	if (ext_qstart || ext_qend) {
 		RC_TRY(j->h_ext.ensure(2 * n1 * sizeof(int32_t)));
 		RC_TRY(j->d_ext.ensure(2 * n1));
@@ -30,11 +30,33 @@ int text_setup(cvx_batch_s *j, const int32_t *ext_qstart, const int32_t *ext_qen
 	RC_TRY(j->d_tlen.ensure(2 * n1 + 8));
 	RC_TRY(j->h_trec.ensure(n1 * sizeof(TextRec)));
 	RC_TRY(j->h_toff.ensure((n1 + 1) * sizeof(unsigned long long)));
-	a.seq = j->d_seq.p; a.tin = j->d_tin.p; a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
 	a.recs = j->d_trec.p;
 	a.text_len = j->d_tlen.p; a.text_off = j->d_tlen.p + n1; a.text_total = j->d_tlen.p + 2 * n1;
-	a.text = nullptr;
-	a.n_tiles = n;
+	return CVX_OK;
+}
+
+/* results and an ops arena the caller holds, as the kernels read a job's: TileOut[] / TileRun[] over the arena, every valid tile's
+ * range and op codes checked */
+int held_ops_tiles(const char *who, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
+		std::vector<TileOut> &tout, std::vector<TileRun> &trun) {
+	const size_t n1 = (size_t) n;
+	tout.resize(n1);
+	trun.resize(n1);
+	for (size_t i = 0; i < n1; ++i) {
+		const cvx_result &r = results[i];
+		memset(&tout[i], 0, sizeof(TileOut));
+		memset(&trun[i], 0, sizeof(TileRun));
+		tout[i].status = r.status;
+		tout[i].qstart = r.qstart;
+		if (r.status != CVX_TILE_OK) continue;
+		if (r.n_ops < 0 || r.ops_begin + (uint64_t) r.n_ops > ops_total) { set_err("%s: ops of tile %zu outside the arena", who, i); return CVX_ERR_ARG; }
+		tout[i].n_ops = r.n_ops;
+		trun[i].ops_off = r.ops_begin;
+		for (int k = 0; k < r.n_ops; ++k) {
+			const int type = (int) (ops_arena[r.ops_begin + (uint64_t) k] & 15u);
+			if (type != CVX_OP_EQ && type != CVX_OP_X && type != CVX_OP_D && type != CVX_OP_I) { set_err("%s: op code %d in tile %zu", who, type, i); return CVX_ERR_ARG; }
+		}
+	}
 	return CVX_OK;
 }
 
@@ -156,11 +178,8 @@ static int nm_profile_common(cvx_handle h, cvx_job j, int32_t first, int32_t cou
 	RC_TRY(j->h_nmoff.ensure((c1 + 1) * sizeof(unsigned long long)));
 	HIP_TRY(j->ev_nm0.make());
 	HIP_TRY(j->ev_nm1.make());
-	TextArgs a;
-	memset(&a, 0, sizeof(a));
-	a.seq = j->d_seq.p; a.tin = j->d_tin.p; a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
+	TextArgs a = job_text_args(j);
 	a.recs = j->d_trec.p;
-	a.n_tiles = j->n;
 	unsigned long long *d_len = j->d_nmoff.p, *d_off = j->d_nmoff.p + c1;      /* the total lands right behind the offsets */
 	HIP_TRY(launch_nm_offsets(a, first, count, d_len, d_off, d_off + c1, st));
 	unsigned long long *hoff = j->h_nmoff.as<unsigned long long>();
@@ -211,20 +230,14 @@ int cvx_nm_profile_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 	HIP_TRY(hipSetDevice(h->device));
 	RC_TRY(ensure_streams(h));
 	const size_t n1 = (size_t) n;
-	std::vector<TileOut> tout(n1);
-	std::vector<TileRun> trun(n1);
+	std::vector<TileOut> tout;
+	std::vector<TileRun> trun;
+	RC_TRY(held_ops_tiles("cvx_nm_profile_ops", n, results, ops_arena, ops_total, tout, trun));
 	std::vector<unsigned long long> off(n1 + 1, 0ull);
 	for (size_t i = 0; i < n1; ++i) {
 		const cvx_result &r = results[i];
-		memset(&tout[i], 0, sizeof(TileOut));
-		memset(&trun[i], 0, sizeof(TileRun));
-		tout[i].status = r.status;
-		tout[i].qstart = r.qstart;
 		unsigned long long cnt = 0;
 		if (r.status == CVX_TILE_OK) {
-			if (r.n_ops < 0 || r.ops_begin + (uint64_t) r.n_ops > ops_total) { set_err("cvx_nm_profile_ops: ops of tile %zu outside the arena", i); return CVX_ERR_ARG; }
-			tout[i].n_ops = r.n_ops;
-			trun[i].ops_off = r.ops_begin;
 			/* entries per op, as addPosition admits them (src/ConvexAlignFast.cpp:76-98) */
 			long long pr = 0, pq = r.qstart;
 			for (int k = 0; k < r.n_ops; ++k) {
@@ -238,9 +251,7 @@ int cvx_nm_profile_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 				} else if (type == CVX_OP_D) {
 					if (pq > 16) { const long long skip = 17 - pr > 0 ? 17 - pr : 0; cnt += (unsigned long long) (len - skip > 0 ? len - skip : 0); }
 					pr += len;
-				} else if (type == CVX_OP_I) {
-					pq += len;
-				} else { set_err("cvx_nm_profile_ops: op code %d in tile %zu", type, i); return CVX_ERR_ARG; }
+				} else pq += len;      /* (CVX_OP_I: held_ops_tiles let nothing else through) */
 			}
 		}
 		off[i + 1] = off[i] + cnt;
@@ -296,10 +307,7 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 	if (open) RC_TRY(j->h_nmopen.ensure(c1 * sizeof(NmOpen)));
 	HIP_TRY(j->ev_nm0.make());
 	HIP_TRY(j->ev_nm1.make());
-	TextArgs a;
-	memset(&a, 0, sizeof(a));
-	a.trun = j->d_trun.p; a.tout = j->d_tout.p; a.ops = j->d_regions.p;
-	a.n_tiles = j->n;
+	const TextArgs a = job_text_args(j);
 	/* pass 1: the regions per tile, their offsets (the total right behind them), the end states */
 	unsigned long long *d_len = j->d_nmroff.p, *d_off = j->d_nmroff.p + c1;
 	HIP_TRY(hipEventRecord(j->ev_nm0, st));
@@ -331,98 +339,6 @@ int cvx_job_nm_regions(cvx_handle h, cvx_job j, int32_t first, int32_t count, ui
 	ABI_GUARD_END
 }
 
-/* the job form: what queue_job_regions (cvx_rt_align.cpp) queued behind the job's compaction and stage_results / stage_ops
- * brought back in their own waits -- nothing is launched, copied or waited for here */
-static int job_regions_ready(const char *who, cvx_handle h, cvx_job j) {
-	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
-	if (!h->nm_regions) { set_err("%s: the handle was created without CVX_CREATE_NM_REGIONS", who); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jr_on || (j->ladder && !j->ladder->merged)) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
-	return CVX_OK;
-}
-
-int cvx_job_regions(cvx_handle h, cvx_job j, const uint64_t **region_off, const cvx_nm_region **regions, const cvx_nm_open **open) {
-	ABI_GUARD_BEGIN
-	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the offsets leave as the scan wrote them");
-	if (region_off) *region_off = nullptr;
-	if (regions) *regions = nullptr;
-	if (open) *open = nullptr;
-	RC_TRY(job_regions_ready("cvx_job_regions", h, j));
-	if (j->ladder) {      /* a ladder job: what cvx_wait merged from its rungs, in the same layout */
-		const LadderState *L = j->ladder;
-		if (region_off) *region_off = L->jr_off.data();
-		if (regions) *regions = L->jr_reg.empty() ? nullptr : reinterpret_cast<const cvx_nm_region *>(L->jr_reg.data());
-		if (open) *open = j->n > 0 ? reinterpret_cast<const cvx_nm_open *>(L->jr_open.data()) : nullptr;
-		return CVX_OK;
-	}
-	if (region_off) *region_off = j->h_jroff.as<uint64_t>();
-	if (regions) *regions = j->h_jrreg.as<cvx_nm_region>();      /* (NULL for a job that never had a region: nothing to point at) */
-	if (open) *open = j->n > 0 ? j->h_jropen.as<cvx_nm_open>() : nullptr;
-	return CVX_OK;
-	ABI_GUARD_END
-}
-
-int cvx_job_regions_info(cvx_handle h, cvx_job j, uint64_t *total, uint64_t *first_capacity, int32_t *rewrites) {
-	ABI_GUARD_BEGIN
-	RC_TRY(job_regions_ready("cvx_job_regions_info", h, j));
-	if (j->ladder) {      /* the merged total, the rungs' rewrites summed, rung 1's first capacity */
-		if (total) *total = j->ladder->jr_off[(size_t) j->n];
-		if (first_capacity) *first_capacity = j->n > 0 ? j->h_jroff.as<uint64_t>()[(size_t) j->n + 1] : 0;
-		if (rewrites) *rewrites = j->ladder->jr_rewrites;
-		return CVX_OK;
-	}
-	if (total) *total = j->jr_total;
-	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jroff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
-	if (rewrites) *rewrites = j->jr_rewrites;
-	return CVX_OK;
-	ABI_GUARD_END
-}
-
-/* the same for the text stage: what queue_job_text queued behind the job's compaction */
-static int job_texts_ready(const char *who, cvx_handle h, cvx_job j) {
-	if (!h || !j) { set_err("%s: NULL argument", who); return CVX_ERR_ARG; }
-	if (!h->job_text) { set_err("%s: the handle was created without CVX_CREATE_JOB_TEXT", who); return CVX_ERR_ARG; }
-	if (j->state < kFinished || !j->have_ops || !j->jt_on || (j->ladder && !j->ladder->merged)) { set_err("%s: job not finished (call cvx_wait first)", who); return CVX_ERR_ARG; }
-	return CVX_OK;
-}
-
-int cvx_job_texts(cvx_handle h, cvx_job j, const cvx_alignment_text **recs, const uint64_t **text_off, const char **text) {
-	ABI_GUARD_BEGIN
-	static_assert(sizeof(TextRec) == sizeof(cvx_alignment_text), "TextRec mirrors cvx_alignment_text");
-	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the offsets leave as the scan wrote them");
-	if (recs) *recs = nullptr;
-	if (text_off) *text_off = nullptr;
-	if (text) *text = nullptr;
-	RC_TRY(job_texts_ready("cvx_job_texts", h, j));
-	if (j->ladder) {      /* a ladder job: what cvx_wait merged from its rungs, in the same layout */
-		const LadderState *L = j->ladder;
-		if (recs) *recs = j->n > 0 ? reinterpret_cast<const cvx_alignment_text *>(L->jt_rec.data()) : nullptr;
-		if (text_off) *text_off = L->jt_off.data();
-		if (text) *text = j->n > 0 ? L->jt_text.data() : "";
-		return CVX_OK;
-	}
-	if (recs) *recs = j->n > 0 ? j->h_jtrec.as<cvx_alignment_text>() : nullptr;
-	if (text_off) *text_off = j->h_jtoff.as<uint64_t>();
-	if (text) *text = j->n > 0 ? j->h_jtext.as<char>() : "";
-	return CVX_OK;
-	ABI_GUARD_END
-}
-
-int cvx_job_texts_info(cvx_handle h, cvx_job j, uint64_t *total_bytes, uint64_t *first_capacity, int32_t *rewrites) {
-	ABI_GUARD_BEGIN
-	RC_TRY(job_texts_ready("cvx_job_texts_info", h, j));
-	if (j->ladder) {
-		if (total_bytes) *total_bytes = j->ladder->jt_off[(size_t) j->n];
-		if (first_capacity) *first_capacity = j->n > 0 ? j->h_jtoff.as<uint64_t>()[(size_t) j->n + 1] : 0;
-		if (rewrites) *rewrites = j->ladder->jt_rewrites;
-		return CVX_OK;
-	}
-	if (total_bytes) *total_bytes = j->jt_total;
-	if (first_capacity) *first_capacity = j->n > 0 ? j->h_jtoff.as<uint64_t>()[(size_t) j->n + 1] : 0;      /* as the first write reported it */
-	if (rewrites) *rewrites = j->jt_rewrites;
-	return CVX_OK;
-	ABI_GUARD_END
-}
-
 int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const uint32_t *ops_arena, uint64_t ops_total,
 		uint64_t *region_off, cvx_nm_region *regions, uint64_t cap_regions, cvx_nm_open *open) {
 	ABI_GUARD_BEGIN
@@ -431,23 +347,9 @@ int cvx_nm_regions_ops(cvx_handle h, int32_t n, const cvx_result *results, const
 	HIP_TRY(hipSetDevice(h->device));
 	RC_TRY(ensure_streams(h));
 	const size_t n1 = (size_t) n;
-	std::vector<TileOut> tout(n1);
-	std::vector<TileRun> trun(n1);
-	for (size_t i = 0; i < n1; ++i) {
-		const cvx_result &r = results[i];
-		memset(&tout[i], 0, sizeof(TileOut));
-		memset(&trun[i], 0, sizeof(TileRun));
-		tout[i].status = r.status;
-		tout[i].qstart = r.qstart;
-		if (r.status != CVX_TILE_OK) continue;
-		if (r.n_ops < 0 || r.ops_begin + (uint64_t) r.n_ops > ops_total) { set_err("cvx_nm_regions_ops: ops of tile %zu outside the arena", i); return CVX_ERR_ARG; }
-		tout[i].n_ops = r.n_ops;
-		trun[i].ops_off = r.ops_begin;
-		for (int k = 0; k < r.n_ops; ++k) {
-			const int type = (int) (ops_arena[r.ops_begin + (uint64_t) k] & 15u);
-			if (type != CVX_OP_EQ && type != CVX_OP_X && type != CVX_OP_D && type != CVX_OP_I) { set_err("cvx_nm_regions_ops: op code %d in tile %zu", type, i); return CVX_ERR_ARG; }
-		}
-	}
+	std::vector<TileOut> tout;
+	std::vector<TileRun> trun;
+	RC_TRY(held_ops_tiles("cvx_nm_regions_ops", n, results, ops_arena, ops_total, tout, trun));
 	std::vector<unsigned long long> off(n1 + 1, 0ull);      /* (in front of the device buffers: they wait for the device as they go, and then nothing copies into it any more) */
 	DevBuf<int32_t> d_ops;
 	DevBuf<TileOut> d_tout;

@@ -11,7 +11,12 @@
  *
  *   cvx_rt_align.cpp    the alignment job pipeline: the upload / plan / compute / results / ops stages,
  *                       cvx_batch_*, cvx_align_batch, cvx_submit / cvx_wait / cvx_job_*
+ *   cvx_rt_stages.cpp   the result stages a handle runs with every job (regions, inversion checks, text): what the
+ *                       pipeline's stages call, and cvx_job_regions / _checks / _texts that hand the data out
+ *   cvx_rt_ladder.cpp   ladder jobs: cvx_submit_ladder(_ex), the rungs, the merge in cvx_wait (cvx_rt_align.h: what it
+ *                       and the pipeline call of each other)
  *   cvx_rt_text.cpp     the device-side text stage of finished jobs and the NM profile
+ *   cvx_rt_checks.cpp   the inversion checks of regions the caller holds
  *   cvx_rt_search.cpp   the resident genome and its window decode, the k-mer index, the candidate search
  *   cvx_rt_score.cpp    sub-read scoring, blocking and asynchronous
  *
@@ -78,6 +83,14 @@ float ev_ms(hipEvent_t a, hipEvent_t b) {
 	float ms = 0.0f;
 	if (hipEventElapsedTime(&ms, a, b) != hipSuccess) { (void) hipGetLastError(); return 0.0f; }
 	return ms;
+}
+
+int event_fired(hipEvent_t e) {
+	const hipError_t q = hipEventQuery(e);
+	if (q == hipSuccess) return 1;
+	if (q == hipErrorNotReady) { (void) hipGetLastError(); return 0; }
+	set_err("hipEventQuery: %s", hipGetErrorString(q));
+	return -1;
 }
 
 /* the streams of an aligning handle beside `main` (cvx_create makes only that one) */
