@@ -718,6 +718,13 @@ class KmerIndex:
         lists = [None if ncand[i] < 0 else cands[int(begin[i]):int(begin[i]) + int(ncand[i])].copy() for i in range(n)]
         return (lists, max_hit[:n], misses[:n]) if extras else lists
 
+    def last_attempts(self, n: int) -> np.ndarray:
+        """cvx_search_last_attempts: table sizes tried by each of the first n reads of the handle's last search (int32[n]; more than
+        one: the read's first attempt overflowed, CS::m_Overflows)."""
+        attempts = np.zeros(max(n, 1), dtype=np.int32)
+        capi.check(self.al.lib.cvx_search_last_attempts(self.al.h, n, attempts.ctypes.data))
+        return attempts[:n]
+
     @staticmethod
     def make_arena(reads: Sequence[bytes], lib=None):
         """The reads back to back with a NUL behind each (cvx_search_batch_arena's input form) -> (arena uint8[], offsets uint64[n + 1],

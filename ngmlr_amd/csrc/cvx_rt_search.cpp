@@ -5,6 +5,7 @@
  */
 #include <algorithm>
 #include <chrono>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include "cvx_rt.h"
 #include "cvx_score_cands.h"
 #include "cvx_score_stage.h"
+#include "cvx_search_plan.h"
 
 /* Per-handle state of the candidate search: staging and device buffers live as long as the handle, so that the steady
  * state of a caller that searches batch after batch (ngmlr's CS threads: a few hundred sub-reads per call) allocates
@@ -283,6 +285,329 @@ void cvx_index_free(cvx_handle h, cvx_index ix) {
 
 } /* extern "C" */
 
+namespace {
+
+/* One call of the search: what its stages share, and the stages in the order search_common runs them.  Every decision -- layouts,
+ * map sizes, the ladder, launches, budgets, regions, offsets -- is cvx_search_plan.h's; a stage issues what the plan says.
+ *
+ * A read starts on the wave-per-read kernel with its vote map in LDS (cvx_search.hip), in the smallest map that certainly holds
+ * it.  A read that does not fit its map after all (more than 3 072 bins; a bin beyond 32 bits; longer than the sequence buffer) is
+ * redone -- the same attempt, then the rest of the ladder -- by the same kernel over the real table in HBM, which needs the vote
+ * count to size its lists.  Candidates of read i lie at d_cand + h_srcoff[i]: the slots of its map for an LDS-map read, the sparse
+ * region behind all of those (two slots per vote) for the others. */
+struct SearchCall {
+	cvx_search_state *const ss;
+	const hipStream_t st;
+	const int32_t n;
+	const size_t n1;
+	const SearchTuning tune;
+	bool classify = false;           /* votes counted first, reads sorted into launches by map size */
+	SearchArgs a;
+	SearchMeta m;                    /* typed views into ss->h_meta, ss->h_out and ss->h_srcoff */
+	SearchOut o;
+	uint64_t *h_srcoff = nullptr;    /* where each read's candidates lie in d_cand */
+	const uint8_t *src = nullptr;    /* the caller's read block (the arena form) */
+	bool zero_copy = false;          /* ... which lies in memory from cvx_host_alloc and travels as it is */
+	uint64_t bytes = 0;              /* the reads with a NUL behind each */
+	uint64_t fixed_total = 0;        /* candidate slots of all LDS-map reads */
+	uint64_t total = 0;              /* votes of the reads that took an HBM form so far: their rList / candidate regions */
+	uint64_t need = 0;               /* candidates of the call */
+	bool counted = false;            /* o.events holds every read's votes */
+	std::vector<uint8_t> has_region, map_log2;      /* per read; map_log2 0: not an LDS-map read */
+	std::vector<int32_t> work_wave, work_hbm, next_wave, next_hbm, hbm_now;      /* reads of this attempt and of the next, per form */
+	std::string tr;                  /* CVX_SEARCH_TRACE: who ran where, for how long */
+	std::chrono::steady_clock::time_point tr0;
+
+	SearchCall(cvx_handle h, int32_t n_) : ss(h->search), st(h->s_main), n(n_), n1((size_t) n_), tune(search_tuning_env()) { memset(&a, 0, sizeof(a)); }
+
+	double tr_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); }
+	__attribute__((format(printf, 2, 3))) void note(const char *fmt, ...) {      /* (tune.trace) */
+		char b[160];
+		va_list ap;
+		va_start(ap, fmt);
+		vsnprintf(b, sizeof(b), fmt, ap);
+		va_end(ap);
+		tr += b;
+	}
+
+	/* the reads, a NUL behind each (the N-run scan of PrefixIteration relies on the terminator), in page-locked staging.  A block that
+	 * lies in memory from cvx_host_alloc travels as it is: the host touches no base (the 64 bytes behind the last read that the kernels
+	 * may read are cleared on the device) */
+	int stage_reads(const char *const *seqs, const int32_t *lens, const uint8_t *arena, const uint64_t *offsets) {
+		const int32_t bad = arena ? search_arena_reads_check(n, arena, offsets, &bytes) : search_string_reads_check(n, seqs, lens, &bytes);
+		if (bad >= 0 && arena) { set_err("cvx_search_batch_arena: read %d is not [offsets[i], offsets[i + 1] - 1) followed by a NUL", bad); return CVX_ERR_ARG; }
+		if (bad >= 0) { set_err("cvx_search_batch: bad read %d", bad); return CVX_ERR_ARG; }
+		src = arena ? arena + offsets[0] : nullptr;
+		zero_copy = arena && in_pinned_block(reinterpret_cast<const char *>(src), bytes + 4);
+		if (!zero_copy) RC_TRY(ss->h_seq.ensure((size_t) bytes + 64));
+		RC_TRY(ss->h_meta.ensure(search_meta_bytes(n1)));
+		RC_TRY(ss->h_out.ensure(search_out_bytes(n1)));
+		m = search_meta_view(ss->h_meta.p, n1);
+		o = search_out_view(ss->h_out.p, n1);
+		uint8_t *hseq = zero_copy ? nullptr : ss->h_seq.as<uint8_t>();
+		if (arena) {
+			search_arena_reads_layout(n, offsets, m.off, m.len);
+			if (!zero_copy) memcpy(hseq, src, (size_t) bytes);
+		} else {
+			search_string_reads_layout(n, lens, m.off, m.len);
+			for (int i = 0; i < n; ++i) { memcpy(hseq + m.off[i], seqs[i], (size_t) lens[i]); hseq[m.off[i] + (uint64_t) lens[i]] = 0; }
+		}
+		if (!zero_copy) memset(hseq + bytes, 0, 64);
+		return CVX_OK;
+	}
+
+	/* the device's side of the call -- its per-read arrays, the kernels' arguments -- and the reads and their layout on their way up */
+	int upload(const cvx_index_s *ix, float sensitivity, float min_hits, int32_t bin_shift) {
+		RC_TRY(ss->d_seq.ensure((size_t) bytes + 64));
+		RC_TRY(ss->d_off.ensure(n1)); RC_TRY(ss->d_listoff.ensure(n1)); RC_TRY(ss->d_begin.ensure(n1 + 1));
+		RC_TRY(ss->d_len.ensure(n1)); RC_TRY(ss->d_ncand.ensure(n1)); RC_TRY(ss->d_work.ensure(n1)); RC_TRY(ss->d_miss.ensure(n1));
+		RC_TRY(ss->d_events.ensure(n1)); RC_TRY(ss->d_maxhit.ensure(n1));
+		a.rows = ix->d_rows.p; a.locs = ix->d_locs.p; a.unit_offset = ix->unit_offset; a.k = ix->k;
+		a.seq = ss->d_seq.p; a.seq_off = ss->d_off.p; a.seq_len = ss->d_len.p; a.n = n;
+		a.events = ss->d_events.p; a.list_off = ss->d_listoff.p; a.n_cand = ss->d_ncand.p; a.max_hit = ss->d_maxhit.p; a.kmer_misses = ss->d_miss.p;
+		a.sensitivity = sensitivity; a.min_hits = min_hits; a.bin_shift = bin_shift;
+		if (zero_copy) {
+			HIP_TRY(hipMemsetAsync(ss->d_seq.p + bytes / 4 * 4, 0, 68, st));      /* what lies behind the block, first: the copy below is rounded up to whole dwords */
+			HIP_TRY(hipMemcpyAsync(ss->d_seq.p, src, (size_t) ((bytes + 3) / 4 * 4), hipMemcpyHostToDevice, st));
+		} else {
+			HIP_TRY(hipMemcpyAsync(ss->d_seq.p, ss->h_seq.p, (size_t) ((bytes + 63) / 4 * 4), hipMemcpyHostToDevice, st));
+		}
+		HIP_TRY(hipMemcpyAsync(ss->d_off.p, m.off, n1 * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(ss->d_len.p, m.len, n1 * 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemsetAsync(ss->d_miss.p, 0, n1 * 4, st));
+		HIP_TRY(hipMemsetAsync(ss->d_maxhit.p, 0, n1 * 4, st));
+		classify = search_classify(tune, n, ix->n_locs, ix->n_index);
+		ss->kev_used = 0;
+		ss->kernel_ms = 0.0f;
+		return CVX_OK;
+	}
+
+	/* votes per read (all reads: the pass is cheap): map sizes, sizes of the HBM kernel's lists */
+	int count_votes() {
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(launch_search_count(a, st));
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(hipMemcpyAsync(o.events, ss->d_events.p, n1 * 8, hipMemcpyDeviceToHost, st));
+		RC_TRY(search_wait(ss, st));
+		counted = true;
+		return CVX_OK;
+	}
+
+	/* every read's map and where its candidates lie; the arena for the LDS-map reads' */
+	int assign_maps() {
+		has_region.assign(n1, 0);
+		map_log2.assign(n1, 0);
+		RC_TRY(ss->d_srcoff.ensure(n1));
+		RC_TRY(ss->h_srcoff.ensure(n1 * 8));
+		h_srcoff = ss->h_srcoff.as<uint64_t>();
+		fixed_total = search_assign_maps(tune, classify, n, m.len, o.events, map_log2.data(), h_srcoff);
+		RC_TRY(ss->d_cand.ensure((size_t) fixed_total + 64));
+		HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
+		return CVX_OK;
+	}
+
+	/* one attempt of the reads on the LDS form: one launch per map size, back to back (the work list holds the sizes' reads one
+	 * after the other), then their flags: done, out of budget (the next attempt), or not for this map (the HBM form, this attempt) */
+	int wave_attempt(int bits) {
+		SearchWaveLaunch launches[kSearchWaveSizes];
+		const int n_launches = search_wave_launches(tune, bits, work_wave, map_log2.data(), m.len, m.work, launches);
+		a.cand = ss->d_cand.p; a.cand_off = ss->d_srcoff.p;
+		for (int k = 0; k < n_launches; ++k) {
+			const SearchWaveLaunch &w = launches[k];
+			HIP_TRY(hipMemcpyAsync(ss->d_work.p + w.first, m.work + w.first, w.count * 4, hipMemcpyHostToDevice, st));
+			a.work = ss->d_work.p + w.first;
+			a.n_work = (int32_t) w.count;
+			RC_TRY(ss->kmark(st));
+			HIP_TRY(launch_search_wave(a, w.log2, w.seq_cap, w.slot8, st));
+			RC_TRY(ss->kmark(st));
+			if (tune.trace) note(" [2^%d-slot maps: %zu reads]", w.log2, w.count);
+		}
+		a.work = ss->d_work.p;
+		HIP_TRY(hipMemcpyAsync(o.ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
+		RC_TRY(search_wait(ss, st));
+		for (int32_t i : work_wave) {
+			if (o.ncand[i] == kSearchNeedsHbm) hbm_now.push_back(i);
+			else if (o.ncand[i] < 0) next_wave.push_back(i);
+		}
+		if (tune.trace) note(" [bits %d wave %zu -> %zu to hbm, %zu retry, at %.2f ms]", bits, work_wave.size(), hbm_now.size() - work_hbm.size(), next_wave.size(), tr_ms());
+		return CVX_OK;
+	}
+
+	/* regions for the reads of hbm_now that have none yet; the candidate arena grows without losing the lists already in it */
+	int give_regions() {
+		if (!search_give_regions(hbm_now, o.events, has_region.data(), m.list_off, &total)) return CVX_OK;
+		RC_TRY(ss->d_rlist.ensure((size_t) total + 64));
+		if (ss->d_cand.cap < search_cand_needed(fixed_total, total)) {
+			DevBuf<SearchCandidate> bigger;
+			RC_TRY(bigger.ensure(search_cand_grown(fixed_total, total)));
+			HIP_TRY_IN("cvx_search_batch", hipMemcpyAsync(bigger.p, ss->d_cand.p, ss->d_cand.cap * sizeof(SearchCandidate), hipMemcpyDeviceToDevice, st));
+			RC_TRY(search_wait(ss, st));
+			ss->d_cand = std::move(bigger);      /* (frees the old arena: the copy out of it is done) */
+		}
+		HIP_TRY(hipMemcpyAsync(ss->d_listoff.p, m.list_off, n1 * 8, hipMemcpyHostToDevice, st));
+		return CVX_OK;
+	}
+
+	/* hbm_now in one launch of the wave-per-read kernel over tables in HBM.  The tables belong to the waves and are empty between
+	 * launches -- a wave frees the slots a read opened when the read is done -- so they are cleared when they are allocated, when the
+	 * table size changes and after a launch that failed, not per read */
+	int launch_hbm_tables(int bits) {
+		RC_TRY(ss->d_undo.ensure((size_t) total + 64));
+		a.undo = ss->d_undo.p;
+		const size_t n_tables = search_hbm_tables(hbm_now.size(), bits), need_words = search_hbm_table_words(n_tables, bits);
+		if (ss->d_keys.cap < need_words) { RC_TRY(ss->d_keys.ensure(need_words)); ss->tables_clean_words = 0; }
+		if (ss->tables_clean_words < need_words) {
+			HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, ss->d_keys.cap * 8, st));      /* (scores of a free slot are never read) */
+			ss->tables_clean_words = ss->d_keys.cap;
+		}
+		RC_TRY(ss->d_ticket.ensure(16));
+		HIP_TRY(hipMemsetAsync(ss->d_ticket.p, 0, 4, st));
+		a.keys = ss->d_keys.p;
+		memcpy(m.work, hbm_now.data(), hbm_now.size() * 4);
+		HIP_TRY(hipMemcpyAsync(ss->d_work.p, m.work, hbm_now.size() * 4, hipMemcpyHostToDevice, st));
+		a.n_work = (int32_t) hbm_now.size();
+		ss->tables_clean_words = 0;                     /* until the launch is known to have ended (hbm_attempt) */
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(launch_search_wave_hbm(a, (int) n_tables, ss->d_ticket.p, st));
+		RC_TRY(ss->kmark(st));
+		return CVX_OK;
+	}
+
+	/* hbm_now on the lane-per-read kernel, a table per read: in chunks of as many reads as the table budget holds */
+	int launch_lane_chunks(int bits) {
+		const size_t chunk = search_lane_chunk(hbm_now.size(), bits);
+		ss->tables_clean_words = 0;                         /* the lane-per-read kernel leaves its tables as they are */
+		RC_TRY(ss->d_keys.ensure(search_lane_keys(chunk, bits)));
+		RC_TRY(ss->d_scores.ensure(search_lane_scores(chunk, bits)));
+		a.keys = ss->d_keys.p; a.scores = ss->d_scores.p;
+		for (size_t w0 = 0; w0 < hbm_now.size(); w0 += chunk) {
+			const size_t k = std::min(chunk, hbm_now.size() - w0);
+			memcpy(m.work, hbm_now.data() + w0, k * 4);
+			HIP_TRY(hipMemcpyAsync(ss->d_work.p, m.work, k * 4, hipMemcpyHostToDevice, st));
+			HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, search_lane_keys(k, bits) * 8, st));          /* every slot empty */
+			a.n_work = (int32_t) k;
+			RC_TRY(ss->kmark(st));
+			HIP_TRY(launch_search(a, st));
+			RC_TRY(ss->kmark(st));
+			if (w0 + chunk < hbm_now.size()) RC_TRY(search_wait(ss, st));      /* (the work list is reused by the next chunk) */
+		}
+		return CVX_OK;
+	}
+
+	/* one attempt of the reads on an HBM form -- those of the last attempt and those the LDS form has just sent -- and their flags */
+	int hbm_attempt(int bits) {
+		a.work = ss->d_work.p;
+		if (!counted) RC_TRY(count_votes());
+		RC_TRY(give_regions());
+		for (int32_t i : hbm_now) h_srcoff[i] = search_hbm_src_off(fixed_total, m.list_off[i]);
+		a.rlist = ss->d_rlist.p; a.cand = ss->d_cand.p + fixed_total;
+		RC_TRY(tune.lane_serial ? launch_lane_chunks(bits) : launch_hbm_tables(bits));
+		HIP_TRY(hipMemcpyAsync(o.ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
+		RC_TRY(search_wait(ss, st));
+		if (!tune.lane_serial) ss->tables_clean_words = ss->d_keys.cap;      /* the launch ended: every wave left its table empty */
+		for (int32_t i : hbm_now) if (o.ncand[i] < 0) next_hbm.push_back(i);
+		if (tune.trace) note(" [bits %d hbm %zu (%llu votes in the call) -> %zu retry, at %.2f ms]", bits, hbm_now.size(), (unsigned long long) total, next_hbm.size(), tr_ms());
+		return CVX_OK;
+	}
+
+	/* the retry ladder (search_ladder_bits): every attempt takes the reads the one before left without a list, each on its form; a
+	 * read that leaves the ladder without a list keeps -1 (one still flagged for the HBM form cannot remain: it was redone in its attempt) */
+	int climb(int32_t first_bits) {
+		tr0 = std::chrono::steady_clock::now();
+		for (int i = 0; i < n; ++i) (map_log2[(size_t) i] ? work_wave : work_hbm).push_back(i);
+		ss->attempts.assign(n1, 0);
+		for (int attempt = 0; !work_wave.empty() || !work_hbm.empty(); ++attempt) {
+			const int bits = search_ladder_bits(first_bits, attempt);
+			if (bits > kSearchLadderMaxBits) break;
+			for (int32_t i : work_wave) ss->attempts[(size_t) i] += 1;
+			for (int32_t i : work_hbm) ss->attempts[(size_t) i] += 1;
+			a.bits = bits;
+			a.hpoc_factor = search_ladder_factor(attempt);
+			next_wave.clear(); next_hbm.clear();
+			hbm_now = work_hbm;
+			if (!work_wave.empty()) RC_TRY(wave_attempt(bits));
+			if (!hbm_now.empty()) RC_TRY(hbm_attempt(bits));
+			work_wave.swap(next_wave);
+			work_hbm.swap(next_hbm);
+		}
+		return CVX_OK;
+	}
+
+	/* the dense candidate list in read order, compacted on the device: only the entries come back (the sparse arena is two slots per vote) */
+	int compact() {
+		RC_TRY(ss->d_dense.ensure((size_t) need + 64));
+		HIP_TRY(hipMemcpyAsync(ss->d_begin.p, m.begin, (n1 + 1) * 8, hipMemcpyHostToDevice, st));
+		HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
+		RC_TRY(ss->kmark(st));
+		HIP_TRY(launch_search_compact(ss->d_cand.p, ss->d_srcoff.p, ss->d_ncand.p, ss->d_begin.p, ss->d_dense.p, n, st));
+		RC_TRY(ss->kmark(st));
+		return CVX_OK;
+	}
+
+	/* The scoring of every candidate, queued behind the compaction: the lists are planned where they lie (d_dense), the strings come
+	 * from the resident genome and from the read block the vote has just used, and both launchers run over all `need` slots -- a
+	 * candidate that is not scored is two empty strings there.  Nothing is uploaded. */
+	int queue_scoring(const SearchScoreArgs &fs) {
+		const CandWinSlots slots = cand_windows_slots(fs.buffer_len, fs.max_read_bytes, need);
+		RC_TRY(ss->d_fdesc.ensure((size_t) need)); RC_TRY(ss->d_fpairs.ensure((size_t) need));
+		RC_TRY(ss->d_fout.ensure((size_t) need)); RC_TRY(ss->d_fstatus.ensure((size_t) need));
+		RC_TRY(ss->d_fseq.ensure((size_t) slots.seq_bytes + 256));
+		RC_TRY(ss->h_fout.ensure((size_t) need * 8));
+		HIP_TRY(ss->ev_f0.make());
+		HIP_TRY(ss->ev_f1.make());
+		HIP_TRY(hipEventRecord(ss->ev_f0, st));
+		HIP_TRY(launch_plan_candidate_windows(ss->d_dense.p, ss->d_begin.p, ss->d_ncand.p, ss->d_off.p, ss->d_len.p, n, need,
+				score_windows_concat_len(fs.g->n_nibbles), fs.buffer_len, fs.window_lead, fs.max_cmrs, slots, ss->d_fdesc.p, ss->d_fstatus.p, st));
+		HIP_TRY(launch_stage_score_windows(fs.g->d_bin.p, ss->d_seq.p, ss->d_fdesc.p, (int) need, ss->d_fseq.p, ss->d_fpairs.p, st));
+		HIP_TRY(launch_score_diag(ss->d_fseq.p, ss->d_fpairs.p, ss->d_fout.p, (int) need, st));
+		HIP_TRY(hipEventRecord(ss->ev_f1, st));
+		return CVX_OK;
+	}
+
+	/* what the call hands back: the lists dense in the caller's arena (and their scores), the per-read counts, offsets and extras */
+	int bring_back(const SearchScoreArgs *fs, int32_t *n_candidates, uint64_t *cand_begin, cvx_candidate *cands, uint64_t cand_capacity, uint64_t *cand_used,
+			float *max_hit, int32_t *kmer_misses) {
+		need = search_dense_offsets(n, o.ncand, m.begin, cand_begin, n_candidates);
+		if (cand_used) *cand_used = need;
+		/* (the launchers behind the compaction count slots in an int; refused here, where nothing of the call is queued any more) */
+		if (fs && need > 0x7fffffffull) { set_err("cvx_search_score_arena: %llu candidates in one call", (unsigned long long) need); return CVX_ERR_ARG; }
+		if (max_hit || kmer_misses) {
+			HIP_TRY(hipMemcpyAsync(o.maxhit, ss->d_maxhit.p, n1 * 4, hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(o.miss, ss->d_miss.p, n1 * 4, hipMemcpyDeviceToHost, st));
+		}
+		if (need > cand_capacity || (need > 0 && !cands)) {
+			if (max_hit || kmer_misses) RC_TRY(search_wait(ss, st));
+			set_err("cvx_search_batch: candidate arena too small (%llu needed, %llu given)", (unsigned long long) need, (unsigned long long) cand_capacity);
+			return CVX_ERR_CAPACITY;
+		}
+		if (need) {
+			RC_TRY(compact());
+			if (fs) RC_TRY(queue_scoring(*fs));
+			/* (straight into the caller's memory: pageable unless it came from cvx_host_alloc, then the copy is staged by the runtime) */
+			HIP_TRY(hipMemcpyAsync(cands, ss->d_dense.p, (size_t) need * sizeof(SearchCandidate), hipMemcpyDeviceToHost, st));
+			if (fs) {
+				HIP_TRY(hipMemcpyAsync(ss->h_fout.p, ss->d_fout.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
+				HIP_TRY(hipMemcpyAsync(ss->h_fout.as<uint8_t>() + (size_t) need * 4, ss->d_fstatus.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
+			}
+		}
+		RC_TRY(search_wait(ss, st));
+		for (size_t q = 0; q + 1 < ss->kev_used; q += 2) ss->kernel_ms += ev_ms(ss->kev[q], ss->kev[q + 1]);
+		if (fs && need) {
+			ss->fused_ms = ev_ms(ss->ev_f0, ss->ev_f1);
+			const float *out = ss->h_fout.as<float>();
+			const int32_t *status = reinterpret_cast<const int32_t *>(out + need);
+			for (uint64_t q = 0; q < need; ++q) fs->sw_scores[q] = status[q] == kCandScored ? out[q] : -1.0f;
+			if (fs->sw_status) memcpy(fs->sw_status, status, (size_t) need * 4);
+		}
+		if (tune.trace) fprintf(stderr, "cvx_search_batch: %d reads, %llu bases, %llu candidates, %.2f ms:%s\n", n, (unsigned long long) bytes - (unsigned long long) n, (unsigned long long) need, tr_ms(), tr.c_str());
+		if (max_hit) memcpy(max_hit, o.maxhit, n1 * 4);
+		if (kmer_misses) memcpy(kmer_misses, o.miss, n1 * 4);
+		return CVX_OK;
+	}
+};
+
+}  // namespace
+
 /* the reads either as n NUL-terminated strings (seqs / lens) or back to back in one block (arena / offsets: read i =
  * arena[offsets[i] .. offsets[i + 1] - 1) with a NUL at offsets[i + 1] - 1) */
 static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *const *seqs, const int32_t *lens, const uint8_t *arena, const uint64_t *offsets,
@@ -302,319 +627,13 @@ static int search_common(cvx_handle h, cvx_index ix, int32_t n, const char *cons
 	if (n == 0) return CVX_OK;
 	HIP_TRY(hipSetDevice(h->device));
 	if (!h->search) { h->search = new (std::nothrow) cvx_search_state(); if (!h->search) return CVX_ERR_OOM; }
-	cvx_search_state *ss = h->search;
-	hipStream_t st = h->s_main;
-	/* the reads, a NUL behind each (the N-run scan of PrefixIteration relies on the terminator), in page-locked staging */
-	uint64_t bytes = 0;
-	if (arena) {
-		for (int i = 0; i < n; ++i) {
-			if (offsets[i + 1] <= offsets[i] || offsets[i + 1] - offsets[i] > 0x7FFFFFFFull || arena[offsets[i + 1] - 1] != 0) {
-				set_err("cvx_search_batch_arena: read %d is not [offsets[i], offsets[i + 1] - 1) followed by a NUL", i); return CVX_ERR_ARG;
-			}
-		}
-		bytes = offsets[n] - offsets[0];
-	} else {
-		for (int i = 0; i < n; ++i) {
-			if (!seqs[i] || lens[i] < 0) { set_err("cvx_search_batch: bad read %d", i); return CVX_ERR_ARG; }
-			bytes += (uint64_t) lens[i] + 1;
-		}
-	}
-	const size_t n1 = (size_t) n;
-	/* a block that lies in memory from cvx_host_alloc travels as it is: the host touches no base (the 64 bytes behind the last read
-	 * that the kernels may read are cleared on the device) */
-	const uint8_t *src = arena ? arena + offsets[0] : nullptr;
-	const bool zero_copy = arena && in_pinned_block(reinterpret_cast<const char *>(src), bytes + 4);
-	if (!zero_copy) RC_TRY(ss->h_seq.ensure((size_t) bytes + 64));
-	/* meta: [off u64 n][list_off u64 n][begin u64 n + 1][len i32 n][work i32 n] */
-	RC_TRY(ss->h_meta.ensure(n1 * (8 + 8 + 8 + 4 + 4) + 8 + 64));
-	/* out: [events u64 n][ncand i32 n][miss i32 n][maxhit f32 n] (the dense candidates get their own buffer below) */
-	RC_TRY(ss->h_out.ensure(n1 * (8 + 4 + 4 + 4) + 64));
-	uint8_t *hseq = zero_copy ? nullptr : ss->h_seq.as<uint8_t>();
-	uint64_t *h_off = ss->h_meta.as<uint64_t>(), *h_listoff = h_off + n1, *h_begin = h_listoff + n1;
-	int32_t *h_len = reinterpret_cast<int32_t *>(h_begin + n1 + 1), *h_work = h_len + n1;
-	unsigned long long *h_events = ss->h_out.as<unsigned long long>();
-	int32_t *h_ncand = reinterpret_cast<int32_t *>(h_events + n1), *h_miss = h_ncand + n1;
-	float *h_maxhit = reinterpret_cast<float *>(h_miss + n1);
-	if (arena) {
-		for (int i = 0; i < n; ++i) { h_off[i] = offsets[i] - offsets[0]; h_len[i] = (int32_t) (offsets[i + 1] - offsets[i] - 1); }
-		if (!zero_copy) { memcpy(hseq, src, (size_t) bytes); memset(hseq + bytes, 0, 64); }
-	} else {
-		uint64_t at = 0;
-		for (int i = 0; i < n; ++i) {
-			h_off[i] = at;
-			memcpy(hseq + at, seqs[i], (size_t) lens[i]);
-			hseq[at + (uint64_t) lens[i]] = 0;
-			at += (uint64_t) lens[i] + 1;
-			h_len[i] = lens[i];
-		}
-		memset(hseq + at, 0, 64);
-	}
-	RC_TRY(ss->d_seq.ensure((size_t) bytes + 64));
-	RC_TRY(ss->d_off.ensure(n1)); RC_TRY(ss->d_listoff.ensure(n1)); RC_TRY(ss->d_begin.ensure(n1 + 1));
-	RC_TRY(ss->d_len.ensure(n1)); RC_TRY(ss->d_ncand.ensure(n1)); RC_TRY(ss->d_work.ensure(n1)); RC_TRY(ss->d_miss.ensure(n1));
-	RC_TRY(ss->d_events.ensure(n1)); RC_TRY(ss->d_maxhit.ensure(n1));
-	SearchArgs a;
-	memset(&a, 0, sizeof(a));
-	a.rows = ix->d_rows.p; a.locs = ix->d_locs.p; a.unit_offset = ix->unit_offset; a.k = ix->k;
-	a.seq = ss->d_seq.p; a.seq_off = ss->d_off.p; a.seq_len = ss->d_len.p; a.n = n;
-	a.events = ss->d_events.p; a.list_off = ss->d_listoff.p; a.n_cand = ss->d_ncand.p; a.max_hit = ss->d_maxhit.p; a.kmer_misses = ss->d_miss.p;
-	a.sensitivity = sensitivity; a.min_hits = min_hits; a.bin_shift = bin_shift;
-	if (zero_copy) {
-		HIP_TRY(hipMemsetAsync(ss->d_seq.p + bytes / 4 * 4, 0, 68, st));      /* what lies behind the block, first: the copy below is rounded up to whole dwords */
-		HIP_TRY(hipMemcpyAsync(ss->d_seq.p, src, (size_t) ((bytes + 3) / 4 * 4), hipMemcpyHostToDevice, st));
-	} else {
-		HIP_TRY(hipMemcpyAsync(ss->d_seq.p, hseq, (size_t) ((bytes + 63) / 4 * 4), hipMemcpyHostToDevice, st));
-	}
-	HIP_TRY(hipMemcpyAsync(ss->d_off.p, h_off, n1 * 8, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemcpyAsync(ss->d_len.p, h_len, n1 * 4, hipMemcpyHostToDevice, st));
-	HIP_TRY(hipMemsetAsync(ss->d_miss.p, 0, n1 * 4, st));
-	HIP_TRY(hipMemsetAsync(ss->d_maxhit.p, 0, n1 * 4, st));
-	/* A read starts on the wave-per-read kernel with its vote map in LDS (cvx_search.hip), in the smallest map that certainly holds
-	 * it: a call of CVX_TUNE_SEARCH_CLASSIFY (2 048) reads or more counts every read's votes first (one cheap kernel and one round
-	 * trip) and sorts the reads into launches by map size -- 6 KB of LDS for a read of <= 384 votes, 24 KB for <= 1 536, 48 KB
-	 * above -- so that as many reads as possible share a CU; a smaller call takes the 2^11-slot map for every read without
-	 * counting (its reads do not fill the device anyway).  A read that does not fit its map after all (more than 3 072 bins; a bin
-	 * beyond 32 bits; longer than the sequence buffer) is redone -- the same attempt, then the rest of the ladder -- by the same
-	 * kernel over the real table in HBM, which needs the vote count to size its lists.  Candidates of read i lie at d_cand +
-	 * src_off[i]: two per bin its map can hold (or per vote, when that is fewer) for an LDS-map read, the sparse region behind all
-	 * of those (two slots per vote) for the others.  CVX_TUNE_SEARCH_WAVE=2 sends every read to the HBM-table form, =0 to the
-	 * lane-per-read kernel (one serial chain of votes per read; an independent implementation: tests, A/B);
-	 * CVX_TUNE_SEARCH_LOG2=9..12 forces one map size (tests: a small one sends most reads through the fall-back). */
-	const char *wave_env = getenv("CVX_TUNE_SEARCH_WAVE");      /* (read per call: the parity tests switch it inside one process) */
-	const int wave_mode = wave_env ? atoi(wave_env) : 1;
-	const bool use_wave = wave_mode == 1;
-	const bool lane_serial = wave_mode == 0;
-	const char *cls_env = getenv("CVX_TUNE_SEARCH_CLASSIFY"), *log2_env = getenv("CVX_TUNE_SEARCH_LOG2"), *slot8_env = getenv("CVX_TUNE_SEARCH_SLOT8");
-	const int classify_min = cls_env ? atoi(cls_env) : 2048;
-	const int forced_log2 = log2_env ? std::min(kSearchWaveLog2Max, std::max(kSearchWaveLog2Min, atoi(log2_env))) : 0;
-	/* (a table with three locations per k-mer and more -- a genome of 600 Mbp and up at ngmlr's defaults -- gives a 256-base read
-	 * 1 500 votes and more: the one-size map of a small call would not hold it, so its reads are counted and sorted as well) */
-	const bool big_table = (uint64_t) ix->n_locs >= 3ull * (ix->n_index - 2ull);
-	const bool classify = use_wave && !forced_log2 && (n >= classify_min || big_table);
-	bool counted = false;
-	uint64_t total = 0;             /* votes of the reads that took the HBM-table form so far: their rList / candidate regions */
-	std::vector<uint8_t> has_region(n1, 0);
-	ss->kev_used = 0;
-	ss->kernel_ms = 0.0f;
-	auto count_votes = [&]() -> int {      /* votes per read (all reads: the pass is cheap): map sizes, sizes of the HBM kernel's lists */
-		RC_TRY(ss->kmark(st));
-		HIP_TRY(launch_search_count(a, st));
-		RC_TRY(ss->kmark(st));
-		HIP_TRY(hipMemcpyAsync(h_events, ss->d_events.p, n1 * 8, hipMemcpyDeviceToHost, st));
-		RC_TRY(search_wait(ss, st));
-		counted = true;
-		return CVX_OK;
-	};
-	if (classify) RC_TRY(count_votes());
-	std::vector<uint8_t> map_log2(n1, 0);      /* 0: not an LDS-map read */
-	RC_TRY(ss->d_srcoff.ensure(n1));
-	RC_TRY(ss->h_srcoff.ensure(n1 * 8));
-	uint64_t *h_srcoff = ss->h_srcoff.as<uint64_t>();
-	uint64_t fixed_total = 0;
-	for (int i = 0; i < n; ++i) {
-		h_srcoff[i] = fixed_total;
-		if (!use_wave || h_len[i] + 1 > kSearchWaveSeq) continue;
-		const int l = forced_log2 ? forced_log2 : classify ? search_wave_log2(h_events[i]) : kSearchWaveLog2Default;
-		map_log2[(size_t) i] = (uint8_t) l;
-		uint64_t bins = (uint64_t) search_wave_entries(l);
-		if (classify && h_events[i] < bins) bins = h_events[i];
-		fixed_total += 2 * bins;
-	}
-	RC_TRY(ss->d_cand.ensure((size_t) fixed_total + 64));
-	HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
-	/* Regions only for the reads that really go to the HBM-table form, handed out when a read first gets there and kept for its
-	 * retries (sizing them by the votes of all n reads cost a repeat-rich call gigabytes per handle).  The
-	 * candidate arena grows without losing the lists already in it. */
-	auto give_regions = [&](const std::vector<int32_t> &reads) -> int {
-		bool grew = false;
-		for (int32_t i : reads) {
-			if (has_region[(size_t) i]) continue;
-			has_region[(size_t) i] = 1;
-			h_listoff[i] = total;
-			total += h_events[i];
-			grew = true;
-		}
-		if (!grew) return CVX_OK;
-		RC_TRY(ss->d_rlist.ensure((size_t) total + 64));
-		if (ss->d_cand.cap < (size_t) (fixed_total + 2 * total) + 64) {
-			DevBuf<SearchCandidate> bigger;
-			RC_TRY(bigger.ensure((size_t) (fixed_total + 2 * total) + (size_t) total / 2 + 64));
-			HIP_TRY_IN("cvx_search_batch", hipMemcpyAsync(bigger.p, ss->d_cand.p, ss->d_cand.cap * sizeof(SearchCandidate), hipMemcpyDeviceToDevice, st));
-			RC_TRY(search_wait(ss, st));
-			ss->d_cand = std::move(bigger);      /* (frees the old arena: the copy out of it is done) */
-		}
-		HIP_TRY(hipMemcpyAsync(ss->d_listoff.p, h_listoff, n1 * 8, hipMemcpyHostToDevice, st));
-		return CVX_OK;
-	};
-	/* the reference's retry ladder (CS.cpp:345-394): the current table size with a probe budget of a third of the table, then
-	 * that + 2, + 3, ... up to 2^20 entries with 0.777; first_bits = CS::c_SrchTableBitLen (16 when the thread starts; the
-	 * reference adapts it per batch, CS.cpp:482-489 -- the size only decides WHEN an attempt runs out of budget, a successful
-	 * attempt returns the same list at every size). */
-	const int bits0 = first_bits ? first_bits : 16;
-	const bool trace = getenv("CVX_SEARCH_TRACE") != nullptr;      /* one line per call on stderr: who ran where, for how long (read per call: tests switch it on inside a process) */
-	const std::chrono::steady_clock::time_point tr0 = std::chrono::steady_clock::now();
-	std::string tr;
-	auto tr_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(); };
-	std::vector<int32_t> work_wave, work_hbm;
-	for (int i = 0; i < n; ++i) (map_log2[(size_t) i] ? work_wave : work_hbm).push_back(i);
-	ss->attempts.assign(n1, 0);
-	for (int attempt = 0; !work_wave.empty() || !work_hbm.empty(); ++attempt) {
-		const int bits = attempt == 0 ? bits0 : bits0 + 1 + attempt;
-		if (bits > 20) break;
-		for (int32_t i : work_wave) ss->attempts[(size_t) i] += 1;
-		for (int32_t i : work_hbm) ss->attempts[(size_t) i] += 1;
-		a.bits = bits;
-		a.hpoc_factor = attempt == 0 ? 0.333f : 0.777f;
-		std::vector<int32_t> next_wave, next_hbm, hbm_now(work_hbm);
-		if (!work_wave.empty()) {
-			/* one launch per map size, back to back (the work list holds the sizes' reads one after the other) */
-			size_t at = 0;
-			a.cand = ss->d_cand.p; a.cand_off = ss->d_srcoff.p;
-			for (int l = kSearchWaveLog2Min; l <= kSearchWaveLog2Max; ++l) {
-				const size_t first = at;
-				int longest = 0;
-				for (int32_t i : work_wave) if (map_log2[(size_t) i] == l) { h_work[at++] = i; longest = std::max(longest, h_len[i]); }
-				if (at == first) continue;
-				HIP_TRY(hipMemcpyAsync(ss->d_work.p + first, h_work + first, (at - first) * 4, hipMemcpyHostToDevice, st));
-				a.work = ss->d_work.p + first;
-				a.n_work = (int32_t) (at - first);
-				RC_TRY(ss->kmark(st));
-				/* the 8-byte map where it applies: the reference's default table size or below, sub-reads (a count of 255 is out of
-				 * reach of a read's 256 k-mers unless a row repeats inside a bin), not the largest map; CVX_TUNE_SEARCH_SLOT8=0 / 1 */
-				const bool slot8 = slot8_env ? atoi(slot8_env) != 0 && bits <= 16 && l < kSearchWaveLog2Max : (bits <= 16 && l < kSearchWaveLog2Max && longest <= 268);
-				HIP_TRY(launch_search_wave(a, l, (longest + 65 + 63) / 64 * 64, slot8, st));
-				RC_TRY(ss->kmark(st));
-				if (trace) { char b[96]; snprintf(b, sizeof(b), " [2^%d-slot maps: %zu reads]", l, at - first); tr += b; }
-			}
-			a.work = ss->d_work.p;
-			HIP_TRY(hipMemcpyAsync(h_ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
-			RC_TRY(search_wait(ss, st));
-			for (int32_t i : work_wave) {
-				if (h_ncand[i] == kSearchNeedsHbm) hbm_now.push_back(i);
-				else if (h_ncand[i] < 0) next_wave.push_back(i);
-			}
-			if (trace) { char b[160]; snprintf(b, sizeof(b), " [bits %d wave %zu -> %zu to hbm, %zu retry, at %.2f ms]", bits, work_wave.size(), hbm_now.size() - work_hbm.size(), next_wave.size(), tr_ms()); tr += b; }
-		}
-		if (!hbm_now.empty()) {
-			a.work = ss->d_work.p;
-			if (!counted) RC_TRY(count_votes());
-			RC_TRY(give_regions(hbm_now));
-			for (int32_t i : hbm_now) h_srcoff[i] = fixed_total + 2 * h_listoff[i];
-			const size_t per_read = (size_t) 1 << bits;
-			a.rlist = ss->d_rlist.p; a.cand = ss->d_cand.p + fixed_total;
-			if (!lane_serial) {
-				/* the wave kernel's tables belong to the waves: as many as can be resident (or as 8 GB hold), each 2^bits entries of 16
-				 * bytes, empty between launches -- a wave frees the slots a read opened when the read is done -- so they are cleared
-				 * when they are allocated, when the table size changes and after a launch that failed, not per read */
-				RC_TRY(ss->d_undo.ensure((size_t) total + 64));
-				a.undo = ss->d_undo.p;
-				const size_t n_tables = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(hbm_now.size(), 8192), ((size_t) 8 << 30) / (per_read * 16)));
-				const size_t need_words = n_tables * per_read * 2;
-				if (ss->d_keys.cap < need_words) { RC_TRY(ss->d_keys.ensure(need_words)); ss->tables_clean_words = 0; }
-				if (ss->tables_clean_words < need_words) {
-					HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, ss->d_keys.cap * 8, st));      /* (scores of a free slot are never read) */
-					ss->tables_clean_words = ss->d_keys.cap;
-				}
-				RC_TRY(ss->d_ticket.ensure(16));
-				HIP_TRY(hipMemsetAsync(ss->d_ticket.p, 0, 4, st));
-				a.keys = ss->d_keys.p;
-				memcpy(h_work, hbm_now.data(), hbm_now.size() * 4);
-				HIP_TRY(hipMemcpyAsync(ss->d_work.p, h_work, hbm_now.size() * 4, hipMemcpyHostToDevice, st));
-				a.n_work = (int32_t) hbm_now.size();
-				ss->tables_clean_words = 0;                     /* until the launch is known to have ended */
-				RC_TRY(ss->kmark(st));
-				HIP_TRY(launch_search_wave_hbm(a, (int) n_tables, ss->d_ticket.p, st));
-				RC_TRY(ss->kmark(st));
-			} else {
-			const size_t chunk = std::max<size_t>(1, std::min<size_t>(hbm_now.size(), ((size_t) 8 << 30) / (per_read * 16)));
-			ss->tables_clean_words = 0;                         /* the lane-per-read kernel leaves its tables as they are */
-			RC_TRY(ss->d_keys.ensure(chunk * per_read));
-			RC_TRY(ss->d_scores.ensure(chunk * per_read * 2));
-			a.keys = ss->d_keys.p; a.scores = ss->d_scores.p;
-			for (size_t w0 = 0; w0 < hbm_now.size(); w0 += chunk) {
-				const size_t m = std::min(chunk, hbm_now.size() - w0);
-				memcpy(h_work, hbm_now.data() + w0, m * 4);
-				HIP_TRY(hipMemcpyAsync(ss->d_work.p, h_work, m * 4, hipMemcpyHostToDevice, st));
-				HIP_TRY(hipMemsetAsync(ss->d_keys.p, 0xFF, m * per_read * 8, st));          /* every slot empty */
-				a.n_work = (int32_t) m;
-				RC_TRY(ss->kmark(st));
-				HIP_TRY(launch_search(a, st));
-				RC_TRY(ss->kmark(st));
-				if (w0 + chunk < hbm_now.size()) RC_TRY(search_wait(ss, st));      /* (the work list is reused by the next chunk) */
-			}
-			}
-			HIP_TRY(hipMemcpyAsync(h_ncand, ss->d_ncand.p, n1 * 4, hipMemcpyDeviceToHost, st));
-			RC_TRY(search_wait(ss, st));
-			if (!lane_serial) ss->tables_clean_words = ss->d_keys.cap;      /* the launch ended: every wave left its table empty */
-			for (int32_t i : hbm_now) if (h_ncand[i] < 0) next_hbm.push_back(i);
-			if (trace) { char b[160]; snprintf(b, sizeof(b), " [bits %d hbm %zu (%llu votes in the call) -> %zu retry, at %.2f ms]", bits, hbm_now.size(), (unsigned long long) total, next_hbm.size(), tr_ms()); tr += b; }
-		}
-		work_wave.swap(next_wave);
-		work_hbm.swap(next_hbm);
-	}
-	/* (a read that left the ladder without a list keeps -1; one still flagged for the HBM kernel cannot remain: it was redone in its attempt) */
-	/* dense candidate list in read order, compacted on the device: only the entries come back (the sparse arena is
-	 * two slots per vote) */
-	uint64_t need = 0;
-	for (int i = 0; i < n; ++i) { h_begin[i] = need; cand_begin[i] = need; n_candidates[i] = h_ncand[i]; if (h_ncand[i] > 0) need += (uint64_t) h_ncand[i]; }
-	h_begin[n] = need;              /* (plan_candidate_windows_kernel's end of the last list) */
-	if (cand_used) *cand_used = need;
-	/* (the launchers behind the compaction count slots in an int; refused here, where nothing of the call is queued any more) */
-	if (fs && need > 0x7fffffffull) { set_err("cvx_search_score_arena: %llu candidates in one call", (unsigned long long) need); return CVX_ERR_ARG; }
-	if (max_hit || kmer_misses) {
-		HIP_TRY(hipMemcpyAsync(h_maxhit, ss->d_maxhit.p, n1 * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(h_miss, ss->d_miss.p, n1 * 4, hipMemcpyDeviceToHost, st));
-	}
-	if (need > cand_capacity || (need > 0 && !cands)) {
-		if (max_hit || kmer_misses) RC_TRY(search_wait(ss, st));
-		set_err("cvx_search_batch: candidate arena too small (%llu needed, %llu given)", (unsigned long long) need, (unsigned long long) cand_capacity);
-		return CVX_ERR_CAPACITY;
-	}
-	if (need) {
-		RC_TRY(ss->d_dense.ensure((size_t) need + 64));
-		HIP_TRY(hipMemcpyAsync(ss->d_begin.p, h_begin, (n1 + 1) * 8, hipMemcpyHostToDevice, st));
-		HIP_TRY(hipMemcpyAsync(ss->d_srcoff.p, h_srcoff, n1 * 8, hipMemcpyHostToDevice, st));
-		RC_TRY(ss->kmark(st));
-		HIP_TRY(launch_search_compact(ss->d_cand.p, ss->d_srcoff.p, ss->d_ncand.p, ss->d_begin.p, ss->d_dense.p, n, st));
-		RC_TRY(ss->kmark(st));
-		if (fs) {
-			/* The scoring of every candidate, queued behind the compaction: the lists are planned where they lie (d_dense), the
-			 * strings come from the resident genome and from the read block the vote has just used, and both launchers run over all
-			 * `need` slots -- a candidate that is not scored is two empty strings there.  Nothing is uploaded. */
-			const CandWinSlots slots = cand_windows_slots(fs->buffer_len, fs->max_read_bytes, need);
-			RC_TRY(ss->d_fdesc.ensure((size_t) need)); RC_TRY(ss->d_fpairs.ensure((size_t) need));
-			RC_TRY(ss->d_fout.ensure((size_t) need)); RC_TRY(ss->d_fstatus.ensure((size_t) need));
-			RC_TRY(ss->d_fseq.ensure((size_t) slots.seq_bytes + 256));
-			RC_TRY(ss->h_fout.ensure((size_t) need * 8));
-			HIP_TRY(ss->ev_f0.make());
-			HIP_TRY(ss->ev_f1.make());
-			HIP_TRY(hipEventRecord(ss->ev_f0, st));
-			HIP_TRY(launch_plan_candidate_windows(ss->d_dense.p, ss->d_begin.p, ss->d_ncand.p, ss->d_off.p, ss->d_len.p, n, need,
-					score_windows_concat_len(fs->g->n_nibbles), fs->buffer_len, fs->window_lead, fs->max_cmrs, slots, ss->d_fdesc.p, ss->d_fstatus.p, st));
-			HIP_TRY(launch_stage_score_windows(fs->g->d_bin.p, ss->d_seq.p, ss->d_fdesc.p, (int) need, ss->d_fseq.p, ss->d_fpairs.p, st));
-			HIP_TRY(launch_score_diag(ss->d_fseq.p, ss->d_fpairs.p, ss->d_fout.p, (int) need, st));
-			HIP_TRY(hipEventRecord(ss->ev_f1, st));
-		}
-		/* (straight into the caller's memory: pageable unless it came from cvx_host_alloc, then the copy is staged by the runtime) */
-		HIP_TRY(hipMemcpyAsync(cands, ss->d_dense.p, (size_t) need * sizeof(SearchCandidate), hipMemcpyDeviceToHost, st));
-		if (fs) {
-			HIP_TRY(hipMemcpyAsync(ss->h_fout.p, ss->d_fout.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
-			HIP_TRY(hipMemcpyAsync(ss->h_fout.as<uint8_t>() + (size_t) need * 4, ss->d_fstatus.p, (size_t) need * 4, hipMemcpyDeviceToHost, st));
-		}
-	}
-	RC_TRY(search_wait(ss, st));
-	for (size_t q = 0; q + 1 < ss->kev_used; q += 2) ss->kernel_ms += ev_ms(ss->kev[q], ss->kev[q + 1]);
-	if (fs && need) {
-		ss->fused_ms = ev_ms(ss->ev_f0, ss->ev_f1);
-		const float *o = ss->h_fout.as<float>();
-		const int32_t *os = reinterpret_cast<const int32_t *>(o + need);
-		for (uint64_t q = 0; q < need; ++q) fs->sw_scores[q] = os[q] == kCandScored ? o[q] : -1.0f;
-		if (fs->sw_status) memcpy(fs->sw_status, os, (size_t) need * 4);
-	}
-	if (trace) fprintf(stderr, "cvx_search_batch: %d reads, %llu bases, %llu candidates, %.2f ms:%s\n", n, (unsigned long long) bytes - (unsigned long long) n, (unsigned long long) need, tr_ms(), tr.c_str());
-	if (max_hit) memcpy(max_hit, h_maxhit, n1 * 4);
-	if (kmer_misses) memcpy(kmer_misses, h_miss, n1 * 4);
-	return CVX_OK;
+	SearchCall c(h, n);
+	RC_TRY(c.stage_reads(seqs, lens, arena, offsets));
+	RC_TRY(c.upload(ix, sensitivity, min_hits, bin_shift));
+	if (c.classify) RC_TRY(c.count_votes());
+	RC_TRY(c.assign_maps());
+	RC_TRY(c.climb(first_bits));
+	return c.bring_back(fs, n_candidates, cand_begin, cands, cand_capacity, cand_used, max_hit, kmer_misses);
 }
 
 extern "C" {

@@ -121,9 +121,12 @@ def test_device_search_corners_against_the_checker(hip_aligner, search_kernel):
     ix = KmerIndex(hip_aligner, fx.k, idx, locs, 0)
     try:
         got, max_hit, misses = ix.search(reads, extras=True)
+        attempts = ix.last_attempts(len(reads))
         got2 = ix.search(reads, sensitivity=0.5, min_kmer_hits=2.0, bin_shift=2)
         got10, max_hit10, misses10 = ix.search(reads, first_bits=10, extras=True)
+        attempts10 = ix.last_attempts(len(reads))
         got8, max_hit8, misses8 = ix.search(reads, first_bits=8, extras=True)
+        attempts8 = ix.last_attempts(len(reads))
     finally:
         ix.free()
     # what CS::RunRead leaves behind beside the list: maxHitNumber, and kCount summed over the attempts of the ladder
@@ -146,6 +149,14 @@ def test_device_search_corners_against_the_checker(hip_aligner, search_kernel):
     assert [float(m) for m in max_hit8] == [float(np.float32(w["max_hit"])) for w in want8]
     assert max(w["kmer_misses"] for w in want) >= 200 and any(w["table_bits"] > 16 and w["kmer_misses"] > 0 for w in want)   # foreign k-mers, also on a read that climbed the ladder
     assert max(w["table_bits"] for w in want if w["n"] >= 0) > 16            # the retry ladder was climbed
+    assert max(w["table_bits"] for w in want10 if w["n"] >= 0) > 10
+    assert max(w["table_bits"] for w in want8 if w["n"] >= 0) > 8
+    # cvx_search_last_attempts: one count per attempt a read took part in -- the first size, then that + 2, + 3, ... (oracle/cs_oracle.c:
+    # 226-261) -- and a read that moves from the LDS map to the table in HBM inside an attempt is counted once.  Of the reads that got a list
+    for first, ws, att in ((16, want, attempts), (10, want10, attempts10), (8, want8, attempts8)):
+        for i, w in enumerate(ws):
+            if w["n"] >= 0:
+                assert int(att[i]) == (1 if w["table_bits"] == first else w["table_bits"] - first), (first, i, int(att[i]), w["table_bits"])
     for i, (w, g) in enumerate(zip(want, got)):
         if w["n"] < 0:
             assert g is None, i
