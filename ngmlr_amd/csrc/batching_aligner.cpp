@@ -63,7 +63,7 @@ namespace Convex {
 BatchingAligner::BatchingAligner(ConvexAlignHip * be, int nWorkers, int maxB, int tmoUs) :
 		backend(be), workers(nWorkers >= 0 ? nWorkers : 1), parked(0),
 		maxBatch(maxB > 0 ? maxB : 1), timeoutUs(tmoUs), stop(false), launches(0), requests(0), maxInFlight(0),
-		target(0), holdUs(20000), feedActive(true), textLaunches(0), textNs(0), launchTrace(false), deviceText(false), parkedNs(0), finishNs(0), busyNs(0), maxFlight(2), emaServiceUs(0.0), leadUs(3000), textPending(0), textStop(false), maxTextAhead(4) {
+		target(0), holdUs(20000), feedActive(true), textLaunches(0), textNs(0), ladderOn(true), ladderRequests(0), ladderClimbed(0), ladderUnresolved(0), ladderLaunches(0), launchTrace(false), deviceText(false), parkedNs(0), finishNs(0), busyNs(0), maxFlight(2), emaServiceUs(0.0), leadUs(3000), textPending(0), textStop(false), maxTextAhead(4) {
 	if (const char * e = getenv("CVX_BATCH_TARGET")) target = atoi(e) > 0 ? atoi(e) : 0;
 	if (const char * e = getenv("CVX_BATCH_HOLD_US")) holdUs = atoi(e) > 0 ? atoi(e) : 0;
 	if (const char * e = getenv("CVX_BATCH_LEAD_US")) leadUs = atoi(e);      /* < 0: the plain timeout rule while a launch runs */
@@ -72,6 +72,7 @@ BatchingAligner::BatchingAligner(ConvexAlignHip * be, int nWorkers, int maxB, in
 	if (const char * e = getenv("CVX_BATCH_INFLIGHT")) maxFlight = atoi(e) > 0 ? atoi(e) : 1;
 	if (const char * e = getenv("CVX_DEVICE_TEXT")) deviceText = atoi(e) != 0;
 	if (const char * e = getenv("CVX_LAUNCH_TRACE")) launchTrace = atoi(e) != 0;
+	if (const char * e = getenv("CVX_DEVICE_LADDER")) ladderOn = atoi(e) != 0;
 	if (const char * e = getenv("CVX_TEXT_AHEAD")) maxTextAhead = atoi(e) > 0 ? atoi(e) : 1;
 	dispatcher = std::thread([this] { dispatchLoop(); });
 	if (deviceText) textThread = std::thread([this] { textLoop(); });
@@ -223,20 +224,36 @@ void BatchingAligner::dispatchLoop() {
 		if (canSubmit && shouldCut(inFlight.empty())) {
 			Launch * l = new Launch();
 			l->job = 0; l->results = 0; l->ops = 0; l->failed = false; l->text = 0; l->haveRegions = false; l->haveTexts = false; l->submitMs = l->waitMs = 0.0;
-			size_t const take = std::min(queue.size(), (size_t) maxBatch);
+			l->ladder = queue.front()->ladder; l->ladders = 0;
 			l->oldestAt = oldest;
 			l->cutAt = std::chrono::steady_clock::now();
-			l->reqs.assign(queue.begin(), queue.begin() + (long) take);
-			queue.erase(queue.begin(), queue.begin() + (long) take);
-			if (!queue.empty()) oldest = std::chrono::steady_clock::now();
+			/* a launch is of one kind, the oldest request's: up to maxBatch requests of that kind in arrival order; the others keep
+			 * their place, and the first of them the time it arrived */
+			bool skipped = false;
+			{
+				size_t kept = 0;
+				for (size_t i = 0; i < queue.size(); ++i) {
+					if (queue[i]->ladder == l->ladder && l->reqs.size() < (size_t) maxBatch) l->reqs.push_back(queue[i]);
+					else { if (kept == 0) skipped = queue[i]->ladder != l->ladder; queue[kept++] = queue[i]; }
+				}
+				queue.resize(kept);
+			}
+			if (!queue.empty()) oldest = skipped ? queue.front()->arrived : std::chrono::steady_clock::now();
 			l->unfinished = (int) l->reqs.size();
 			for (Request * r : l->reqs) r->launch = l;
 			launches += 1;
+			if (l->ladder) ladderLaunches += 1;
 			lk.unlock();
-			std::vector<ConvexAlignHip::Tile> tiles(l->reqs.size());
-			for (size_t i = 0; i < tiles.size(); ++i) tiles[i] = l->reqs[i]->tile;
 			try {
-				l->job = backend->Submit(tiles.data(), (int) tiles.size());
+				if (l->ladder) {
+					std::vector<ConvexAlignHip::LadderTile> tiles(l->reqs.size());
+					for (size_t i = 0; i < tiles.size(); ++i) tiles[i] = l->reqs[i]->ltile;
+					l->job = backend->SubmitLadders(tiles.data(), (int) tiles.size());
+				} else {
+					std::vector<ConvexAlignHip::Tile> tiles(l->reqs.size());
+					for (size_t i = 0; i < tiles.size(); ++i) tiles[i] = l->reqs[i]->tile;
+					l->job = backend->Submit(tiles.data(), (int) tiles.size());
+				}
 			} catch (...) {
 				l->failed = true;
 			}
@@ -253,7 +270,10 @@ void BatchingAligner::dispatchLoop() {
 			 * into the second launch -- whose upload and corridor analysis then run under its kernels -- as soon as
 			 * one of the rules fires. */
 			Launch * l = inFlight.front();
-			bool const block = l->failed || (int) inFlight.size() >= maxFlight || parked >= workers;
+			/* A ladder job climbs only where somebody asks: cvx_job_poll advances every climber of the handle, cvx_wait's blocking
+			 * path only the job waited for.  So while any launch in flight is a ladder job the dispatcher never blocks in Wait for
+			 * an unfinished one -- it polls, and enters Wait once the poll has said that the job is done. */
+			bool const block = l->failed || (!ladderInFlight() && ((int) inFlight.size() >= maxFlight || parked >= workers));
 			if (!block) {
 				lk.unlock();
 				bool const done = backend->Poll(l->job);
@@ -269,6 +289,7 @@ void BatchingAligner::dispatchLoop() {
 				try {
 					std::chrono::steady_clock::time_point const tw = std::chrono::steady_clock::now();
 					backend->Wait(l->job, &l->results, &l->ops);
+					if (l->ladder) backend->Ladders(l->job, &l->ladders);
 					l->haveRegions = !deviceText && backend->Regions(l->job, l->regions);      /* (they came back inside that wait) */
 					l->haveTexts = l->haveRegions && backend->JobTexts(l->job, l->texts);      /* (as did these) */
 					if (launchTrace) {
@@ -295,7 +316,7 @@ void BatchingAligner::dispatchLoop() {
 				/* a launch of windows decoded on the device (window_decode_binding.inc): its workers' host text stage reads the
 				 * characters that came back with the results (they are parked: nobody else touches their tiles) */
 				std::vector<ConvexAlignHip::Tile *> tp(l->reqs.size());
-				for (size_t i = 0; i < tp.size(); ++i) tp[i] = &l->reqs[i]->tile;
+				for (size_t i = 0; i < tp.size(); ++i) tp[i] = l->ladder ? &l->reqs[i]->ltile.resolved : &l->reqs[i]->tile;
 				lk.unlock();
 				bool refsFailed = false;
 				try {
@@ -323,25 +344,21 @@ void BatchingAligner::dispatchLoop() {
 	}
 }
 
-int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int const corridorHeight,
-		char const * const refSeq, char const * const qrySeq, Align & result,
-		int const externalQStart, int const externalQEnd, void * extData) {
-	(void) mode; (void) extData;
-	Request req;
-	req.tile.corridor = corridor; req.tile.corridorHeight = corridorHeight;
-	req.tile.refSeq = refSeq; req.tile.qrySeq = qrySeq; req.tile.result = &result;
-	req.tile.externalQStart = externalQStart; req.tile.externalQEnd = externalQEnd; req.tile.ret = -1; req.tile.failed = false;
-	req.launch = 0; req.result = 0; req.done = false; req.failed = false;
-	req.fiber = FiberApi::Current();
-	ConvexAlignHip::Prepare(req.tile, backend->ScalarTwin());       /* in the caller's thread; throws like the reference for a malformed call */
+/* with mtx held */
+bool BatchingAligner::ladderInFlight() const {
+	for (Launch const * l : inFlight) if (l->ladder && !l->failed) return true;
+	return false;
+}
 
-	std::unique_lock<std::mutex> lk(mtx);
-	if (queue.empty()) oldest = std::chrono::steady_clock::now();
+/* with mtx held: the request joins the queue and its caller sleeps until the dispatcher (or the text thread) has completed its launch */
+void BatchingAligner::park(Request & req, std::unique_lock<std::mutex> & lk) {
+	std::chrono::steady_clock::time_point const t0 = std::chrono::steady_clock::now();
+	req.arrived = t0;
+	if (queue.empty()) oldest = t0;
 	queue.push_back(&req);
 	requests += 1;
 	parked += 1;
 	cvDispatch.notify_one();
-	std::chrono::steady_clock::time_point const t0 = std::chrono::steady_clock::now();
 	if (req.fiber) {
 		/* the read gives its carrier thread back while its tile is in flight; the dispatcher's Wake makes it runnable there */
 		while (!req.done) {
@@ -352,9 +369,70 @@ int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int co
 	} else {
 		while (!req.done) req.cv.wait(lk);
 	}
-	std::chrono::steady_clock::time_point const t1 = std::chrono::steady_clock::now();
-	parkedNs += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+	parkedNs += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
 	parked -= 1;
+}
+
+bool BatchingAligner::SingleLadder(char const * refSeq, char const * qrySeq, Align & result, int const externalQStart, int const externalQEnd,
+		cvx_ladder const & ladder, int & ret, int & rung, int & attempts, int & width) {
+	if (!TakesLadders()) return false;      /* the caller runs the reference's loop */
+	Request req;
+	memset(&req.ltile, 0, sizeof(req.ltile));
+	req.ltile.refSeq = refSeq; req.ltile.qrySeq = qrySeq; req.ltile.result = &result;
+	req.ltile.externalQStart = externalQStart; req.ltile.externalQEnd = externalQEnd;
+	req.ltile.ladder = ladder;
+	req.launch = 0; req.result = 0; req.done = false; req.failed = false; req.ladder = true;
+	req.fiber = FiberApi::Current();
+	ConvexAlignHip::PrepareLadder(req.ltile);       /* in the caller's context, where a window's note lives; throws for a malformed call */
+
+	std::unique_lock<std::mutex> lk(mtx);
+	park(req, lk);
+	std::chrono::steady_clock::time_point const t1 = std::chrono::steady_clock::now();
+	Launch * l = req.launch;
+	bool const failed = req.failed;
+	cvx_result const * r = req.result;
+	lk.unlock();
+
+	/* this request's text stage, in this caller's thread, out of the launch's buffers */
+	bool threw = failed;
+	if (!failed) {
+		try {
+			int const index = (int) (r - l->results);
+			backend->FinishLadder(req.ltile, *r, l->ops, l->ladders[index], l->haveRegions ? &l->regions : 0, index, l->haveTexts ? &l->texts : 0);
+		} catch (...) {
+			threw = true;
+		}
+	}
+	lk.lock();
+	finishNs += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t1).count();
+	ladderRequests += 1;
+	if (!threw && req.ltile.attempts >= 2) ladderClimbed += 1;
+	if (!threw && req.ltile.ret < 0) ladderUnresolved += 1;
+	if (--l->unfinished == 0) {
+		retired.push_back(l);
+		cvDispatch.notify_one();
+	}
+	lk.unlock();
+	if (threw) throw 1;
+	ret = req.ltile.ret; rung = req.ltile.rung; attempts = req.ltile.attempts; width = req.ltile.width;
+	return true;
+}
+
+int BatchingAligner::SingleAlign(int const mode, CorridorLine * corridor, int const corridorHeight,
+		char const * const refSeq, char const * const qrySeq, Align & result,
+		int const externalQStart, int const externalQEnd, void * extData) {
+	(void) mode; (void) extData;
+	Request req;
+	req.tile.corridor = corridor; req.tile.corridorHeight = corridorHeight;
+	req.tile.refSeq = refSeq; req.tile.qrySeq = qrySeq; req.tile.result = &result;
+	req.tile.externalQStart = externalQStart; req.tile.externalQEnd = externalQEnd; req.tile.ret = -1; req.tile.failed = false;
+	req.launch = 0; req.result = 0; req.done = false; req.failed = false; req.ladder = false;
+	req.fiber = FiberApi::Current();
+	ConvexAlignHip::Prepare(req.tile, backend->ScalarTwin());       /* in the caller's thread; throws like the reference for a malformed call */
+
+	std::unique_lock<std::mutex> lk(mtx);
+	park(req, lk);
+	std::chrono::steady_clock::time_point const t1 = std::chrono::steady_clock::now();
 	Launch * l = req.launch;
 	bool const failed = req.failed;
 	cvx_result const * r = req.result;
@@ -473,6 +551,8 @@ SharedAligner::~SharedAligner() {
 		g_lastBusy += g_shared[device]->BusySeconds();
 		g_lastTextLaunches += g_shared[device]->TextLaunches();
 		g_lastTextSeconds += g_shared[device]->TextSeconds();
+		fprintf(stderr, "SharedAligner: device %d: %ld ladder requests, %ld with attempts >= 2, %ld reported a failed last rung, %ld ladder launches (CVX_DEVICE_LADDER=0 turns that off)\n",
+				device, g_shared[device]->LadderRequests(), g_shared[device]->LadderClimbed(), g_shared[device]->LadderUnresolved(), g_shared[device]->LadderLaunches());
 		delete g_shared[device]; g_shared[device] = 0;
 		delete g_backend[device]; g_backend[device] = 0;
 	}
@@ -519,6 +599,11 @@ int SharedAligner::SingleAlign(int const mode, CorridorLine * corridor, int cons
 		char const * const refSeq, char const * const qrySeq, Align & result,
 		int const externalQStart, int const externalQEnd, void * extData) {
 	return shared->SingleAlign(mode, corridor, corridorHeight, refSeq, qrySeq, result, externalQStart, externalQEnd, extData);
+}
+
+bool SharedAligner::SingleLadder(char const * refSeq, char const * qrySeq, Align & result, int const externalQStart, int const externalQEnd,
+		cvx_ladder const & ladder, int & ret, int & rung, int & attempts, int & width) {
+	return shared->SingleLadder(refSeq, qrySeq, result, externalQStart, externalQEnd, ladder, ret, rung, attempts, width);
 }
 
 long SharedAligner::Launches() {

@@ -49,7 +49,7 @@
 
 namespace Convex {
 
-class BatchingAligner: public IAlignment {
+class BatchingAligner: public IAlignment, public LadderAligner {
 public:
 	/* backend is owned by the caller.  maxBatch: cut a launch when this many requests wait;
 	 * timeoutUs: cut one when the oldest request has waited this long (0 = only the other rules). */
@@ -68,6 +68,16 @@ public:
 	virtual int SingleAlign(int const mode, CorridorLine * corridor, int const corridorHeight,
 			char const * const refSeq, char const * const qrySeq, Align & result,
 			int const externalQStart, int const externalQEnd, void * extData);
+
+	/* computeAlignment's whole retry ladder as one request (LadderAligner, convex_align_hip.h; ladder_binding.inc).  false, nothing
+	 * done, when this aligner cannot take ladders: CVX_DEVICE_LADDER=0, or CVX_DEVICE_TEXT=1 (cvx_job_text* and cvx_job_nm_*
+	 * refuse a ladder job).  Otherwise it behaves like SingleAlign: PrepareLadder in the caller's context, the request queued,
+	 * the caller parked (fiber or thread), FinishLadder in the caller's thread out of the launch's buffers, the last finisher
+	 * retires the launch.  A launch is of one kind: the cut takes the kind of the oldest queued request and up to maxBatch
+	 * requests of that kind in arrival order; the others keep their place and the time they arrived. */
+	virtual bool SingleLadder(char const * refSeq, char const * qrySeq, Align & result, int const externalQStart, int const externalQEnd,
+			cvx_ladder const & ladder, int & ret, int & rung, int & attempts, int & width);
+	bool TakesLadders() const { return ladderOn && !deviceText; }
 
 	/* a worker that stops calling (end of input) must say so, or the "everybody is parked"
 	 * rule would wait for it */
@@ -91,6 +101,12 @@ public:
 	double ParkedSeconds() const { return parkedNs * 1e-9; }
 	double FinishSeconds() const { return finishNs * 1e-9; }
 	double BusySeconds() const { return busyNs * 1e-9; }
+	/* ladder requests, those that made two attempts or more, those whose reported rung failed too, and the launches they travelled in
+	 * (which Launches() counts as well) */
+	long LadderRequests() const { return ladderRequests; }
+	long LadderClimbed() const { return ladderClimbed; }
+	long LadderUnresolved() const { return ladderUnresolved; }
+	long LadderLaunches() const { return ladderLaunches; }
 	long TextLaunches() const { return textLaunches; }        /* launches whose text stage ran on the device (CVX_DEVICE_TEXT=1) */
 	double TextSeconds() const { return textNs * 1e-9; }      /* the dispatcher's time in those calls */
 
@@ -98,6 +114,9 @@ private:
 	struct Launch;
 	struct Request {
 		ConvexAlignHip::Tile tile;
+		bool ladder;                       /* a SingleLadder request: ltile in place of tile */
+		ConvexAlignHip::LadderTile ltile;
+		std::chrono::steady_clock::time_point arrived;
 		Launch * launch;                   /* set when the dispatcher has taken the request */
 		cvx_result const * result;         /* set when the launch is done */
 		bool done;
@@ -115,6 +134,8 @@ private:
 		double submitMs, waitMs;            /* CVX_LAUNCH_TRACE: the dispatcher's time inside Submit (tile table + cvx_submit) and blocked in Wait */
 		int unfinished;                    /* workers still writing their text out of this launch's buffers */
 		bool failed;
+		bool ladder;                       /* a ladder job (SubmitLadders): every request of it is one */
+		cvx_ladder_result const * ladders; /* its cvx_job_ladder records */
 		ConvexAlignHip::JobText * text;    /* CVX_DEVICE_TEXT=1: the launch's text stage ran on the device (else 0) */
 		ConvexAlignHip::JobRegions regions; /* a backend with NmRegions(): the launch's regions, for the requests among its tiles (Finish) */
 		bool haveRegions;
@@ -136,6 +157,8 @@ private:
 	int holdUs;                                 /* wait for it (CVX_BATCH_HOLD_US) */
 	bool feedActive;                            /* see SetFeedActive (true until told otherwise) */
 	long textLaunches; long long textNs;
+	bool ladderOn;                              /* unless CVX_DEVICE_LADDER=0 */
+	long ladderRequests, ladderClimbed, ladderUnresolved, ladderLaunches;      /* under mtx */
 	bool launchTrace;                           /* CVX_LAUNCH_TRACE=1: one stderr line per finished launch */
 	bool deviceText;                            /* CVX_DEVICE_TEXT=1: cvx_job_text + cvx_job_nm_profile per launch instead of one
 	                                             * host text stage per request on the workers (measured: DESIGN.md 6) */
@@ -161,6 +184,8 @@ private:
 
 	void dispatchLoop();
 	void textLoop();
+	void park(Request & req, std::unique_lock<std::mutex> & lk);      /* with mtx held: queues the request and sleeps until its launch is done */
+	bool ladderInFlight() const;           /* with mtx held: a ladder job among the launches in flight */
 	void completeLaunch(Launch * l);       /* with mtx held: hands every request of the launch its result and wakes it */
 	bool shouldCut(bool deviceIdle) const;
 };
@@ -176,7 +201,7 @@ private:
  * its pair, the last one to go deletes it; the very last one prints the launch statistics.  Scoring parameters are those of the
  * first construction (every worker passes the same Config values).
  */
-class SharedAligner: public IAlignment {
+class SharedAligner: public IAlignment, public LadderAligner {
 public:
 	SharedAligner(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = -1 /* -1: workers are dealt over all devices */,
@@ -196,6 +221,9 @@ public:
 	virtual int SingleAlign(int const mode, CorridorLine * corridor, int const corridorHeight,
 			char const * const refSeq, char const * const qrySeq, Align & result,
 			int const externalQStart, int const externalQEnd, void * extData);
+
+	virtual bool SingleLadder(char const * refSeq, char const * qrySeq, Align & result, int const externalQStart, int const externalQEnd,
+			cvx_ladder const & ladder, int & ret, int & rung, int & attempts, int & width);
 
 	/* statistics of the process-wide aligner (0 when none exists) */
 	static long Launches();

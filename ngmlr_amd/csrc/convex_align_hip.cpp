@@ -554,41 +554,78 @@ void ConvexAlignHip::AlignTiles(Tile * tiles, int n) {
 	Release(job);
 }
 
-void ConvexAlignHip::AlignLadders(LadderTile * tiles, int n) {
-	if (n <= 0) return;
-	/* the requests as Tiles without a corridor: the strings resolved the way Prepare resolves them (windows and read placeholders
-	 * of a binding included), so that the launch takes Submit's forms and the tiles finish the way AlignTiles finishes them */
-	std::vector<Tile> ts((size_t) n);
-	std::vector<cvx_ladder> lad((size_t) n);
-	packed.resize((size_t) n);
+/* the request as a Tile without a corridor: the strings resolved the way Prepare resolves them (windows and read placeholders of a
+ * binding included), in the calling context, so that the launch takes Submit's forms and the tile finishes the way Finish
+ * finishes any */
+void ConvexAlignHip::PrepareLadder(LadderTile & lt) {
+	lt.ret = -1; lt.failed = false; lt.rung = lt.attempts = lt.width = 0;
+	if (lt.refSeq == 0 || lt.qrySeq == 0 || lt.result == 0) {
+		fprintf(stderr, "ConvexAlignHip: a ladder request without its strings or its Align\n");
+		throw 1;
+	}
+	Tile & t = lt.resolved;
+	memset(&t, 0, sizeof(t));
+	t.refSeq = lt.refSeq; t.qrySeq = lt.qrySeq; t.result = lt.result;
+	t.externalQStart = lt.externalQStart; t.externalQEnd = lt.externalQEnd;
+	t.ret = -1;
+	resolveSequences(t);
+	t.corridorHeight = t.qryLen;
+	/* what cvx_submit_ladder would refuse for the whole launch (an unknown flag, a negative corridor, left / right out of range)
+	 * is this caller's error alone */
+	cvx_tile probe, form;
+	memset(&probe, 0, sizeof(probe));
+	memset(&form, 0, sizeof(form));
+	probe.ref_len = t.refLen; probe.qry_len = t.qryLen;
+	if (cvx_ladder_rung(&probe, &lt.ladder, 1, &form) < 0) {
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+}
+
+cvx_job ConvexAlignHip::SubmitLadders(LadderTile const * tiles, int n) {
+	std::vector<Tile> ts((size_t) (n > 0 ? n : 0));
+	std::vector<cvx_ladder> lad((size_t) (n > 0 ? n : 0));
+	packed.resize((size_t) (n > 0 ? n : 1));
 	for (int i = 0; i < n; ++i) {
-		Tile & t = ts[(size_t) i];
-		memset(&t, 0, sizeof(t));
-		t.refSeq = tiles[i].refSeq; t.qrySeq = tiles[i].qrySeq; t.result = tiles[i].result;
-		t.externalQStart = tiles[i].externalQStart; t.externalQEnd = tiles[i].externalQEnd;
-		t.ret = -1;
-		resolveSequences(t);
-		t.corridorHeight = t.qryLen;
+		Tile const & t = ts[(size_t) i] = tiles[i].resolved;
 		cvx_tile & c = packed[(size_t) i];
 		memset(&c, 0, sizeof(c));
 		c.ref = t.refSeq; c.qry = t.qrySeq;
 		c.ref_len = t.refLen; c.qry_len = t.qryLen;
 		c.row_stride_bytes = 4;
 		lad[(size_t) i] = tiles[i].ladder;
-		tiles[i].ret = -1; tiles[i].failed = false; tiles[i].rung = tiles[i].attempts = tiles[i].width = 0;
 	}
-	cvx_job job = submitPacked(ts.data(), n, lad.data());
+	return submitPacked(ts.data(), n, lad.data());
+}
+
+void ConvexAlignHip::Ladders(cvx_job job, cvx_ladder_result const ** out) {
+	if (cvx_job_ladder(handle, job, out) != CVX_OK) {
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+}
+
+void ConvexAlignHip::FinishLadder(LadderTile & lt, cvx_result const & r, uint32_t const * ops, cvx_ladder_result const & lr, JobRegions const * jr, int index, JobTextView const * jx) const {
+	lt.rung = lr.rung; lt.attempts = lr.attempts; lt.width = lr.width;
+	Finish(lt.resolved, r, ops, jr, index, jx);
+	lt.ret = lt.resolved.ret;
+}
+
+void ConvexAlignHip::AlignLadders(LadderTile * tiles, int n) {
+	if (n <= 0) return;
+	for (int i = 0; i < n; ++i) PrepareLadder(tiles[i]);
+	cvx_job job = SubmitLadders(tiles, n);
 	cvx_result const * res = 0;
 	uint32_t const * ops = 0;
 	cvx_ladder_result const * lr = 0;
 	std::vector<Tile *> ptrs((size_t) n);
-	for (int i = 0; i < n; ++i) ptrs[(size_t) i] = &ts[(size_t) i];
+	for (int i = 0; i < n; ++i) ptrs[(size_t) i] = &tiles[i].resolved;
 	JobRegions jr;
 	JobTextView jx;
 	bool haveRegions = false, haveTexts = false;
 	try {
 		Wait(job, &res, &ops);
-		if (cvx_job_ladder(handle, job, &lr) != CVX_OK) { fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error()); throw 1; }
+		Ladders(job, &lr);
 		(void) WindowRefs(job, ptrs.data(), n);      /* windows decoded on the device: the host text stage reads what came back */
 		haveRegions = Regions(job, jr);
 		haveTexts = JobTexts(job, jx);
@@ -597,11 +634,8 @@ void ConvexAlignHip::AlignLadders(LadderTile * tiles, int n) {
 		throw;
 	}
 	for (int i = 0; i < n; ++i) {
-		Tile & t = ts[(size_t) i];
-		tiles[i].rung = lr[i].rung; tiles[i].attempts = lr[i].attempts; tiles[i].width = lr[i].width;
 		try {
-			Finish(t, res[i], ops, haveRegions ? &jr : 0, i, haveTexts ? &jx : 0);
-			tiles[i].ret = t.ret;
+			FinishLadder(tiles[i], res[i], ops, lr[i], haveRegions ? &jr : 0, i, haveTexts ? &jx : 0);
 		} catch (...) {
 			tiles[i].failed = true;
 			tiles[i].ret = -1;

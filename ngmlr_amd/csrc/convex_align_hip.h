@@ -96,6 +96,8 @@ public:
 	 * a failure of the launch itself throws. */
 	void AlignTiles(Tile * tiles, int n);
 
+	struct JobRegions;
+	struct JobTextView;
 	/* One request of AlignLadders(): what AlignmentBuffer::computeAlignment's retry loop reads (src/AlignmentBuffer.cpp:259-425)
 	 * in place of one CorridorLine[] -- see cvx_ladder, include/cvx_align.h. */
 	struct LadderTile {
@@ -108,6 +110,9 @@ public:
 		int ret;               /* out: the reference's cigarLength of the rung reported, or -1 */
 		bool failed;           /* out: this tile hit a hard error */
 		int rung, attempts, width;      /* out: the rung reported (1-based), the attempts made, that rung's corridor width */
+		/* filled by PrepareLadder(): the request as a Tile without a corridor -- placeholders recognised, refLen / qryLen -- which
+		 * SubmitLadders packs and FinishLadder finishes the way Finish finishes any tile */
+		Tile resolved;
 	};
 	/* n retry ladders in one device job (cvx_submit_ladder; cvx_submit_ladder_ex on an aligner constructed with nmRegions and / or
 	 * jobText, and for the placeholder forms below): every tile's corridor is rebuilt at multiplier 2, 3, ... and aligned again on
@@ -118,6 +123,19 @@ public:
 	 * placeholder -- the genome form; every qrySeq a DeviceReads placeholder -- the segments form, distinct reads sent once; a
 	 * mix is materialised on the host.  Hard errors as for AlignTiles. */
 	void AlignLadders(LadderTile * tiles, int n);
+	/* The same in stages, as AlignTiles has them (below), for a driver that gathers a launch from many calling contexts
+	 * (batching_aligner.h).  Poll, Wait, Regions, JobTexts, WindowRefs (on &tile.resolved) and Release work on the job as on any.
+	 *   PrepareLadder  any thread, the CALLER's: recognises the DeviceWindows / DeviceReads placeholders where a window's note
+	 *                  lives and takes the lengths; throws 1 for a malformed call (no strings, no Align, a ladder cvx_ladder_rung
+	 *                  refuses).  No corridor is fitted and no CorridorLine is touched: there is none
+	 *   SubmitLadders  the device thread: one ladder job of n prepared tiles, in the input form Submit would choose
+	 *   Ladders        after Wait: the job's cvx_job_ladder records, valid until Release
+	 *   FinishLadder   any thread: one tile's Align out of the job's buffers as Finish leaves it for the rung reported, and
+	 *                  ret / rung / attempts / width; throws 1 for that tile's hard errors */
+	static void PrepareLadder(LadderTile & t);
+	cvx_job SubmitLadders(LadderTile const * tiles, int n);
+	void Ladders(cvx_job job, cvx_ladder_result const ** out);
+	void FinishLadder(LadderTile & t, cvx_result const & r, uint32_t const * ops, cvx_ladder_result const & lr, JobRegions const * jr = 0, int index = 0, JobTextView const * jx = 0) const;
 
 	/* The same in stages, for a driver that keeps launches in flight.  Prepare / Finish may run on any thread (they
 	 * touch only the tile and the caller's Align); Submit / Wait / Release belong to the ONE thread that owns this
@@ -190,7 +208,7 @@ public:
 
 private:
 	static void resolveSequences(Tile & t);      /* Prepare's first half: placeholders recognised, refLen / qryLen */
-	cvx_job submitPacked(Tile const * tiles, int n, cvx_ladder const * ladders);      /* Submit's second half, shared with AlignLadders */
+	cvx_job submitPacked(Tile const * tiles, int n, cvx_ladder const * ladders);      /* Submit's second half, shared with SubmitLadders */
 	void fillAlign(Tile & t, cvx_alignment_text const & txt) const;
 	bool noAlignment(Tile & t, cvx_result const & r) const;
 	cvx_handle handle;
@@ -273,6 +291,22 @@ struct DeviceReads {
  * handles with the flag, the binding's allocation site writes a request instead of allocating the profile, and Finish answers
  * it.  CVX_DEVICE_REGIONS=0 turns all of it off inside the same binary: plain handles, no requests, the reference's loop.
  */
+/*
+ * computeAlignment's retry ladder as ONE request (ladder_binding.inc, in front of the loop at src/AlignmentBuffer.cpp:292).
+ *
+ * The binding reaches an aligner that can take it through this interface, found with dynamic_cast on ngmlr's IAlignment *: the
+ * IAlignment vtable stays as it is.  SingleLadder returns false, having done nothing, when the aligner cannot take ladders
+ * right now -- the caller then runs the reference's loop; otherwise `result` is filled as SingleAlign fills it for the rung
+ * reported, ret is that rung's return value (-1: its attempt failed), rung / attempts / width are cvx_job_ladder's record.
+ * Hard errors throw like SingleAlign's.
+ */
+class LadderAligner {
+public:
+	virtual ~LadderAligner() {}
+	virtual bool SingleLadder(char const * refSeq, char const * qrySeq, Align & result, int const externalQStart, int const externalQEnd,
+			cvx_ladder const & ladder, int & ret, int & rung, int & attempts, int & width) = 0;
+};
+
 struct DeviceRegions {
 	static void Announce();                /* the binding's finder site is compiled in */
 	static bool Enabled();                 /* announced, unless CVX_DEVICE_REGIONS=0 */

@@ -50,21 +50,28 @@ mkdir -p "$REPO/oracle/_ref"
 #                      computeAlignment allocates it, the peak finder's loop as a walk over the aligner's note (nm_regions_*_binding.inc,
 #                      ngmlr_amd/csrc/nm_regions_note.h; CVX_DEVICE_REGIONS=0 restores the profile inside the same binary)
 #   ngmlr_regions_cpu  the same two insertions around the reference's CPU aligner (tests/cpp/regions_cpu_aligner.h), no GPU
+#   ngmlr_hip_ladder   ngmlr_hip_regions + computeAlignment's retry loop as ONE request (ladder_binding.inc in front of the loop at
+#                      src/AlignmentBuffer.cpp:292, which stays as the fallback; Convex::LadderAligner, found with dynamic_cast): the
+#                      dispatcher gathers ladder launches, the device climbs; CVX_DEVICE_LADDER=0 restores ngmlr_hip_regions' behaviour
+#                      inside the same binary (tests/test_gpu_e2e_ladder.py)
+#   ngmlr_ladder_cpu   the same insertion around the reference's CPU aligner (tests/cpp/ladder_cpu_aligner.h), no GPU
+#                      (tests/test_ladder_binding_cpu.py)
 #   ngmlr_pool_parked  the same with a park / wake of the read's user-level context in front of every SingleAlign
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-} REGIONS=${12:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-} REGIONS=${12:-} LADDER=${13:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" "$REGIONS" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" "$REGIONS" "$LADDER" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 SCOREWIN = sys.argv[10]
 FEED = sys.argv[11]
 READSEG = sys.argv[12]
 REGIONS = sys.argv[13]
+LADDER = sys.argv[14]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -143,6 +150,17 @@ if REGIONS:
     s = open(p).read()
     s = sub1(s, '\t\tif (Config.getNoSSE()) {\n', ('\t\tif (%s) Convex::DeviceRegions::Announce();      /* cvx: this binary\'s detectMisalignment walks a note */\n\t\tif (Config.getNoSSE()) {\n'
              % ('!Config.getNoSSE()' if 'RegionsCpu' in CLASS else 'true')), 'AlignmentBuffer ctor (regions)')
+    open(p, 'w').write(s)
+if LADDER:
+    # computeAlignment's retry loop as one request to a Convex::LadderAligner (ngmlr_amd/csrc/ladder_binding.inc and
+    # ladder_binding_logic.h): `corridor` kept as it was passed, in front of the clamp, and the binding in front of the loop, which
+    # stays as it stands
+    assert CLASS != 'cpu'
+    p = T + '/src/AlignmentBuffer.cpp'
+    s = open(p).read()
+    s = sub1(s, '\t\t\tint const maxCorridorSize = refSeqLen * 2;\n', '\t\t\tint const cvxLadderCorridor = corridor;      /* cvx: before the clamp (ladder_binding.inc) */\n'
+             '\t\t\tint const maxCorridorSize = refSeqLen * 2;\n', 'corridor clamp')
+    s = sub1(s, '\t\t\tint corridorMultiplier = 1;\n\t\t\twhile (!validAlignment\n', '\t\t\tint corridorMultiplier = 1;\n#include "ladder_binding.inc"\n\t\t\twhile (!validAlignment\n', 'retry loop')
     open(p, 'w').write(s)
 if SEARCH:
     # the k-mer vote of a CS thread's batch on the device (ngmlr_amd/csrc/candidate_search_hip.h, cs_search_binding.inc)
@@ -287,7 +305,8 @@ if SCORER:
 if CLASS != 'cpu':
     p = T + '/src/AlignmentBuffer.h'
     s = open(p).read()
-    s = s.replace('#include "ConvexAlignFast.h"', '#include "ConvexAlignFast.h"\n#include "convex_align_hip.h"\n#include "batching_aligner.h"' + ('\n#include "parking_cpu_aligner.h"' if 'Parking' in CLASS else '') + ('\n#include "nm_regions_note.h"' if REGIONS else '') + ('\n#include "regions_cpu_aligner.h"' if 'RegionsCpu' in CLASS else ''), 1)
+    s = s.replace('#include "ConvexAlignFast.h"', '#include "ConvexAlignFast.h"\n#include "convex_align_hip.h"\n#include "batching_aligner.h"' + ('\n#include "parking_cpu_aligner.h"' if 'Parking' in CLASS else '') + ('\n#include "nm_regions_note.h"' if REGIONS else '') + ('\n#include "regions_cpu_aligner.h"' if 'RegionsCpu' in CLASS else '')
+                  + ('\n#include "ladder_binding_logic.h"' if LADDER else '') + ('\n#include "ladder_cpu_aligner.h"' if 'LadderCpu' in CLASS else ''), 1)
     pat = re.compile(r'aligner = new Convex::ConvexAlignFast\(', re.S)
     assert len(pat.findall(s)) == 1
     s = pat.sub('aligner = new %s(' % CLASS, s)
@@ -330,10 +349,12 @@ bv ngmlr_hip_feed Convex::SharedAligner StrippedSWHip sam pool search index "" s
 bv ngmlr_hip_readseg Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" readseg
 bv ngmlr_hip_regions Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions
 bv ngmlr_regions_cpu Convex::RegionsCpuAligner "" "" "" "" "" "" "" "" "" regions      # the reference's CPU aligner behind the request / note exchange (tests/cpp/regions_cpu_aligner.h)
+bv ngmlr_hip_ladder Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions ladder
+bv ngmlr_ladder_cpu Convex::LadderCpuAligner "" "" "" "" "" "" "" "" "" "" ladder      # the reference's CPU aligner behind Convex::LadderAligner (tests/cpp/ladder_cpu_aligner.h)
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_hip_regions ngmlr_regions_cpu ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_hip_regions ngmlr_regions_cpu ngmlr_hip_ladder ngmlr_ladder_cpu ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
