@@ -522,7 +522,7 @@ SharedAligner::SharedAligner(int const stdOutMode, float const match, float cons
 		if (const char * e = getenv("CVX_BATCH_MAX")) maxBatch = atoi(e);
 		if (const char * e = getenv("CVX_BATCH_TIMEOUT_US")) timeoutUs = atoi(e);
 		g_backend[device] = new ConvexAlignHip(stdOutMode, match, mismatch, gapOpen, gapExtend, gapExtendMin, gapDecay, nPhysical > 0 ? device % nPhysical : device, 0, scalarTwin,
-				DeviceRegions::Enabled(), DeviceRegions::Enabled() && (jobText || DeviceRegions::JobText()));   /* throws without a usable device; the regions of every launch come back with its results where a binding reads them */
+				DeviceRegions::Enabled(), DeviceRegions::Enabled() && (jobText || DeviceRegions::JobText()), DeviceInvChecks::Enabled());   /* throws without a usable device; the regions of every launch come back with its results where a binding reads them */
 		g_shared[device] = new BatchingAligner(g_backend[device], 0, maxBatch, timeoutUs);   /* workers join one by one */
 		/* with alignment contexts off the CS threads (align_pool.h) a launch waits for 256 tiles, 30 ms at most: hundreds of
 		 * contexts hide that wait, and the device sees a few large launches instead of many small ones (CVX_BATCH_TARGET /
@@ -589,6 +589,7 @@ SharedAligner::~SharedAligner() {
 			ConvexAlignHip::JobTextStats(fromDevice, onHost);
 			if (DeviceRegions::Enabled() && fromDevice + onHost > 0) fprintf(stderr, "SharedAligner: %ld alignments took their CIGAR and MD from the device, %ld were formatted on the host (CVX_JOB_TEXT=0 turns that off)\n", fromDevice, onHost);
 		}
+		if (DeviceInvChecks::Enabled()) fprintf(stderr, "SharedAligner: %ld alignments with regions came from launches without inversion checks (their windows were decoded on the host) and got a regions-only note\n", DeviceInvChecks::Stats().regionsOnlyAlignments);
 		if (g_lastTextLaunches > 0) fprintf(stderr, "SharedAligner: text stage on the device for %ld launches (cvx_job_text + cvx_job_nm_profile), %.3f s of the dispatchers' time\n", g_lastTextLaunches, g_lastTextSeconds);
 		fprintf(stderr, "SharedAligner: library loaded at 0, first worker joined at %.2f s, last one left at %.2f s\n",
 				std::chrono::duration<double>(g_firstJoin - g_loaded).count(), std::chrono::duration<double>(std::chrono::steady_clock::now() - g_loaded).count());

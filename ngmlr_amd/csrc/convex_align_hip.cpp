@@ -6,6 +6,7 @@
 #include "convex_align_hip.h"
 #include "cvx_fiber.h"
 #include "nm_regions_note.h"
+#include "inv_checks_binding_logic.h"
 
 #include <atomic>
 #include <cstdio>
@@ -156,6 +157,9 @@ namespace {
 std::atomic<bool> g_regionsAnnounced(false);
 std::atomic<long> g_noteAlignments(0), g_noteRegions(0), g_profileAlignments(0);
 bool const g_deviceRegions = [] { const char * e = getenv("CVX_DEVICE_REGIONS"); return !(e && atoi(e) == 0); }();
+/* (DeviceInvChecks, below: on only where the regions are) */
+bool const g_deviceInvChecks = [] { const char * e = getenv("CVX_DEVICE_INV_CHECKS"); return !(e && atoi(e) == 0); }();
+bool const g_invChecksVerify = [] { const char * e = getenv("CVX_INV_CHECKS_VERIFY"); return e && atoi(e) != 0; }();
 bool const g_jobText = [] { const char * e = getenv("CVX_JOB_TEXT"); return e && atoi(e) != 0; }();
 std::atomic<long> g_textFromDevice(0), g_textOnHost(0);
 }
@@ -172,6 +176,45 @@ void DeviceRegions::Stats(long & noteAlignments, long & noteRegions, long & prof
 	noteAlignments = g_noteAlignments.load();
 	noteRegions = g_noteRegions.load();
 	profileAlignments = g_profileAlignments.load();
+}
+
+/* ------------------------------------------------------------------ DeviceInvChecks */
+namespace {
+static_assert((int) kInvCheckScored == (int) CVX_CHECK_SCORED && (int) kInvCheckTooShort == (int) CVX_CHECK_TOO_SHORT &&
+		(int) kInvCheckNoRead == (int) CVX_CHECK_NO_READ && (int) kInvCheckNoWindow == (int) CVX_CHECK_NO_WINDOW, "the binding's logic reads cvx_inv_check's status");
+static_assert(sizeof(NmRegionsNote::Check) == sizeof(cvx_inv_check), "a checks note holds cvx_inv_check records");
+std::atomic<bool> g_invChecksAnnounced(false);
+std::atomic<long> g_invScored(0), g_invNoRead(0), g_invOwn[3], g_invVerified(0), g_invDisagreements(0), g_invRegionsOnly(0);
+/* the binding's exit line: once per process, from the copy of this file whose Announce was called */
+struct InvChecksExitLine {
+	~InvChecksExitLine() {
+		if (!g_invChecksAnnounced.load()) return;
+		DeviceInvChecks::Counts const c = DeviceInvChecks::Stats();
+		fprintf(stderr, "DeviceInvChecks: %ld checks taken from the job (%ld scored, %ld without a read part), %ld through checkForSV's own scoring "
+				"(%ld no window, %ld inconsistent record, %ld note without checks), %ld verified, %ld disagreements\n",
+				c.scored + c.noRead, c.scored, c.noRead, c.noWindow + c.inconsistent + c.noteWithoutChecks, c.noWindow, c.inconsistent, c.noteWithoutChecks,
+				c.verified, c.disagreements);
+	}
+} g_invChecksExitLine;
+}
+
+void DeviceInvChecks::Announce() { g_invChecksAnnounced.store(true); }
+bool DeviceInvChecks::Enabled() { return g_deviceInvChecks && g_invChecksAnnounced.load() && DeviceRegions::Enabled(); }
+bool DeviceInvChecks::Verify() { return g_invChecksVerify; }
+void DeviceInvChecks::CountTaken(bool scored) { (scored ? g_invScored : g_invNoRead).fetch_add(1, std::memory_order_relaxed); }
+void DeviceInvChecks::CountOwn(Own why) { g_invOwn[(int) why].fetch_add(1, std::memory_order_relaxed); }
+void DeviceInvChecks::CountVerified(bool agrees) {
+	g_invVerified.fetch_add(1, std::memory_order_relaxed);
+	if (!agrees) g_invDisagreements.fetch_add(1, std::memory_order_relaxed);
+}
+void DeviceInvChecks::CountRegionsOnly() { g_invRegionsOnly.fetch_add(1, std::memory_order_relaxed); }
+DeviceInvChecks::Counts DeviceInvChecks::Stats() {
+	Counts c;
+	c.scored = g_invScored.load(); c.noRead = g_invNoRead.load();
+	c.noWindow = g_invOwn[kNoWindow].load(); c.inconsistent = g_invOwn[kInconsistent].load(); c.noteWithoutChecks = g_invOwn[kNoteWithoutChecks].load();
+	c.verified = g_invVerified.load(); c.disagreements = g_invDisagreements.load();
+	c.regionsOnlyAlignments = g_invRegionsOnly.load();
+	return c;
 }
 
 void ConvexAlignHip::ReadStats(long & notedLaunches, long & notedTiles, long & mixedLaunches) {
@@ -198,7 +241,8 @@ void ConvexAlignHip::CorridorStats(long & prepared, long & closedForm) {
 
 ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float const mismatch,
 		float const gapOpen, float const gapExtend, float const gapExtendMin, float const gapDecay,
-		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin, bool const nmRegions, bool const jobText_) : handle(0), twin(scalarTwin), regions(nmRegions), jobText(jobText_), genome(0) {
+		int const deviceId, unsigned long const maxMatrixSizeMB, bool const scalarTwin, bool const nmRegions, bool const jobText_, bool const invChecks_) : handle(0), twin(scalarTwin), regions(nmRegions), jobText(jobText_),
+		invChecks(invChecks_ && nmRegions), genome(0) {
 	(void) stdOutMode;
 	cvx_params p;
 	p.match = match; p.mismatch = mismatch; p.gap_open = gapOpen;
@@ -209,7 +253,7 @@ ConvexAlignHip::ConvexAlignHip(int const stdOutMode, float const match, float co
 #endif
 	if (maxMatrixMB == 0) maxMatrixMB = 10000;      /* IConfig's default (src/IConfig.h:47) */
 	uint32_t const flags = (twin ? (uint32_t) CVX_CREATE_SCALAR_TWIN : 0u) | (regions ? (uint32_t) CVX_CREATE_NM_REGIONS : 0u) |
-			(jobText ? (uint32_t) CVX_CREATE_JOB_TEXT : 0u);
+			(jobText ? (uint32_t) CVX_CREATE_JOB_TEXT : 0u) | (invChecks ? (uint32_t) CVX_CREATE_INV_CHECKS : 0u);
 	if (cvx_create_ex(deviceId, &p, (uint64_t) maxMatrixMB, flags, &handle) != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
 		throw "ConvexAlignHip: no usable MI355X / unsupported scoring";
@@ -459,10 +503,15 @@ void ConvexAlignHip::Wait(cvx_job job, cvx_result const ** results, uint32_t con
 }
 
 bool ConvexAlignHip::Regions(cvx_job job, JobRegions & jr) {
-	jr.off = 0; jr.regions = 0;
+	jr.off = 0; jr.regions = 0; jr.checks = 0;
 	if (!regions) return false;
 	if (cvx_job_regions(handle, job, &jr.off, &jr.regions, 0) != CVX_OK) {
 		/* a request must never be answered with nothing: fail the launch like any other error of it */
+		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
+		throw 1;
+	}
+	/* the checks came back with the regions (no device call); NULL for a launch without the genome or without a region */
+	if (invChecks && cvx_job_checks(handle, job, &jr.checks) != CVX_OK) {
 		fprintf(stderr, "ConvexAlignHip: %s\n", cvx_last_error());
 		throw 1;
 	}
@@ -689,12 +738,7 @@ void ConvexAlignHip::Finish(Tile & t, cvx_result const & r, uint32_t const * ops
 		if (!again) break;
 	}
 	if (fromRequest) NmRegionsNote::CoverScan(a.nmPerPosition, a.nmPerPostionLength, txt.nm_count, txt.alignment_length);
-	if (asNote) {
-		static_assert(sizeof(NmRegionsNote::Region) == sizeof(cvx_nm_region), "a note holds cvx_nm_region records");
-		int const count = (int) (jr->off[index + 1] - jr->off[index]);
-		NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr->regions + jr->off[index]) : 0;
-		NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
-	}
+	if (asNote) putNote(a, *jr, index);
 	if (txt.cigar_len > a.maxBufferLength) {
 		fprintf(stderr, "CIGAR/MD buffer not long enough (%d %d > %d %d). Please report this!\n",
 				txt.cigar_len, txt.md_len, a.maxBufferLength, a.maxMdBufferLength);
@@ -720,15 +764,27 @@ void ConvexAlignHip::FinishJobText(Tile & t, JobTextView const & jx, JobRegions 
 		throw 1;
 	}
 	memcpy(a.pBuffer2, src + rec.cigar_len + 1, (size_t) rec.md_len + 1);
-	int const count = (int) (jr.off[index + 1] - jr.off[index]);
-	NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr.regions + jr.off[index]) : 0;
-	NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
+	putNote(a, jr, index);
 	if (txt.cigar_len > a.maxBufferLength) {
 		fprintf(stderr, "CIGAR/MD buffer not long enough (%d %d > %d %d). Please report this!\n",
 				txt.cigar_len, txt.md_len, a.maxBufferLength, a.maxMdBufferLength);
 		throw 1;
 	}
 	fillAlign(t, txt);
+}
+
+/* the answer to a request: the tile's regions, and -- where the binding reads them and the job brought them -- their check records
+ * behind them; a job without checks (its windows were materialised on the host) answers with the regions-only note */
+void ConvexAlignHip::putNote(Align & a, JobRegions const & jr, int index) const {
+	static_assert(sizeof(NmRegionsNote::Region) == sizeof(cvx_nm_region), "a note holds cvx_nm_region records");
+	int const count = (int) (jr.off[index + 1] - jr.off[index]);
+	NmRegionsNote::Region const * mine = count > 0 ? reinterpret_cast<NmRegionsNote::Region const *>(jr.regions + jr.off[index]) : 0;
+	if (jr.checks != 0 && DeviceInvChecks::Enabled()) {
+		NmRegionsNote::PutChecks(a.nmPerPosition, a.nmPerPostionLength, mine, reinterpret_cast<NmRegionsNote::Check const *>(jr.checks + jr.off[index]), count);
+		return;
+	}
+	if (count > 0 && invChecks && DeviceInvChecks::Enabled()) DeviceInvChecks::CountRegionsOnly();
+	NmRegionsNote::Put(a.nmPerPosition, a.nmPerPostionLength, mine, count);
 }
 
 void ConvexAlignHip::fillAlign(Tile & t, cvx_alignment_text const & txt) const {

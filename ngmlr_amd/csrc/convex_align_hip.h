@@ -32,7 +32,12 @@ public:
 	ConvexAlignHip(int const stdOutMode, float const match, float const mismatch, float const gapOpen,
 			float const gapExtend, float const gapExtendMin, float const gapDecay, int const deviceId = 0,
 			unsigned long const maxMatrixSizeMB = 0 /* Config.getMaxMatrixSizeMB(); 0 = the reference's default 10000 */,
-			bool const scalarTwin = false, bool const nmRegions = false, bool const jobText = false);
+			bool const scalarTwin = false, bool const nmRegions = false, bool const jobText = false, bool const invChecks = false);
+	/* invChecks: the handle is created with CVX_CREATE_INV_CHECKS (only together with nmRegions; alone it is ignored) -- every launch
+	 * that travelled with the resident genome brings checkForSV's two scores per region back beside its regions (cvx_job_checks),
+	 * and, where DeviceInvChecks::Enabled(), Finish answers a request with the checks form of the note (nm_regions_note.h).  A launch
+	 * that materialised its windows on the host brings none: its requests get today's regions-only note. */
+	bool InvChecks() const { return invChecks; }
 	/* jobText: the handle is created with CVX_CREATE_JOB_TEXT -- every launch brings CIGAR, MD and the scalar fields of its tiles back
 	 * with its results (external clips zero), and Finish copies them (FinishJobText) for every tile whose request it answers with a
 	 * note instead of walking the tile's ops; a tile that wants its profile keeps the host form, in the same launch. */
@@ -151,10 +156,12 @@ public:
 	bool Poll(cvx_job job);       /* true: Wait would not block (also keeps queued launches moving) */
 	void Wait(cvx_job job, cvx_result const ** results, uint32_t const ** ops);
 	/* the regions of a finished job (cvx_job_regions: the job's page-locked memory, valid until Release); tile i owns
-	 * regions[off[i] .. off[i + 1]) */
+	 * regions[off[i] .. off[i + 1]); checks (cvx_job_checks, the same memory and lifetime): the check record of every region, parallel
+	 * to `regions` -- NULL where the handle delivers none, the job travelled without a genome, or the job has no region */
 	struct JobRegions {
 		uint64_t const * off;
 		cvx_nm_region const * regions;
+		cvx_inv_check const * checks = 0;
 	};
 	bool Regions(cvx_job job, JobRegions & jr);      /* after Wait.  false: the handle delivers none (throws 1 when one that should cannot) */
 	/* jr / index: the launch's regions and the tile's place in it.  With them a request (or an earlier note) in
@@ -211,10 +218,12 @@ private:
 	cvx_job submitPacked(Tile const * tiles, int n, cvx_ladder const * ladders);      /* Submit's second half, shared with SubmitLadders */
 	void fillAlign(Tile & t, cvx_alignment_text const & txt) const;
 	bool noAlignment(Tile & t, cvx_result const & r) const;
+	void putNote(Align & a, JobRegions const & jr, int index) const;      /* the note of tile `index`: with its checks where the job brought them */
 	cvx_handle handle;
 	bool twin;
 	bool regions;
 	bool jobText;
+	bool invChecks;
 	unsigned long maxMatrixMB;
 	std::vector<cvx_tile> packed;
 	cvx_genome genome;                     /* DeviceWindows' genome on this aligner's device (uploaded by the first launch that carries a window) */
@@ -315,6 +324,33 @@ struct DeviceRegions {
 	static void CountNote(int regions);
 	static void CountProfile();
 	static void Stats(long & noteAlignments, long & noteRegions, long & profileAlignments);
+};
+
+/*
+ * checkForSV on the scores its job brought (inv_checks_binding.inc, inv_checks_binding_logic.h; CVX_CREATE_INV_CHECKS).
+ *
+ * Every region detectMisalignment keeps costs its read's context a window decode, a copy, a reverse complement and two
+ * StrippedSW::SingleScore calls (reference src/AlignmentBuffer.cpp:1195-1225).  A job of a handle with the flag has scored them
+ * already.  A binding whose checkForSV reads a record announces itself beside the regions binding; SharedAligner then creates its
+ * handles with the flag, Finish writes the checks form of the note, the finder site offers region k's record to the checkForSV
+ * call of region k.  CVX_DEVICE_INV_CHECKS=0 (or CVX_DEVICE_REGIONS=0) turns all of it off inside the same binary: handles without
+ * the flag, regions-only notes, the reference's scoring.  CVX_INV_CHECKS_VERIFY=1 runs the reference's scoring beside every
+ * record, compares and uses the reference's result.  One line on stderr when the process ends (announced binaries only).
+ */
+struct DeviceInvChecks {
+	static void Announce();                /* the binding's checkForSV site is compiled in */
+	static bool Enabled();                 /* announced, DeviceRegions::Enabled(), and not CVX_DEVICE_INV_CHECKS=0 */
+	static bool Verify();                  /* CVX_INV_CHECKS_VERIFY=1 */
+	/* checkForSV: a record was taken (scored: its two scores; else it said that no read part exists) */
+	static void CountTaken(bool scored);
+	/* checkForSV: the reference's own scoring ran although the binding is on */
+	enum Own { kNoWindow = 0, kInconsistent = 1, kNoteWithoutChecks = 2 };
+	static void CountOwn(Own why);
+	static void CountVerified(bool agrees);
+	/* the aligner: an alignment with regions whose launch brought no checks got a regions-only note while the binding is on */
+	static void CountRegionsOnly();
+	struct Counts { long scored, noRead, noWindow, inconsistent, noteWithoutChecks, verified, disagreements, regionsOnlyAlignments; };
+	static Counts Stats();
 };
 
 }  // namespace Convex

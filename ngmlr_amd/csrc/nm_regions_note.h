@@ -10,10 +10,15 @@
  *   request   row 0 = (kMagicRef, kMagicRead, kRequest): "the caller wants regions, not a profile".
  *   note      row 0 = (kMagicRef, kMagicRead, -1 - n), then n regions of four ints each, packed from row 1 on:
  *             what ConvexAlignHip::Finish writes over a request after a valid alignment.
+ *   checks    row 0 = (kMagicRef, kMagicRead, kChecksBase - n), then the n regions as in a note and behind them n check records
+ *   note      of 16 bytes each, in the same order (Check: the layout of cvx_inv_check): what Finish writes when the job brought
+ *             the inversion checks of its regions (Convex::DeviceInvChecks, convex_align_hip.h).  A regions-only header lies in
+ *             [-1 - INT32_MAX / 8, -1], a checks header in [kChecksBase - INT32_MAX / 8, kChecksBase], the request is INT32_MIN:
+ *             the third int alone tells the three apart, and IsNote never takes a checks note (nor IsChecksNote a note).
  *
  * A row of a profile is (refPosition, readPosition, nm) with both positions >= 1 and 0 <= nm <= 32 (addPosition,
  * src/ConvexAlignFast.cpp:76-98), a fresh buffer is zeros: neither has a negative first row, so neither is ever taken for a
- * request or a note.  Rows are three ints (PositionNM, src/IAlignment.h:16-21); this header knows neither that type nor
+ * request or a note of either form.  Rows are three ints (PositionNM, src/IAlignment.h:16-21); this header knows neither that type nor
  * HIP nor the library's own headers.
  */
 #ifndef NM_REGIONS_NOTE_H
@@ -29,9 +34,13 @@ struct NmRegionsNote {
 	static int32_t const kMagicRef = -0x4E4D5247;       /* "NMRG", negated */
 	static int32_t const kMagicRead = -0x4E4F5445;      /* "NOTE", negated */
 	static int32_t const kRequest = INT32_MIN;
+	struct Check { float scoreFwd, scoreRev; int32_t status, windowChars; };      /* the layout of cvx_inv_check */
+	static int32_t const kChecksBase = -0x40000000;
 
 	/* rows (12 bytes each) a note of n regions takes: the header and 4 n ints */
 	static int RowsFor(int n) { return 1 + (4 * n + 2) / 3; }
+	/* rows a checks note of n regions takes: the header, 4 n ints of regions and 4 n ints of check records */
+	static int RowsForChecks(int n) { return 1 + (8 * n + 2) / 3; }
 	/* rows: the buffer (capRows >= 1 rows of three ints) */
 	static void Request(void * rows) {
 		int32_t const head[3] = { kMagicRef, kMagicRead, kRequest };
@@ -54,10 +63,21 @@ struct NmRegionsNote {
 		n = (int) count;
 		return true;
 	}
-	/* a request, or the note an earlier alignment into the same buffer left: either way the caller wants regions */
+	/* true: the buffer holds a checks note (whole, as for IsNote); n = its regions, each with a check record */
+	static bool IsChecksNote(void const * rows, int capRows, int & n) {
+		int32_t head[3];
+		if (rows == 0 || capRows < 1) return false;
+		memcpy(head, rows, sizeof(head));
+		if (head[0] != kMagicRef || head[1] != kMagicRead || head[2] > kChecksBase || head[2] == kRequest) return false;
+		int64_t const count = (int64_t) kChecksBase - (int64_t) head[2];
+		if (count > (int64_t) (INT32_MAX / 8) || RowsForChecks((int) count) > capRows) return false;
+		n = (int) count;
+		return true;
+	}
+	/* a request, or the note (of either form) an earlier alignment into the same buffer left: either way the caller wants regions */
 	static bool Wanted(void const * rows, int capRows) {
 		int n = 0;
-		return IsRequest(rows, capRows) || IsNote(rows, capRows, n);
+		return IsRequest(rows, capRows) || IsNote(rows, capRows, n) || IsChecksNote(rows, capRows, n);
 	}
 	/* false (nothing written): the buffer is too small, the caller grows it to RowsFor(n) rows and writes again */
 	static bool Write(void * rows, int capRows, Region const * regions, int n) {
@@ -67,7 +87,24 @@ struct NmRegionsNote {
 		if (n > 0) memcpy((char *) rows + sizeof(head), regions, (size_t) n * sizeof(Region));
 		return true;
 	}
-	/* region i of a note (IsNote said so); copied out: the rows are aligned for ints, not for anything wider */
+	/* the checks note: as Write, with checks[i] the record of regions[i] */
+	static bool WriteChecks(void * rows, int capRows, Region const * regions, Check const * checks, int n) {
+		if (rows == 0 || n < 0 || n > INT32_MAX / 8 || RowsForChecks(n) > capRows || (n > 0 && (regions == 0 || checks == 0))) return false;
+		int32_t const head[3] = { kMagicRef, kMagicRead, kChecksBase - n };
+		memcpy(rows, head, sizeof(head));
+		if (n > 0) {
+			memcpy((char *) rows + sizeof(head), regions, (size_t) n * sizeof(Region));
+			memcpy((char *) rows + sizeof(head) + (size_t) n * sizeof(Region), checks, (size_t) n * sizeof(Check));
+		}
+		return true;
+	}
+	/* the check record of region i of a checks note of n regions (IsChecksNote said so); its regions are read with At */
+	static Check CheckAt(void const * rows, int n, int i) {
+		Check c;
+		memcpy(&c, (char const *) rows + 3 * sizeof(int32_t) + (size_t) n * sizeof(Region) + (size_t) i * sizeof(Check), sizeof(c));
+		return c;
+	}
+	/* region i of a note of either form (IsNote / IsChecksNote said so); copied out: the rows are aligned for ints, not for anything wider */
 	static Region At(void const * rows, int i) {
 		Region r;
 		memcpy(&r, (char const *) rows + 3 * sizeof(int32_t) + (size_t) i * sizeof(Region), sizeof(r));
@@ -78,6 +115,7 @@ struct NmRegionsNote {
 	static void Clear(void * rows, int capRows) {
 		int n = 0;
 		if (IsNote(rows, capRows, n)) memset(rows, 0, (size_t) RowsFor(n) * 3 * sizeof(int32_t));
+		else if (IsChecksNote(rows, capRows, n)) memset(rows, 0, (size_t) RowsForChecks(n) * 3 * sizeof(int32_t));
 		else if (IsRequest(rows, capRows)) memset(rows, 0, 3 * sizeof(int32_t));
 	}
 	/* What an aligner does with the buffer once it has a VALID alignment (an invalid one touches nothing: the request stays for
@@ -134,6 +172,20 @@ struct NmRegionsNote {
 			capRows = cap;
 		}
 		(void) Write(rows, capRows, regions, n);
+	}
+	/* the checks note into the caller's buffer, grown by Put's rule */
+	template <typename Row>
+	static void PutChecks(Row * & rows, int & capRows, Region const * regions, Check const * checks, int n) {
+		static_assert(sizeof(Row) == 3 * sizeof(int32_t), "a profile row is three ints");
+		int const need = RowsForChecks(n);
+		if (need > capRows) {
+			int cap = capRows > 0 ? capRows : 64;
+			while (cap < need) cap *= 2;
+			delete[] rows;
+			rows = new Row[cap];
+			capRows = cap;
+		}
+		(void) WriteChecks(rows, capRows, regions, checks, n);
 	}
 };
 

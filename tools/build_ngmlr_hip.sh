@@ -56,15 +56,23 @@ mkdir -p "$REPO/oracle/_ref"
 #                      inside the same binary (tests/test_gpu_e2e_ladder.py)
 #   ngmlr_ladder_cpu   the same insertion around the reference's CPU aligner (tests/cpp/ladder_cpu_aligner.h), no GPU
 #                      (tests/test_ladder_binding_cpu.py)
+#   ngmlr_hip_invchecks ngmlr_hip_regions + checkForSV on the two scores its job brought: handles with CVX_CREATE_INV_CHECKS, the checks form of
+#                      the note (nm_regions_note.h), region k's record offered by the finder's walk to the checkForSV call of region k
+#                      (a member the script adds to AlignmentBuffer), and in checkForSV the record's scores in front of the reference's
+#                      decision, which the script moves into a lambda both paths call (inv_checks_binding.inc, inv_checks_binding_logic.h);
+#                      CVX_DEVICE_INV_CHECKS=0 restores ngmlr_hip_regions' behaviour inside the same binary, CVX_INV_CHECKS_VERIFY=1 runs the
+#                      reference's scoring beside every record and compares (tests/test_gpu_e2e_invchecks.py).  Nobody's default.
+#   ngmlr_invchecks_cpu ngmlr_regions_cpu + the same insertions, the records filled in at the finder site from the host rule
+#                      (tests/cpp/inv_checks_cpu_source.h), no GPU (tests/test_inv_checks_binding_cpu.py)
 #   ngmlr_pool_parked  the same with a park / wake of the read's user-level context in front of every SingleAlign
 #                      (tests/cpp/parking_cpu_aligner.h): the fiber runtime under ngmlr's own long-read stage, no GPU
 #   ngmlr_ref          (nothing changed)       the unmodified reference, for wall-clock comparison only
 build_variant() {
-local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-} REGIONS=${12:-} LADDER=${13:-}
+local OUT_NAME=$1 CLASS=$2 SCORER=${3:-} SAM=${4:-} POOL=${5:-} SEARCH=${6:-} INDEX=${7:-} CHECKS=${8:-} SCOREWIN=${9:-} FEED=${10:-} READSEG=${11:-} REGIONS=${12:-} LADDER=${13:-} INVCHECKS=${14:-}
 local T="$WORK/$OUT_NAME"
 cp -r /root/reference "$T"
 if [ "$CLASS" != "unmodified" ]; then
-python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" "$REGIONS" "$LADDER" <<'PY'
+python3 - "$T" "$REPO" "$CLASS" "$SCORER" "$SAM" "$POOL" "$SEARCH" "$INDEX" "$CHECKS" "$SCOREWIN" "$FEED" "$READSEG" "$REGIONS" "$LADDER" "$INVCHECKS" <<'PY'
 import re, sys
 T, REPO, CLASS, SCORER, SAM, POOL, SEARCH, INDEX, CHECKS = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6], sys.argv[7], sys.argv[8], sys.argv[9]
 SCOREWIN = sys.argv[10]
@@ -72,6 +80,7 @@ FEED = sys.argv[11]
 READSEG = sys.argv[12]
 REGIONS = sys.argv[13]
 LADDER = sys.argv[14]
+INVCHECKS = sys.argv[15]
 def sub1(s, old, new, what):
     assert s.count(old) == 1, (what, s.count(old))
     return s.replace(old, new, 1)
@@ -86,13 +95,15 @@ if CHECKS:
     s = open(p).read()
     s = sub1(s, 'IAlignment * lqCheckAligner = new StrippedSW();', 'IAlignment * lqCheckAligner = new Convex::SharedScorer(Convex::SharedScorer::kInversionCheck);', 'inversion check')
     open(p, 'w').write(s)
-if INDEX:
-    # the k-mer table built by cvx_index_build (ngmlr_amd/csrc/index_build_binding.inc at the top of CompactPrefixTable::CreateTable)
+if INDEX or (INVCHECKS and 'RegionsCpu' in CLASS):
+    # (the accessor alone where only tests/cpp/inv_checks_cpu_source.h reads the genome)
     p = T + '/src/SequenceProvider.h'
     s = open(p).read()
     s = sub1(s, '\tChromosome getChrStart(uloc const position);\n', '\tChromosome getChrStart(uloc const position);\n\t/* the 4-bit genome as Init built it (read access for cvx_index_build) */\n'
              '\tchar const * cvxBinRef() const { return binRef; }\n', 'SequenceProvider.h accessor')
     open(p, 'w').write(s)
+if INDEX:
+    # the k-mer table built by cvx_index_build (ngmlr_amd/csrc/index_build_binding.inc at the top of CompactPrefixTable::CreateTable)
     p = T + '/src/PrefixTable.cpp'
     s = open(p).read()
     s = sub1(s, '#include "PrefixTable.h"', '#include "PrefixTable.h"\n#include <vector>\n#include <stdlib.h>\n#include <string.h>\n#include <stdint.h>\n#include "cvx_align.h"', 'PrefixTable.cpp includes')
@@ -150,6 +161,41 @@ if REGIONS:
     s = open(p).read()
     s = sub1(s, '\t\tif (Config.getNoSSE()) {\n', ('\t\tif (%s) Convex::DeviceRegions::Announce();      /* cvx: this binary\'s detectMisalignment walks a note */\n\t\tif (Config.getNoSSE()) {\n'
              % ('!Config.getNoSSE()' if 'RegionsCpu' in CLASS else 'true')), 'AlignmentBuffer ctor (regions)')
+    open(p, 'w').write(s)
+if INVCHECKS:
+    # checkForSV on the scores its job brought (ngmlr_amd/csrc/inv_checks_binding.inc and inv_checks_binding_logic.h, Convex::DeviceInvChecks in
+    # convex_align_hip.h; CVX_DEVICE_INV_CHECKS=0 turns it off): the reference's decision (src/AlignmentBuffer.cpp:1230-1236) moved, as it
+    # stands, into a lambda at the top of the branch -- with the constant it reads (:1221) -- which the reference's path calls where the
+    # lines stood and the binding calls on a record's scores; the finder's walk (REGIONS, above) offers the records through a member
+    assert REGIONS
+    p = T + '/src/AlignmentBuffer.cpp'
+    s = open(p).read()
+    a = s.index('int AlignmentBuffer::checkForSV(')
+    b = s.index('int AlignmentBuffer::detectMisalignment(')
+    f = s[a:b]
+    first, last = '\t\t\tif ((scoreRev / scoreFwd) > Config.getInvScoreRatio() && scoreRev > minScore) {\n', '\t\t\t\tsvType = SV_TRANSLOCATION;\n\t\t\t}\n'
+    assert f.count(first) == 1 and f.count(last) == 1, 'checkForSV decision'
+    d0, d1 = f.index(first), f.index(last) + len(last)
+    assert d0 < d1
+    decision = f[d0:d1]
+    f = f[:d0] + '\t\t\tcvxOwnScored = true; cvxOwnFwd = scoreFwd; cvxOwnRev = scoreRev;\n\t\t\tcvxDecide(scoreFwd, scoreRev);\n' + f[d1:]
+    m = re.search(r'^[ \t]*static const float minScore = [^;\n]*;\n', f, re.M)
+    assert m and f.count('static const float minScore =') == 1, 'checkForSV minScore'
+    min_score = m.group(0)
+    f = f[:m.start()] + f[m.end():]
+    f = sub1(f, '\tif (inversionLength > minInversionLength) {\n', '\tif (inversionLength > minInversionLength) {\n' + min_score +
+             '\t\tauto cvxDecide = [&](float const scoreFwd, float const scoreRev) {\n' + decision + '\t\t};\n'
+             '#define CVX_INV_CHECKS_SITE 1\n#include "inv_checks_binding.inc"\n#undef CVX_INV_CHECKS_SITE\n', 'checkForSV branch')
+    f = sub1(f, '\t\tdelete[] refSeq;\n\t\trefSeq = 0;\n\t\tdelete[] readSeq;\n', '#define CVX_INV_CHECKS_SITE 2\n#include "inv_checks_binding.inc"\n#undef CVX_INV_CHECKS_SITE\n'
+             '\t\tdelete[] refSeq;\n\t\trefSeq = 0;\n\t\tdelete[] readSeq;\n', 'checkForSV end of scoring')
+    s = s[:a] + f + s[b:]
+    open(p, 'w').write(s)
+    p = T + '/src/AlignmentBuffer.h'
+    s = open(p).read()
+    m = re.search(r'^[ \t]*int checkForSV\([^;]*;\n', s, re.M)
+    assert m and len(re.findall(r'\bint checkForSV\(', s)) == 1, 'checkForSV declaration'
+    s = s[:m.end()] + '\t/* cvx (nm_regions_finder_binding.inc, inv_checks_binding.inc): the check record of the region the next checkForSV call is about */\n\tConvex::InvCheckSlot cvxInvCheck;\n' + s[m.end():]
+    s = sub1(s, 'Convex::DeviceRegions::Announce();', 'Convex::DeviceRegions::Announce(), Convex::DeviceInvChecks::Announce();', 'AlignmentBuffer ctor (inversion checks)')
     open(p, 'w').write(s)
 if LADDER:
     # computeAlignment's retry loop as one request to a Convex::LadderAligner (ngmlr_amd/csrc/ladder_binding.inc and
@@ -306,7 +352,8 @@ if CLASS != 'cpu':
     p = T + '/src/AlignmentBuffer.h'
     s = open(p).read()
     s = s.replace('#include "ConvexAlignFast.h"', '#include "ConvexAlignFast.h"\n#include "convex_align_hip.h"\n#include "batching_aligner.h"' + ('\n#include "parking_cpu_aligner.h"' if 'Parking' in CLASS else '') + ('\n#include "nm_regions_note.h"' if REGIONS else '') + ('\n#include "regions_cpu_aligner.h"' if 'RegionsCpu' in CLASS else '')
-                  + ('\n#include "ladder_binding_logic.h"' if LADDER else '') + ('\n#include "ladder_cpu_aligner.h"' if 'LadderCpu' in CLASS else ''), 1)
+                  + ('\n#define CVX_INV_CHECKS_BINDING 1\n#include "inv_checks_binding_logic.h"' if INVCHECKS else '') + ('\n#include "inv_checks_cpu_source.h"' if INVCHECKS and 'RegionsCpu' in CLASS else '')
+              + ('\n#include "ladder_binding_logic.h"' if LADDER else '') + ('\n#include "ladder_cpu_aligner.h"' if 'LadderCpu' in CLASS else ''), 1)
     pat = re.compile(r'aligner = new Convex::ConvexAlignFast\(', re.S)
     assert len(pat.findall(s)) == 1
     s = pat.sub('aligner = new %s(' % CLASS, s)
@@ -349,12 +396,14 @@ bv ngmlr_hip_feed Convex::SharedAligner StrippedSWHip sam pool search index "" s
 bv ngmlr_hip_readseg Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" readseg
 bv ngmlr_hip_regions Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions
 bv ngmlr_regions_cpu Convex::RegionsCpuAligner "" "" "" "" "" "" "" "" "" regions      # the reference's CPU aligner behind the request / note exchange (tests/cpp/regions_cpu_aligner.h)
+bv ngmlr_hip_invchecks Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions "" invchecks
+bv ngmlr_invchecks_cpu Convex::RegionsCpuAligner "" "" "" "" "" "" "" "" "" regions "" invchecks      # the binding without a GPU: records from the host rule at the finder site (tests/cpp/inv_checks_cpu_source.h)
 bv ngmlr_hip_ladder Convex::SharedAligner StrippedSWHip sam pool search index "" "" "" "" regions ladder
 bv ngmlr_ladder_cpu Convex::LadderCpuAligner "" "" "" "" "" "" "" "" "" "" ladder      # the reference's CPU aligner behind Convex::LadderAligner (tests/cpp/ladder_cpu_aligner.h)
 bv ngmlr_index_cpu cpu "" "" "" "" index
 bv ngmlr_ref unmodified      # the reference as it is: wall-clock yardstick of tools/e2e_rates.py
 wait
-for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_hip_regions ngmlr_regions_cpu ngmlr_hip_ladder ngmlr_ladder_cpu ngmlr_index_cpu ngmlr_ref; do
+for v in ngmlr_hip ngmlr_hip_batched ngmlr_hip_full ngmlr_sam ngmlr_hip_pool ngmlr_pool_cpu ngmlr_pool_parked ngmlr_hip_all ngmlr_hip_checks ngmlr_hip_scorewin ngmlr_hip_feed ngmlr_hip_readseg ngmlr_hip_regions ngmlr_regions_cpu ngmlr_hip_invchecks ngmlr_invchecks_cpu ngmlr_hip_ladder ngmlr_ladder_cpu ngmlr_index_cpu ngmlr_ref; do
 	test -x "$REPO/oracle/_ref/$v" || { echo "missing oracle/_ref/$v"; exit 1; }
 done
 readelf -d "$REPO/oracle/_ref/ngmlr_hip" | grep -E "RPATH|RUNPATH|NEEDED" | head
